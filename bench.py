@@ -10,9 +10,11 @@ synthetic and resident in HBM before the timed region.  Multi-GPU: one process
 per GPU (torch.distributed / RCCL), brick partition with one ghost-cell layer,
 weak scaling (64^3 cells per GPU), forward halo overlapped with interior cells.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         (N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run measures the headline only (set-up, W warm-up cycles, K timed
+cycles); --full adds every other measurement and check the line can carry (roofline, graph replay, CPU baseline
+and parity, extra configurations, the multi-rank gate).
 """
 from __future__ import annotations
 
@@ -207,7 +209,35 @@ def parse_args(argv=None):
                     help="skip the BASELINE config-5 measurement (p = 6 -> 3 -> 1 with the AMG coarse solve)")
     ap.add_argument("--mesh-sweep", action="store_true",
                     help="N = 1: PCG iteration counts at 32^3 / 64^3 / 96^3 with a random right-hand side")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: the replayed cycle, the kernel "
+                         "roofline, the coarse-solve, PCG, config-5, affine and degree-sweep measurements, the CPU "
+                         "baseline and its parity check, and on several ranks the strong-scaling block with its gate "
+                         "against the C oracle.  Without it a run sets up, warms up, times --steps cycles and prints "
+                         "the headline; the --no-* / --extras / --mesh-sweep / --graph-exchange / --corrupt-halo "
+                         "options act on --full runs only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed cycles, write what they computed to DIR/<name>.npy (float64): the iterate x "
+                         f"after the last timed cycle, owned fine-level entries, sampled at {DUMP_ENTRIES} fixed "
+                         "positions (numpy default_rng(0), sorted) shared out over the ranks -- 'x.npy' on one rank, "
+                         "'x_rank<r>.npy' on several")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up")
+    return args
+
+
+DUMP_ENTRIES = 4 << 20  # float64 entries --dump-outputs writes over all ranks: 32 MB
+
+
+def dump_indices(n, budget, seed=0):
+    """Positions of the --dump-outputs sample of an output of n entries: all of them if they fit the budget, else
+    `budget` distinct positions drawn with a fixed seed, in increasing order (the same for the same n)."""
+    import numpy as np
+
+    if n <= budget:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=budget, replace=False))
 
 
 class LaunchError(SystemExit):
@@ -443,6 +473,97 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = fine_dofs_global * args.steps / elapsed
     counts = H.mg.apply_counts()
+    if args.dump_outputs:  # before anything below runs another cycle on x
+        watch["phase"] = "writing the outputs"
+        xo = x.data_copy()[: H.levels[-1].size_local]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "x.npy" if world == 1 else f"x_rank{rank}.npy"),
+                xo[dump_indices(xo.size, DUMP_ENTRIES // world)])
+        del xo
+
+    if not multi:
+        exchange_note = "none (single rank)"
+    elif comm is None:
+        exchange_note = comm_note or "torch.distributed callbacks"
+    elif args.comm == "windows":
+        exchange_note = ("library communicator made of windows: halo and reductions as direct stores into IPC-mapped "
+                         "device memory, no transport library")
+    elif args.halo == "windows":
+        exchange_note = ("library halo windows (direct stores into the neighbours' IPC-mapped memory), RCCL device "
+                         "all-reduce")
+    else:
+        exchange_note = "library RCCL communicator (grouped send/recv, device all-reduce)"
+    out = {
+        "metric": "DoFs/sec per p-MG V-cycle (Poisson, hex, p=4)",
+        "value": value,
+        "unit": "DoF/s",
+        "n_gpus": 1 if args.share_gpu else world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"Poisson p={P} V-cycle p=" + "->".join(str(p) for p in reversed(orders))
+                        + f", Chebyshev({args.cheb})/Jacobi, {args.n}^3 hexes per GPU" if args.scaling == "weak"
+                        else f"Poisson p={P} V-cycle, {args.n}^3 hexes total",
+            "cells_global": list(n_global),
+            "fine_dofs_global": fine_dofs_global,
+            "levels": list(reversed(orders)),
+            "cheb_iterations": args.cheb,
+            "partition": "x".join(str(d) for d in dims) + " bricks, 1 ghost-cell layer",
+            "exchange": exchange_note,
+            "stiffness_launches_per_cycle": {f"p{p}": c for p, c in zip(orders, counts)},
+            # ranks of the communicator the halo and the reductions really ran on (pmg_comm_size of the library's
+            # RCCL communicator, or torch.distributed's RCCL group on the callback route); 1 = no communicator
+            "rccl_ranks": rccl_ranks if args.comm == "rccl" else 0,
+            # the same for whichever communicator carried the run (RCCL or the one made of windows)
+            "comm_ranks": rccl_ranks,
+            # a halo exchange captured into a hipGraph keeps its overlap with the interior cells only on a HIP >= 7.2
+            # runtime (profiles/rccl_capture_probe_r03.md); a Python process runs on PyTorch's bundled runtime
+            "captured_exchange_overlaps": bool(pm._lib.lib().pmg_comm_capture_overlaps()) if multi else None,
+        },
+    }
+    watch["out"] = out
+    watch["phase"] = "after the headline"
+    if args.share_gpu:
+        out["rehearsal"] = (f"{world} ranks SHARE ONE GPU (--share-gpu): a rehearsal of the multi-rank path with real "
+                            "inter-process exchanges, not a multi-GPU measurement; `value` is the aggregate of the "
+                            "ranks time-slicing that GPU")
+        out["ranks"] = world
+
+    def emit(failures):
+        """The ONE line (rank 0): a failed check takes its `value` away (finish_line)."""
+        finish_line(out, failures)
+        if deadline > 0:
+            timer.cancel()
+        if rank == 0:
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        os.close(json_fd)
+
+    def release():
+        """After the library objects are gone: let the runtime finish them while it is still up, then leave the group."""
+        import gc
+
+        gc.collect()
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # the headline alone: everything below measures or checks something else
+        if multi:
+            out["parity"] = {"gate": "unverified: the strong-scaling block and its gate against the C oracle run with "
+                                     "--full"}
+        emit([])
+        del H, x, b
+        comm = None
+        release()
+        return
+
     # the same K cycles replayed as a hipGraph (one launch per cycle instead of ~120; single rank only)
     graph_ms = None
     if not multi or (args.graph_exchange and comm is not None):
@@ -537,61 +658,7 @@ def main():
                 "replay_frac": round(alg_bytes / (replay_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                 "cells_per_launch": ncells_launch,
                 "launches_per_apply": nlaunch, "apply_ms": round(kernel_ms * nlaunch, 5)}
-
-    if not multi:
-        exchange_note = "none (single rank)"
-    elif comm is None:
-        exchange_note = comm_note or "torch.distributed callbacks"
-    elif args.comm == "windows":
-        exchange_note = ("library communicator made of windows: halo and reductions as direct stores into IPC-mapped "
-                         "device memory, no transport library")
-    elif args.halo == "windows":
-        exchange_note = ("library halo windows (direct stores into the neighbours' IPC-mapped memory), RCCL device "
-                         "all-reduce")
-    else:
-        exchange_note = "library RCCL communicator (grouped send/recv, device all-reduce)"
-    out = {
-        "metric": "DoFs/sec per p-MG V-cycle (Poisson, hex, p=4)",
-        "value": value,
-        "unit": "DoF/s",
-        "n_gpus": 1 if args.share_gpu else world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"Poisson p={P} V-cycle p=" + "->".join(str(p) for p in reversed(orders))
-                        + f", Chebyshev({args.cheb})/Jacobi, {args.n}^3 hexes per GPU" if args.scaling == "weak"
-                        else f"Poisson p={P} V-cycle, {args.n}^3 hexes total",
-            "cells_global": list(n_global),
-            "fine_dofs_global": fine_dofs_global,
-            "levels": list(reversed(orders)),
-            "cheb_iterations": args.cheb,
-            "partition": "x".join(str(d) for d in dims) + " bricks, 1 ghost-cell layer",
-            "exchange": exchange_note,
-            "stiffness_launches_per_cycle": {f"p{p}": c for p, c in zip(orders, counts)},
-            # ranks of the communicator the halo and the reductions really ran on (pmg_comm_size of the library's
-            # RCCL communicator, or torch.distributed's RCCL group on the callback route); 1 = no communicator
-            "rccl_ranks": rccl_ranks if args.comm == "rccl" else 0,
-            # the same for whichever communicator carried the run (RCCL or the one made of windows)
-            "comm_ranks": rccl_ranks,
-            # a halo exchange captured into a hipGraph keeps its overlap with the interior cells only on a HIP >= 7.2
-            # runtime (profiles/rccl_capture_probe_r03.md); a Python process runs on PyTorch's bundled runtime
-            "captured_exchange_overlaps": bool(pm._lib.lib().pmg_comm_capture_overlaps()) if multi else None,
-        },
-        "roofline": roofline,
-    }
-    watch["out"] = out
-    watch["phase"] = "after the headline"
-    if args.share_gpu:
-        out["rehearsal"] = (f"{world} ranks SHARE ONE GPU (--share-gpu): a rehearsal of the multi-rank path with real "
-                            "inter-process exchanges, not a multi-GPU measurement; `value` is the aggregate of the "
-                            "ranks time-slicing that GPU")
-        out["ranks"] = world
+    out["roofline"] = roofline
     if graph_ms is not None:
         out["graph_replay"] = {"ms_per_step": graph_ms, "value": fine_dofs_global / (graph_ms * 1e-3), "unit": "DoF/s",
                                "note": "the same cycle replayed with one hipGraphLaunch per cycle"
@@ -1137,23 +1204,11 @@ def main():
     _cpu_baseline()
     for f in parity_failures:
         log("PARITY FAILURE: " + f)
-    finish_line(out, parity_failures)
-
-    if deadline > 0:
-        timer.cancel()
-    if rank == 0:
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    os.close(json_fd)
+    emit(parity_failures)
     # release the library objects (and with them the RCCL communicator) while the runtime is still up
     del H, x, b, u, y, op
     comm = None
-    import gc
-
-    gc.collect()
-    torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-        dist.destroy_process_group()
+    release()
     if parity_failures:
         sys.exit(1)
 

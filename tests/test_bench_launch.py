@@ -86,6 +86,28 @@ def test_self_launch_starts_the_ranks_as_children(monkeypatch):
     assert len(ports) == 1 and 1024 < ports.pop() < 65536
 
 
+def test_plain_options_and_the_dump_sample():
+    """A plain run is the default (--full off, nothing dumped), --steps sets a count of at least one timed cycle, and
+    the --dump-outputs sample is fixed: the same sorted, distinct positions for the same output size, the whole
+    output when it fits, at most 64 MB of float64 in all."""
+    import numpy as np
+
+    b = _bench_module()
+    a = b.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit) as e:
+            b.parse_args(bad)
+        assert e.value.code == 2
+    assert 8 * b.DUMP_ENTRIES <= 64 * 2**20
+    assert np.array_equal(b.dump_indices(1000, 4096), np.arange(1000))
+    i = b.dump_indices(1_000_000, 5000)
+    assert i.size == 5000 and np.all(np.diff(i) > 0) and 0 <= i[0] and i[-1] < 1_000_000
+    assert np.array_equal(i, b.dump_indices(1_000_000, 5000))
+
+
 def test_self_launch_refuses_when_devices_are_short(monkeypatch):
     b = _bench_module()
     monkeypatch.setattr(b, "visible_gpus", lambda: 1)

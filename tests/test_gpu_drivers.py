@@ -243,6 +243,37 @@ def test_bench_refuses_more_gpus_than_the_box_has():
     assert f"--gpus {n}" in r.stderr and "refusing" in r.stderr
 
 
+def test_plain_bench_run_prints_the_headline_and_dumps_its_outputs(built, tmp_path):
+    """A plain `bench.py` run measures the headline only (no `--full` sections in the line), times exactly --steps
+    cycles, and with --dump-outputs writes the iterate after the last timed cycle; two runs with the same arguments
+    start from the same inputs, so they write the same iterate up to the summation order of the launches."""
+    import json
+    import sys
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumped = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                            "1", "--n", "8", "--dump-outputs", str(d)], env=env, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["value"] > 0 and line["unit"] == "DoF/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f64" and line["metric"].startswith("DoFs/sec")
+        assert abs(line["value"] - line["config"]["fine_dofs_global"] / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert not {"roofline", "graph_replay", "cpu_baseline", "degree_sweep", "parity"} & set(line)
+        assert sorted(os.listdir(d)) == ["x.npy"]
+        x = np.load(d / "x.npy")
+        assert x.dtype == np.float64 and x.shape == (line["config"]["fine_dofs_global"],)  # 33^3 dofs: all of them
+        assert np.all(np.isfinite(x)) and np.abs(x).max() > 0
+        dumped.append(x)
+    assert np.abs(dumped[0] - dumped[1]).max() <= 1e-10 * np.abs(dumped[1]).max()
+
+
 @pytest.mark.parametrize("dims", ["1,1,2", "1,2,2"])
 def test_pmg_driver_ranks_share_the_gpu_through_the_window_communicator(built, dims):
     """examples/pmg/run_ranks.sh with --comm windows: the C++ driver as 2 and 4 PROCESSES, one brick each, on the one

@@ -4,7 +4,7 @@
 //                           joined back with another (what csrc/comm.hip did when RCCL 2.26 crashed, commit 820fc9e),
 //   mode "fork-blocking"    the same with a default-flags second stream,
 //   mode "fork-eager-first" fork-nonblocking, but after one eager (uncaptured) exchange on that stream.
-// Prints a line per step; run under rocgdb to see where a crash comes from (tools/rccl_capture_probe.sh).
+// Prints a line per step: the last line of a mode that fails says where it stopped (tools/rccl_capture_probe.sh).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 

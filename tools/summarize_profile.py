@@ -69,7 +69,7 @@ json.dump(out, open(os.path.join(dst, f"hbm_traffic_{tag}.json"), "w"), indent=1
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 with open(os.path.join(dst, f"README_{tag}.md"), "w") as f:
     f.write(f"# rocprofv3 summary, round tag {tag}\n\n")
-    f.write("Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu` "
+    f.write("Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu` "
             "(set-up kernels included), MI355X, ROCm 7.2.\n\n")
     f.write("| kernel | calls | total ms | avg us | % |\n|---|---|---|---|---|\n")
     for r in rows[:16]:
