@@ -20,6 +20,8 @@
 //                    --id-file.  examples/pmg/run_ranks.sh launches the processes.
 //   --graph          time the cycles as hipGraph replays (one launch per cycle; with --ranks the grouped send/recv of
 //                    every halo exchange are captured on the compute stream: no host work per exchange)
+//   --fp32-cycle     run the V-cycle's smoothers, operators and transfers in FP32 (pmg_multigrid_set_precision); the
+//                    stationary cycles, PCG and residuals stay FP64.  Single domain only: refused with --ranks
 //   --check-partition px,py,pz   host-only consistency check of the brick partition (no GPU)
 //   --node-order basix   the dofmaps handed over in basix's cell-local node order (endpoints first), as dolfinx
 //                    gives them to the reference (examples/pmg/main.cpp:83-87); same numbers as without
@@ -73,7 +75,7 @@ struct Options : examples::RankOptions
 {
   int n = 64, cheb_its = 3, cycles = 10, amg_cycles = 0;
   std::vector<int> orders = {1, 2, 4};
-  bool pcg = false, coarse_cg = false, use_amg = false, random_rhs = false, graph = false;
+  bool pcg = false, coarse_cg = false, use_amg = false, random_rhs = false, graph = false, fp32_cycle = false;
   std::string output;
   pmg_amd::NodeOrder node_order = pmg_amd::NodeOrder::ascending; // of the dofmaps handed to the library
   bool amg_gather = false; // --amg-setup gathered
@@ -234,6 +236,13 @@ void solve(const Options& o)
     check(pmg_multigrid_set_coarse_solver(pmg.handle(), coarse_cg->handle()));
   }
 
+  if (o.fp32_cycle)
+  {
+    pmg.set_precision(PMG_PRECISION_FP32);
+    if (root)
+      std::printf("Cycle precision: fp32\n");
+  }
+
   // Create solution vector
   DeviceVector x(maps.back(), 1);
   x.set(T{0.0});
@@ -366,6 +375,8 @@ int main(int argc, char** argv)
         o.random_rhs = true;
       else if (!std::strcmp(argv[i], "--graph"))
         o.graph = true;
+      else if (!std::strcmp(argv[i], "--fp32-cycle"))
+        o.fp32_cycle = true;
       else if (!std::strcmp(argv[i], "--coarse-cg"))
         o.coarse_cg = true;
       else if (!std::strcmp(argv[i], "--amg"))
@@ -421,7 +432,7 @@ int main(int argc, char** argv)
       else
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
-                     "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph]\n"
+                     "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"
@@ -434,6 +445,9 @@ int main(int argc, char** argv)
         || std::adjacent_find(o.orders.begin(), o.orders.end()) != o.orders.end())
       throw std::runtime_error("--orders must be strictly ascending (coarse to fine)");
     const int size = o.ranks[0] * o.ranks[1] * o.ranks[2];
+    if (o.fp32_cycle && size > 1)
+      throw std::runtime_error("--fp32-cycle is single-domain only (--ranks asks for " + std::to_string(size)
+                               + " ranks)");
     if (ndofs) // cells per direction of the whole mesh so that a rank holds about ndofs fine dofs
       o.n = examples::cells_for_ndofs(ndofs * (std::size_t)size, o.orders.back());
     if (!check_dims.empty())

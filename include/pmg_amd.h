@@ -310,6 +310,14 @@ int pmg_laplacian_destroy(pmg_laplacian op);
  * ghosts of `in` (side effect, as in the reference), interior cells overlap
  * the halo exchange, then the boundary cells. */
 int pmg_laplacian_apply(pmg_laplacian op, double* in, double* out, pmg_stream stream);
+/* The same application in FP32 (the operator of the FP32 V-cycle, pmg_multigrid_set_precision): `in` and `out` are
+ * device arrays of size_local floats; `out` is overwritten, Dirichlet rows are out = in, interior and boundary cell
+ * lists are both applied.  The geometry tensor is computed in FP64 from the mesh, multiplied by kappa and rounded to
+ * float once -- 24 bytes per quadrature point, built on the first FP32 use and freed with the operator; the patch
+ * plan and its launches are the FP64 apply's, the cell sums are float.  Refused with PMG_ERR_INVALID: a layout with
+ * ghosts or a communicator (FP32 is single-domain only), an operator in batched-geometry mode.  The geometry mode
+ * (affine cells) and the chain form do not apply: the float form always streams its stored tensor. */
+int pmg_laplacian_apply_f32(pmg_laplacian op, float* in, float* out, pmg_stream stream);
 /* get_diag_inverse / set_diag_inverse, :484-495 (owned+ghost entries). */
 int pmg_laplacian_get_diag_inverse(pmg_laplacian op, double* diag_inv, pmg_stream stream);
 int pmg_laplacian_set_diag_inverse(pmg_laplacian op, const double* diag_inv, pmg_stream stream);
@@ -574,6 +582,25 @@ long long pmg_multigrid_graph_replays(pmg_multigrid mg);
 /* Number of stiffness-kernel launches issued by the last pmg_multigrid_apply,
  * per level (coarse -> fine); for the byte accounting in bench.py. */
 int pmg_multigrid_apply_counts(pmg_multigrid mg, int* counts, int capacity);
+/* Precision of the cycle (not in the reference).  PMG_PRECISION_FP64 (default): everything in FP64, as above.
+ * PMG_PRECISION_FP32: every later pmg_multigrid_apply, and the V-cycle preconditioner inside pmg_cg_solve, runs the
+ * smoothers, operators (pmg_laplacian_apply_f32) and transfers of every level in FP32; rhs and y stay double.
+ *   - zero initial guess (the preconditioner): y = V32(rhs) converted to double;
+ *   - non-zero y (stationary cycles): defect correction, y += V32(rhs - A y) with the FP64 operator forming the
+ *     defect -- equal to the FP64 cycle to float rounding, so repeated cycles converge below float accuracy;
+ *   - a coarse AMG / CG / callback solver keeps running in FP64 (b_0 converted up, u_0 down); the smoother-only coarse
+ *     level runs in FP32;
+ *   - smoother bounds and iteration counts are the pmg_chebyshev objects'; the float Jacobi diagonal is a copy of the
+ *     operator's diag_inv, refreshed after pmg_laplacian_set_diag_inverse / _compute_diag_inverse;
+ *   - graph replay (pmg_multigrid_set_graph) works as in FP64, the precision is part of the graph's key.
+ * Switching precision drops the cached graphs.  Refused with PMG_ERR_INVALID (message in pmg_last_error): an unknown
+ * precision; FP32 when a level's layout has ghosts or a communicator (single-domain only), an interpolator is not in
+ * patch form (pmg_interpolator_create_with_operator), or an operator is in batched-geometry mode -- checked here and
+ * again by each FP32 cycle.  pmg_multigrid_precision returns the current mode. */
+#define PMG_PRECISION_FP64 0
+#define PMG_PRECISION_FP32 1
+int pmg_multigrid_set_precision(pmg_multigrid mg, int precision);
+int pmg_multigrid_precision(pmg_multigrid mg);
 
 #ifdef __cplusplus
 }

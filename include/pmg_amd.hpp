@@ -984,6 +984,9 @@ public:
     _matfree_interpolation = interpolators;
     _wired = false;
   }
+  /// PMG_PRECISION_FP32: the cycle's smoothers, operators and transfers run in FP32, the vectors handed in stay
+  /// FP64 (pmg_multigrid_set_precision; single domain only).  PMG_PRECISION_FP64 (default) restores the FP64 cycle.
+  void set_precision(int precision) { check(pmg_multigrid_set_precision(_mg, precision)); }
   /// x = rhs, y = initial guess in / result out (:56-155).  With verbose the final
   /// residual norm is computed and returned (the reference prints it, :147-150); else 0.
   T apply(const Vector& x, Vector& y, bool verbose = false)

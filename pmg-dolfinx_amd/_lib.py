@@ -97,6 +97,7 @@ _SIGS = {
     "pmg_interpolation_table_ordered": (C.c_int, [C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_dp]),
     "pmg_laplacian_destroy": (C.c_int, [vp]),
     "pmg_laplacian_apply": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_laplacian_apply_f32": (C.c_int, [vp, vp, vp, vp]),
     "pmg_laplacian_get_diag_inverse": (C.c_int, [vp, vp, vp]),
     "pmg_laplacian_set_diag_inverse": (C.c_int, [vp, vp, vp]),
     "pmg_laplacian_compute_diag_inverse": (C.c_int, [vp, vp]),
@@ -153,6 +154,8 @@ _SIGS = {
     "pmg_multigrid_set_coarse_solver": (C.c_int, [vp, vp]),
     "pmg_multigrid_set_coarse_callback": (C.c_int, [vp, COARSE_FN, vp]),
     "pmg_multigrid_set_coarse_amg": (C.c_int, [vp, vp]),
+    "pmg_multigrid_set_precision": (C.c_int, [vp, C.c_int]),
+    "pmg_multigrid_precision": (C.c_int, [vp]),
     "pmg_amg_create": (C.c_int, [C.POINTER(vp), vp, vp]),
     "pmg_amg_create_replicated": (C.c_int, [C.POINTER(vp), vp, C.POINTER(C.c_int64), C.c_int64, vp]),
     "pmg_amg_create_distributed": (C.c_int, [C.POINTER(vp), vp, C.POINTER(C.c_int64), C.c_int64, vp]),
@@ -177,7 +180,7 @@ _SIGS = {
 
 # functions whose int return value is a count, not a status
 _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplacian_geometry_bytes", "pmg_comm_rank", "pmg_comm_size", "pmg_comm_capture_overlaps", "pmg_cg_coefficients", "pmg_cg_compute_eigenvalues", "pmg_multigrid_apply_counts", "pmg_version",
-                "pmg_laplacian_degree", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine",
+                "pmg_laplacian_degree", "pmg_multigrid_precision", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_layout_forward_scatters"}
 

@@ -253,4 +253,26 @@ void launch_cg_update2(int n, double* x, double* r, const double* p, const doubl
                        const double* d_py, hipStream_t s);
 void launch_cg_direction(int n, double* p, const double* y, double rnorm, const double* d_new,
                          const double* d_sub, hipStream_t s);
+
+// ---- the FP32 V-cycle (cycle_f32.hip, laplacian_f32.hip; single domain only) ----
+struct ChebWork32
+{
+  float *r = nullptr, *z = nullptr, *q = nullptr;
+};
+// cheb_iterate in FP32 on the operator's float form (no ghosts: no exchange bookkeeping, no zeroed-output variant)
+int cheb_iterate_f32(const ChebWork32& w, pmg_laplacian A, const float* dinv, int n, double lmax, int max_iter,
+                     float* x, const float* b, int need_r, bool x_zero, hipStream_t s, bool* split);
+int laplacian_f32_supported(pmg_laplacian op, const char* who); // PMG_OK, or the refusal (ghosts, batched geometry)
+int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s);      // float tensor and table on first use (allocates)
+int laplacian_f32_diag(pmg_laplacian op, const float** d, hipStream_t s, bool* changed);
+long long laplacian_diag_version(pmg_laplacian op);
+int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s);
+int transfer_f32_prepare(pmg_interpolator ip, float** M1); // float copy of the 1-D table (caller frees)
+int prolong_add_f32(pmg_interpolator ip, const float* M1, const float* coarse, float* fine, hipStream_t s);
+int restrict_f32(pmg_interpolator ip, const float* M1, const float* fine, const float* fine_sub, float* coarse,
+                 hipStream_t s);
+void launch_to_f32(int n, const double* in, const double* sub, float* out, hipStream_t s); // out = in (- sub)
+void launch_from_f32(int n, const float* in, double* out, bool add, hipStream_t s);        // out (+)= in
+void launch_zero_f32(int n, float* x, hipStream_t s);
+void launch_mask_bc_f32(int n, float* b, const int8_t* bc, hipStream_t s);
 } // namespace pmg

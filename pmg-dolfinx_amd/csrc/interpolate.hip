@@ -679,6 +679,26 @@ namespace pmg
 {
 bool interp_is_patched(pmg_interpolator ip) { return ip->patched; }
 
+TransferView interp_transfer_view(pmg_interpolator ip)
+{
+  TransferView v;
+  v.lc = ip->lc;
+  v.lf = ip->lf;
+  v.ndc = ip->ndc;
+  v.ndf = ip->ndf;
+  v.cmax_m = ip->cmax_m;
+  v.pwaves = ip->pwaves;
+  v.fv = ip->fv;
+  v.n_interior = ip->patched ? interior_patches(ip) : 0;
+  v.cpoff = ip->cpoff;
+  v.cpdofs = ip->cpdofs;
+  v.clmap_id = ip->clmap_id;
+  v.clmaps = ip->clmaps;
+  v.pmult = ip->pmult;
+  v.M1 = ip->M1;
+  return v;
+}
+
 // fine += P coarse in one pass (src/pmg.hpp:123-129 fused); patch path only
 int interp_prolong_add(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s)
 {

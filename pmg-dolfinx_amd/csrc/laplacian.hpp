@@ -1,0 +1,121 @@
+// The operator handle, shared by the FP64 (laplacian.hip) and FP32 (laplacian_f32.hip) forms of the apply.
+#pragma once
+
+#include "common.hpp"
+#include "patches.hpp"
+
+struct pmg_laplacian_s
+{
+  pmg_layout layout = nullptr;
+  int P = 0, nd = 0, N = 0, K = 0;
+  int32_t ncells = 0, npoints = 0;
+  // caller-owned
+  const double* kappa = nullptr;
+  const int32_t* dofmap = nullptr;
+  const double* xgeom = nullptr;
+  const int32_t* geom_dofmap = nullptr;
+  const int8_t* bc = nullptr;
+  // cell-local node order of the caller's arrays (pmg_amd.h): the kernels index nodes by ascending coordinate, so a
+  // caller in another order gets an ascending copy of its dofmap (op->dofmap then points to it) and its
+  // quadrature-indexed arrays are permuted on the way in (tables) and out (get_geometry)
+  int node_order = PMG_NODES_ASCENDING;
+  int32_t* dofmap_own = nullptr; // [ncells * N], ascending order; nullptr = the caller's array is used as it is
+  int32_t* qperm = nullptr;      // [N] device: caller's cell-local number -> ascending; nullptr = identity
+  // owned
+  double2* G = nullptr;        // [nslots][3][N]
+  double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell
+  double* W1 = nullptr;        // [nd] 1-D GLL weights
+  bool all_affine = false;     // every listed cell is a parallelepiped
+  int geometry_mode = 0;       // 0 = stored G (reference data structure), 1 = affine cells
+  double* D = nullptr;         // [nd*nd]
+  double* dphi_geom = nullptr; // [3][N][8]
+  double* gweights = nullptr;  // [N]
+  int32_t* pcell = nullptr;    // [npatch*K]
+  int32_t* pncell = nullptr;   // [npatch]
+  int32_t* bzero = nullptr;    // dofs first written by the (atomic) boundary launch
+  int32_t n_bzero = 0;
+  int32_t* poff = nullptr;     // [npatch+1]
+  uint32_t* pdofs = nullptr;
+  int32_t* lmap_id = nullptr;  // [npatch]
+  uint16_t* lmaps = nullptr;   // [nuniq][K*N]
+  int32_t npatch = 0;
+  std::vector<int32_t> launch_first, launch_count;
+  // two halves of the interior on two streams (PatchPlan::launch_stream): the second stream and its fork / order /
+  // join events
+  std::vector<int8_t> launch_stream;
+  int launch_signal = -1, launch_wait = -1;
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_order = nullptr, ev_join = nullptr;
+  std::vector<int32_t> pcell_h, pncell_h; // host copies for components that share the patches
+  long long npdofs = 0;
+  int max_m = 0;
+  int n_launch_l = 0;
+  int n_plain = 0;
+  bool needs_zero = false; // some local dof belongs to no listed cell
+  // chain form of the interior launches (patches.hpp ChainPlan, stiffness_chain_kernel): available / in use
+  bool chain_ok = false, chain_on = false;
+  uint32_t* cdofs = nullptr;
+  uint32_t* ccar = nullptr;
+  int32_t* chain_off = nullptr;
+  int32_t* chain_patch = nullptr;
+  std::vector<int32_t> chain_first, chain_count; // chains of each colour
+  bool stream_policy = true; // the stored tensor exceeds the Infinity Cache: nt loads / stores (launch_stiffness)
+  double* diag_inv = nullptr; // [size_local + num_ghosts]
+  bool have_diag = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  long long launches = 0; // full operator applications' kernel launches since creation
+  long long applies = 0;
+  // geometry batching (src/laplacian.hpp:383-396): > 0 = G is not resident; it is recomputed for
+  // `batch_patches` patches at a time into a buffer of that size, in every application
+  int32_t batch_patches = 0;
+  // in-situ timing of the stiffness launches (pmg_laplacian_set_profiling)
+  bool profiling = false;
+  std::vector<hipEvent_t> prof_events; // pairs: before / after a run of launches
+  size_t prof_used = 0;
+  long long prof_launches = 0;
+  // single-precision form of the operator (laplacian_f32.hip; built on first use, freed with the handle)
+  float2* G32 = nullptr;          // [nslots][layer c][3][nd*nd]: kappa * G, rounded once (the default layout of G)
+  float* D32 = nullptr;           // [nd*nd]
+  float* diag32 = nullptr;        // [size_local + num_ghosts] float copy of diag_inv
+  long long diag_version = 0;     // bumped whenever diag_inv changes; diag32 is current while the two agree
+  long long diag32_version = -1;
+};
+
+namespace pmg
+{
+// ---- geometry: J, adj(J), det at one quadrature point (src/laplacian.hpp:72-97) ----
+__device__ inline void jacobian(const double* __restrict__ xgeom,
+                                const int32_t* __restrict__ gdofs, const double* __restrict__ dphi,
+                                int nq, int q, double K[3][3], double& detJ)
+{
+  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  for (int k = 0; k < 8; ++k)
+  {
+    const double* xk = xgeom + 3 * (size_t)gdofs[k];
+    double x0 = xk[0], x1 = xk[1], x2 = xk[2];
+    double d0 = dphi[(0 * nq + q) * 8 + k], d1 = dphi[(1 * nq + q) * 8 + k],
+           d2 = dphi[(2 * nq + q) * 8 + k];
+    J[0][0] += x0 * d0;
+    J[0][1] += x0 * d1;
+    J[0][2] += x0 * d2;
+    J[1][0] += x1 * d0;
+    J[1][1] += x1 * d1;
+    J[1][2] += x1 * d2;
+    J[2][0] += x2 * d0;
+    J[2][1] += x2 * d1;
+    J[2][2] += x2 * d2;
+  }
+  K[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+  K[0][1] = -J[0][1] * J[2][2] + J[0][2] * J[2][1];
+  K[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+  K[1][0] = -J[1][0] * J[2][2] + J[1][2] * J[2][0];
+  K[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+  K[1][2] = -J[0][0] * J[1][2] + J[0][2] * J[1][0];
+  K[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+  K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
+  K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+  // full cofactor expansion along the first row (the reference's :97 drops to
+  // the diagonal-J special case)
+  detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
+}
+} // namespace pmg

@@ -1,0 +1,476 @@
+// Single-precision form of the operator: the stiffness apply of the FP32 V-cycle (cycle_f32.hip) and of
+// pmg_laplacian_apply_f32.
+//
+// Same patch plan as the FP64 apply (laplacian.hip): one workgroup per patch, the patch's x values and y sums in
+// LDS, the colours launched in plan order with plain stores, the merged launch of a small level and of the boundary
+// shell adding with float atomics, bzero cleared first, Dirichlet rows y = x written by their first patch.  What
+// changes is the width of every byte: the stored tensor is float (24 B per quadrature point instead of 48), kappa is
+// folded into it, the vectors are float, and the cell sums meet in LDS with ds_add_f32.
+//
+// The tensor is computed in FP64 from the mesh (the Jacobian of laplacian.hpp) and rounded once, on the first FP32
+// use of the operator; it is never converted from the FP64 tensor (which may not be resident: batched geometry).
+//
+// One kernel form for every degree: the column scheme of laplacian.hip without its build options -- a lane owns the
+// (a, b) column of a cell, keeps the column's values in registers and marches through the nd layers; the x and y
+// contractions pass one nd x nd slice through LDS, the z contraction stays in registers.  Half-width registers let
+// every degree run eight wavefronts per workgroup where it has the items (P = 6: 49 of 64 lanes, P = 7: 64 of 64),
+// and P = 5 / P = 8 share one item of 7 / 3 cells between four wavefronts as the FP64 kernel does.
+#include "laplacian.hpp"
+
+#include <algorithm>
+
+using namespace pmg;
+
+namespace
+{
+template <int P>
+struct Shape32
+{
+  static constexpr int ND = P + 1;
+  static constexpr int N = ND * ND * ND;
+  static constexpr int NQ2 = ND * ND;
+  static constexpr PatchShape PS = patch_shape(P);
+  static constexpr int K = PS.bx * PS.by * PS.bz;
+  static constexpr int MAXM = PS.max_m;
+  static constexpr bool SHARED_ITEM = P == 5 || P == 8; // one item of K cells over four wavefronts (patches.hpp)
+  static constexpr int CW = SHARED_ITEM ? K : (NQ2 <= 64 ? 64 / NQ2 : 1); // cells per item
+  static constexpr int WPC = SHARED_ITEM ? 4 : (NQ2 + 63) / 64;            // wavefronts per item
+  static_assert(CW * NQ2 <= 64 * WPC, "an item's columns need a lane each");
+  static constexpr int WL = CW * NQ2; // columns of an item
+  static constexpr int ITEMS = (K + CW - 1) / CW;
+  static constexpr int NWMAX = 8;
+  static constexpr int NG = ITEMS < NWMAX / WPC ? ITEMS : NWMAX / WPC; // items in flight per workgroup
+  static constexpr int NW = NG * WPC;
+  static constexpr int THREADS = NW * 64;
+  static constexpr int ITER = (MAXM + THREADS - 1) / THREADS; // patch list entries per thread
+  // layers of the tensor in flight per wavefront: a float layer is half the bytes of a double one, so twice as many
+  // are needed for the same bytes in flight per compute unit
+  static constexpr int GD = (P == 1 || P == 4) ? 2 : 3; // (P = 4: two, or the six wavefronts per SIMD below spill)
+  // waves per SIMD the register allocation must leave room for: three workgroups of eight wavefronts per compute unit
+  // up to P = 4 (the tensor stream needs the wavefronts), what the cell loop needs above
+  static constexpr int MIN_WAVES = P <= 4 ? 6 : 1;
+  static_assert(MAXM <= 65535, "patch positions are 16-bit");
+};
+
+__device__ __forceinline__ void wave_fence32()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// workgroup barrier that orders LDS only (no vmcnt drain: nothing passes through global memory inside the kernel)
+__device__ __forceinline__ void lds_barrier32()
+{
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+typedef float fvec2 __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ float2 gload32(const float2* p)
+{
+  if constexpr (NT)
+  {
+    fvec2 v = __builtin_nontemporal_load(reinterpret_cast<const fvec2*>(p));
+    return make_float2(v.x, v.y);
+  }
+  else
+    return *p;
+}
+
+// kappa * G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]
+__global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __restrict__ pcell,
+                                    const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                                    const double* __restrict__ dphi, const double* __restrict__ w,
+                                    const double* __restrict__ kappa, float2* __restrict__ G)
+{
+  const int nsq = nd * nd, nq = nsq * nd;
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * nq)
+    return;
+  const long long slot = gid / nq;
+  const int q = (int)(gid - slot * nq);
+  const int c = pcell[slot];
+  double g[6] = {0, 0, 0, 0, 0, 0};
+  if (c >= 0)
+  {
+    double K[3][3], detJ;
+    jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
+    const double s = kappa[c] * w[q] / detJ;
+    g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
+    g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+    g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+    g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+    g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+    g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+  }
+  const int a = q / nsq, b = (q - a * nsq) / nd, cc = q - a * nsq - b * nd;
+  float2* o = G + (size_t)slot * 3 * nq + (size_t)cc * 3 * nsq + a * nd + b;
+  o[0] = make_float2((float)g[0], (float)g[1]);
+  o[nsq] = make_float2((float)g[2], (float)g[3]);
+  o[2 * nsq] = make_float2((float)g[4], (float)g[5]);
+}
+
+template <int P, bool NT>
+__global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
+    stiffness_f32_kernel(const float* __restrict__ x, float* __restrict__ y, const float2* __restrict__ G,
+                         const int32_t* __restrict__ poff, const uint32_t* __restrict__ pdofs,
+                         const int32_t* __restrict__ lmap_id, const uint16_t* __restrict__ lmaps,
+                         const int32_t* __restrict__ pncell, const float* __restrict__ Dg, int first, int atomic_out)
+{
+  using Sh = Shape32<P>;
+  constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, NG = Sh::NG, WPC = Sh::WPC, WL = Sh::WL;
+  constexpr int MAXM = Sh::MAXM, THREADS = Sh::THREADS, CW = Sh::CW, ITER = Sh::ITER, GD = Sh::GD;
+  __shared__ float sD[ND * ND];
+  __shared__ float sx[MAXM];
+  __shared__ float sy[MAXM];
+  __shared__ float sq[NG * WL];
+  __shared__ float sgr[NG * WL];
+  __shared__ float sgs[NG * WL];
+
+  const int p = first + blockIdx.x;
+  const int t = threadIdx.x;
+  const int off = poff[p];
+  const int M = poff[p + 1] - off; // 1 <= M <= MAXM
+  const int table = lmap_id[p];
+  const int nc = pncell[p];
+
+  // gather: x (zero on Dirichlet dofs, src/laplacian.hpp:186-189) and, in a coloured launch, the sums the earlier
+  // colours stored for the dofs they share with this patch
+  // (unconditional loads with clamped indices, all issued before the first is used)
+  {
+    uint32_t m[ITER];
+    float xv[ITER], yv[ITER];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      m[k] = pdofs[off + (i < M ? i : M - 1)];
+    }
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const uint32_t dof = m[k] & PD_MASK;
+      const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
+      xv[k] = x[dof];
+      yv[k] = *(acc ? (const float*)(y + dof) : x + dof);
+    }
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      if (i < M)
+      {
+        const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
+        sx[i] = (m[k] & PD_BC) ? 0.0f : xv[k];
+        sy[i] = acc ? yv[k] : 0.0f;
+      }
+    }
+  }
+  if (t < ND * ND)
+    sD[t] = Dg[t];
+  lds_barrier32();
+
+  const int wave = (t >> 6) / WPC, lane = (t & 63) + 64 * ((t >> 6) % WPC);
+  const bool lane_ok = lane < WL;
+  const int lw = lane_ok ? lane : WL - 1; // idle lanes shadow the last column (finite values, no contribution)
+  const int cw = lw / NQ2, ab = lw - cw * NQ2;
+  const int a = ab / ND, b = ab - a * ND;
+  float Da[ND], Db[ND], DTa[ND], DTb[ND]; // D[a][.], D[b][.], D[.][a], D[.][b]
+#pragma unroll
+  for (int mm = 0; mm < ND; ++mm)
+  {
+    Da[mm] = sD[a * ND + mm];
+    Db[mm] = sD[b * ND + mm];
+    DTa[mm] = sD[mm * ND + a];
+    DTb[mm] = sD[mm * ND + b];
+  }
+  float* q_s = sq + wave * WL + cw * NQ2;
+  float* gr_s = sgr + wave * WL + cw * NQ2;
+  float* gs_s = sgs + wave * WL + cw * NQ2;
+  // wavefronts that share an item exchange slices through workgroup barriers: all of them run the same item count
+  const int items = WPC > 1 ? (((nc + CW - 1) / CW + NG - 1) / NG) * NG : (nc + CW - 1) / CW;
+  auto slice_sync = [] {
+    if constexpr (WPC > 1)
+      lds_barrier32();
+    else
+      wave_fence32();
+  };
+  const uint16_t* lmb = lmaps + (size_t)table * (K * N);
+  for (int it = wave; it < items; it += NG)
+  {
+    const int slot = it * CW + cw;
+    const int slotc = slot < K ? slot : K - 1;
+    const unsigned lmo = (unsigned)(slotc * N + ab);
+    int l[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+      l[k] = lmb[lmo + (unsigned)(k * NQ2)];
+    const float2* Gb = G + (size_t)p * K * 3 * N;
+    const unsigned Gs = (unsigned)(slotc * 3 * N + ab);
+    float2 gq[GD][3]; // layers 0 .. GD-1 in flight, slot k % GD refilled with layer k + GD once layer k is read
+#pragma unroll
+    for (int d = 0; d < GD; ++d)
+    {
+      const unsigned o = Gs + (unsigned)(d * 3 * NQ2);
+      gq[d][0] = gload32<NT>(Gb + o);
+      gq[d][1] = gload32<NT>(Gb + (o + NQ2));
+      gq[d][2] = gload32<NT>(Gb + (o + 2 * NQ2));
+    }
+    float u[ND], Aq[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      u[k] = sx[l[k]];
+      Aq[k] = 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      const float2 g01 = gq[k % GD][0], g23 = gq[k % GD][1], g45 = gq[k % GD][2];
+      if (k + GD < ND)
+      {
+        const unsigned o = Gs + (unsigned)((k + GD) * 3 * NQ2);
+        gq[k % GD][0] = gload32<NT>(Gb + o);
+        gq[k % GD][1] = gload32<NT>(Gb + (o + NQ2));
+        gq[k % GD][2] = gload32<NT>(Gb + (o + 2 * NQ2));
+      }
+      q_s[ab] = u[k];
+      slice_sync();
+      float qr = 0.0f, qs = 0.0f, qt = 0.0f;
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+      {
+        qr += Da[mm] * q_s[mm * ND + b]; // d/dx
+        qs += Db[mm] * q_s[a * ND + mm]; // d/dy
+        qt += Dg[k * ND + mm] * u[mm];   // d/dz: registers, wave-uniform table entries
+      }
+      const float fr = g01.x * qr + g01.y * qs + g23.x * qt;
+      const float fs = g01.y * qr + g23.y * qs + g45.x * qt;
+      const float ft = g23.x * qr + g45.x * qs + g45.y * qt;
+      gr_s[ab] = fr;
+      gs_s[ab] = fs;
+      slice_sync();
+      float acc = 0.0f;
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+      {
+        acc += DTa[mm] * gr_s[mm * ND + b];
+        acc += DTb[mm] * gs_s[a * ND + mm];
+        Aq[mm] += Dg[k * ND + mm] * ft;
+      }
+      Aq[k] += acc;
+      slice_sync();
+    }
+    // every lane adds (lanes without a cell add an exact zero: no branch around the accumulation)
+    const bool contributes = lane_ok && slot < nc;
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+      atomicAdd(&sy[l[k]], contributes ? Aq[k] : 0.0f); // ds_add_f32
+  }
+  // write-back: sums of the non-Dirichlet dofs (store onto the earlier colours' values, or a float atomic in a merged
+  // launch); the Dirichlet rows y = x by the first patch that holds them (src/laplacian.hpp:273-274).  The list is
+  // re-read before the closing barrier, so that no dependent load sits behind it.
+  int tw = t;
+  asm volatile("" : "+v"(tw)); // (opaque: the list addresses are not computed ahead and held through the cell loop)
+  uint32_t mk[ITER];
+#pragma unroll
+  for (int k = 0; k < ITER; ++k)
+  {
+    const int i = tw + k * THREADS;
+    mk[k] = pdofs[off + (i < M ? i : M - 1)];
+  }
+  lds_barrier32();
+#pragma unroll
+  for (int k = 0; k < ITER; ++k)
+  {
+    const int i = tw + k * THREADS;
+    if (i >= M)
+      break;
+    const uint32_t m = mk[k];
+    const uint32_t dof = m & PD_MASK;
+    if (!(m & PD_BC))
+    {
+      if (atomic_out)
+        atomicAdd(&y[dof], sy[i]);
+      else if constexpr (NT)
+        __builtin_nontemporal_store(sy[i], &y[dof]);
+      else
+        y[dof] = sy[i];
+    }
+    else if (!(m & PD_ACC))
+      y[dof] = x[dof];
+  }
+}
+
+__global__ void zero_list_f32_kernel(int n, const int32_t* __restrict__ idx, float* __restrict__ y)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    y[idx[i]] = 0.0f;
+}
+
+__global__ void fill_f32_kernel(int n, float* __restrict__ y)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    y[i] = 0.0f;
+}
+
+__global__ void to_float_kernel(int n, const double* __restrict__ in, float* __restrict__ out)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = (float)in[i];
+}
+
+int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 2048); }
+
+template <int P>
+void launch_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, bool nt,
+                hipStream_t s)
+{
+  if (nt)
+    stiffness_f32_kernel<P, true><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
+                                                                      op->lmap_id, op->lmaps, op->pncell, op->D32,
+                                                                      first, atomic_out);
+  else
+    stiffness_f32_kernel<P, false><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
+                                                                       op->lmap_id, op->lmaps, op->pncell, op->D32,
+                                                                       first, atomic_out);
+}
+
+int launch_patches_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, bool nt,
+                       hipStream_t s)
+{
+  switch (op->P)
+  {
+  case 1: launch_f32<1>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 2: launch_f32<2>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 3: launch_f32<3>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 4: launch_f32<4>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 5: launch_f32<5>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 6: launch_f32<6>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 7: launch_f32<7>(op, x, y, first, count, atomic_out, nt, s); break;
+  case 8: launch_f32<8>(op, x, y, first, count, atomic_out, nt, s); break;
+  default: return fail(PMG_ERR_INVALID, "Unsupported degree");
+  }
+  op->launches++;
+  return PMG_OK;
+}
+} // namespace
+
+namespace pmg
+{
+// Can this operator run in FP32?  (0 = yes, else the refusal has been recorded)
+int laplacian_f32_supported(pmg_laplacian op, const char* who)
+{
+  pmg_layout l = op->layout;
+  PMG_REQUIRE(l->num_ghosts == 0 && !l->multi_rank() && !l->win,
+              "%s: FP32 is single-domain only (the layout has ghosts or a communicator)", who);
+  PMG_REQUIRE(op->batch_patches == 0, "%s: FP32 needs the resident geometry (the operator is in batched-geometry mode)",
+              who);
+  return PMG_OK;
+}
+
+// The float tensor and 1-D table, built on the first FP32 use (outside any stream capture: it allocates)
+int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
+{
+  if (op->G32)
+    return PMG_OK;
+  const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
+  PMG_HIP(hipMalloc(&op->G32, sizeof(float2) * 3 * (size_t)(n > 0 ? n : 1)));
+  PMG_HIP(hipMalloc(&op->D32, sizeof(float) * op->nd * op->nd));
+  to_float_kernel<<<1, 256, 0, s>>>(op->nd * op->nd, op->D, op->D32);
+  if (n > 0)
+    geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
+                                                                    op->geom_dofmap, op->dphi_geom, op->gweights,
+                                                                    op->kappa, op->G32);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
+// float copy of the operator's diagonal inverse, refreshed when the diagonal has changed since; `*changed` (optional)
+// tells the caller that a conversion was enqueued
+int laplacian_f32_diag(pmg_laplacian op, const float** d, hipStream_t s, bool* changed)
+{
+  const int total = op->layout->total();
+  if (changed)
+    *changed = false;
+  if (!op->diag32)
+    PMG_HIP(hipMalloc(&op->diag32, sizeof(float) * (total ? total : 1)));
+  if (op->diag32_version != op->diag_version)
+  {
+    if (total > 0)
+      to_float_kernel<<<grid_for(total), 256, 0, s>>>(total, op->diag_inv, op->diag32);
+    PMG_HIP(hipGetLastError());
+    op->diag32_version = op->diag_version;
+    if (changed)
+      *changed = true;
+  }
+  *d = op->diag32;
+  return PMG_OK;
+}
+long long laplacian_diag_version(pmg_laplacian op) { return op->diag_version; }
+
+// out = A in in FP32, with the semantics of laplacian_apply on a layout without ghosts: out is overwritten, the
+// Dirichlet rows are out = in, every launch of the plan in its order (the two-stream and chain forms of the FP64
+// apply are not used).  The operator must have been prepared (laplacian_f32_prepare).
+int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s)
+{
+  pmg_layout l = op->layout;
+  const int nl = (int)op->launch_first.size();
+  const bool zero_all = op->needs_zero || nl == 0 || 2LL * op->n_bzero > l->total();
+  if (zero_all)
+  {
+    if (l->total() > 0)
+      fill_f32_kernel<<<grid_for(l->total()), 256, 0, s>>>(l->total(), out);
+  }
+  else if (op->n_bzero > 0)
+    zero_list_f32_kernel<<<grid_for(op->n_bzero), 256, 0, s>>>(op->n_bzero, op->bzero, out);
+  const bool prof = op->profiling && nl > 0;
+  if (prof)
+  {
+    if (op->prof_used + 2 > op->prof_events.size())
+    {
+      hipEvent_t a, b;
+      PMG_HIP(hipEventCreate(&a));
+      op->prof_events.push_back(a);
+      PMG_HIP(hipEventCreate(&b));
+      op->prof_events.push_back(b);
+    }
+    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used], s));
+  }
+  // the tensor streams past the Infinity Cache (the FP64 rule at half the bytes): nt loads and stores
+  const bool nt = op->P >= 2 && (long long)sizeof(float2) * 3 * op->npatch * op->K * op->N > (128LL << 20);
+  int issued = 0;
+  for (int i = 0; i < nl; ++i)
+  {
+    const int first = op->launch_first[i];
+    int count = op->launch_count[i];
+    const int atomic_out = i >= op->n_plain ? 1 : 0;
+    while (atomic_out && i + 1 < nl && op->launch_first[i + 1] == first + count) // contiguous atomic launches: one
+      count += op->launch_count[++i];
+    if (count > 0)
+    {
+      PMG_TRY(launch_patches_f32(op, in, out, first, count, atomic_out, nt, s));
+      ++issued;
+    }
+  }
+  PMG_HIP(hipGetLastError());
+  if (prof)
+  {
+    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used + 1], s));
+    op->prof_used += 2;
+    op->prof_launches += issued;
+  }
+  op->applies++;
+  return PMG_OK;
+}
+} // namespace pmg
+
+extern "C" int pmg_laplacian_apply_f32(pmg_laplacian op, float* in, float* out, pmg_stream stream)
+{
+  PMG_REQUIRE(op && in && out, "pmg_laplacian_apply_f32: NULL argument");
+  PMG_REQUIRE(in != out, "pmg_laplacian_apply_f32: in and out alias");
+  PMG_TRY(laplacian_f32_supported(op, "pmg_laplacian_apply_f32"));
+  hipStream_t s = S(stream);
+  PMG_TRY(laplacian_f32_prepare(op, s));
+  return laplacian_apply_f32(op, in, out, s);
+}

@@ -155,6 +155,21 @@ struct PatchView
   long long npdofs = 0; // total entries of pdofs
 };
 
+// What the single-precision transfers (cycle_f32.hip) read of an interpolator that shares its fine operator's patches.
+struct TransferView
+{
+  pmg_layout lc = nullptr, lf = nullptr;
+  int ndc = 0, ndf = 0, cmax_m = 0, pwaves = 4;
+  int n_interior = 0; // patches of the interior cell list (they come first in launch order)
+  PatchView fv;
+  const int32_t* cpoff = nullptr;
+  const uint32_t* cpdofs = nullptr;
+  const int32_t* clmap_id = nullptr;
+  const uint16_t* clmaps = nullptr;
+  const uint8_t* pmult = nullptr;
+  const double* M1 = nullptr; // [ndf][ndc]
+};
+
 // Chains (round 4, second half): the interior patches of a large level strung together along the axis with the fewest
 // patch positions (z on a box whose patches are long in z), one PERSISTENT workgroup per chain (stiffness_chain_kernel,
 // laplacian.hip).  A chain is walked in order, so the dofs two consecutive patches share never pass through global

@@ -95,6 +95,13 @@ struct pmg_multigrid_s
   std::vector<GraphEntry> graphs;
   hipStream_t capture_stream = nullptr;
   long long graph_replays = 0;
+  // FP32 cycle (pmg_multigrid_set_precision): float vectors of every level and float copies of the transfer tables,
+  // allocated on the first FP32 cycle; the operators hold their own float forms (laplacian_f32.hip)
+  int precision = PMG_PRECISION_FP64;
+  std::vector<float*> u32, b32;
+  std::vector<ChebWork32> w32;
+  std::vector<float*> M1_32;          // per interpolator (dropped when the interpolators change)
+  std::vector<const float*> dinv32;   // per level, the operators' float diagonals (refreshed by mg_prepare_f32)
 };
 
 namespace pmg
@@ -225,6 +232,180 @@ bool local_correction(pmg_multigrid mg, int level)
   return level > 0 && mg->layouts[level]->num_ghosts > 0 && interp_is_patched(mg->interps[level - 1]);
 }
 
+// Is every part of the multigrid fit for the FP32 cycle?  (the refusals of pmg_multigrid_set_precision)
+int mg_check_f32(pmg_multigrid mg, const char* who)
+{
+  for (int i = 0; i < mg->L; ++i)
+  {
+    pmg_layout l = mg->layouts[i];
+    PMG_REQUIRE(l->num_ghosts == 0 && !l->multi_rank() && !l->win,
+                "%s: the FP32 cycle is single-domain only (level %d's layout has ghosts or a communicator)", who, i);
+  }
+  for (size_t i = 0; i < mg->interps.size(); ++i)
+    PMG_REQUIRE(interp_is_patched(mg->interps[i]),
+                "%s: the FP32 cycle needs patch-form interpolators (pmg_interpolator_create_with_operator; level %zu)",
+                who, i);
+  for (pmg_laplacian op : mg->ops)
+    PMG_TRY(laplacian_f32_supported(op, who));
+  return PMG_OK;
+}
+
+void free_f32(pmg_multigrid mg)
+{
+  for (float* p : mg->u32)
+    (void)hipFree(p);
+  for (float* p : mg->b32)
+    (void)hipFree(p);
+  for (const ChebWork32& w : mg->w32)
+  {
+    (void)hipFree(w.r);
+    (void)hipFree(w.z);
+    (void)hipFree(w.q);
+  }
+  for (float* p : mg->M1_32)
+    (void)hipFree(p);
+  mg->u32.clear();
+  mg->b32.clear();
+  mg->w32.clear();
+  mg->M1_32.clear();
+}
+
+int alloc_vec_f32(pmg_layout l, float** p)
+{
+  size_t n = l->total() ? l->total() : 1;
+  PMG_HIP(hipMalloc(p, sizeof(float) * n));
+  PMG_HIP(hipMemset(*p, 0, sizeof(float) * n));
+  PMG_HIP(hipStreamSynchronize(nullptr));
+  return PMG_OK;
+}
+
+// Everything the FP32 cycle reads besides its vectors, current on `s`: float vectors, the operators' float tensors,
+// float diagonals (re-converted after a change of diag_inv) and transfer tables.  Allocates on first use -- called
+// outside any capture (mg_apply_graph prepares before it captures; inside the capture this is a no-op).
+int mg_prepare_f32(pmg_multigrid mg, hipStream_t s)
+{
+  const int L = mg->L;
+  PMG_TRY(mg_check_f32(mg, "pmg_multigrid_apply"));
+  if ((int)mg->u32.size() != L)
+  {
+    mg->u32.assign(L, nullptr);
+    mg->b32.assign(L, nullptr);
+    mg->w32.assign(L, ChebWork32{});
+    for (int i = 0; i < L; ++i)
+    {
+      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->u32[i]));
+      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->b32[i]));
+      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].r));
+      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].z));
+      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].q));
+    }
+  }
+  if ((int)mg->M1_32.size() != L - 1)
+  {
+    for (float* p : mg->M1_32)
+      (void)hipFree(p);
+    mg->M1_32.assign(L - 1, nullptr);
+    for (int i = 0; i < L - 1; ++i)
+      PMG_TRY(transfer_f32_prepare(mg->interps[i], &mg->M1_32[i]));
+  }
+  mg->dinv32.assign(L, nullptr);
+  for (int i = 0; i < L; ++i)
+  {
+    PMG_TRY(laplacian_f32_prepare(mg->ops[i], s));
+    PMG_TRY(laplacian_f32_diag(mg->ops[i], &mg->dinv32[i], s, nullptr));
+  }
+  return PMG_OK;
+}
+
+// The V-cycle in FP32 (pmg_multigrid_set_precision): the caller's FP64 rhs / y at the finest level only.
+//   zero guess: y = double(V32(float(rhs)));
+//   otherwise (defect correction): y += double(V32(float(rhs - A y))), the defect formed with the FP64 operator -- the
+//   cycle is affine, so this is the FP64 cycle to float rounding, and stationary cycles keep converging below the
+//   float accuracy of a single cycle.
+// A Krylov, AMG or callback coarse solver runs in FP64 on the library's existing objects: b_0 is converted up and
+// u_0 down around it; the smoother-only coarse level runs in FP32.
+int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStream_t s)
+{
+  const int L = mg->L;
+  std::vector<long long> before(L);
+  for (int i = 0; i < L; ++i)
+    before[i] = laplacian_launches(mg->ops[i]);
+  PMG_TRY(mg_prepare_f32(mg, s));
+  Range cycle("pmg:vcycle_f32");
+  const int nf = mg->layouts[L - 1]->size_local;
+  if (y_zero)
+    launch_to_f32(nf, rhs, nullptr, mg->b32[L - 1], s);
+  else
+  {
+    double* q = mg->smoothers[L - 1]->q; // FP64 work vector of the finest level
+    PMG_TRY(laplacian_apply(mg->ops[L - 1], y, q, s));
+    launch_to_f32(nf, rhs, q, mg->b32[L - 1], s);
+  }
+  for (int i = L - 1; i > 0; --i)
+  {
+    pmg_chebyshev sm = mg->smoothers[i];
+    bool split = false;
+    {
+      Range rg("pmg:pre_smooth");
+      PMG_TRY(cheb_iterate_f32(mg->w32[i], mg->ops[i], mg->dinv32[i], mg->layouts[i]->size_local, sm->eig_max,
+                               sm->max_iter, mg->u32[i], mg->b32[i], ResidualSplit, true, s, &split));
+    }
+    Range rg("pmg:restrict");
+    PMG_TRY(restrict_f32(mg->interps[i - 1], mg->M1_32[i - 1], mg->w32[i].r, split ? mg->w32[i].q : nullptr,
+                         mg->b32[i - 1], s));
+  }
+  const int n0 = mg->layouts[0]->size_local;
+  if (L > 1)
+    launch_mask_bc_f32(n0, mg->b32[0], mg->bc0, s);
+  {
+    Range rg("pmg:coarse_solve");
+    if ((mg->coarse_amg || mg->coarse || mg->coarse_fn) && L > 1) // FP64 on the existing objects
+    {
+      launch_from_f32(n0, mg->b32[0], mg->b[0], false, s);
+      if (mg->coarse_amg)
+        PMG_TRY(amg_solve(mg->coarse_amg, mg->u[0], mg->b[0], s));
+      else
+      {
+        launch_zero(mg->layouts[0]->total(), mg->u[0], s);
+        if (mg->coarse_fn)
+        {
+          if (mg->coarse_fn(mg->coarse_user, mg->u[0], mg->b[0], (pmg_stream)s) != 0)
+            return fail(PMG_ERR_INVALID, "the coarse-solver callback failed");
+        }
+        else
+        {
+          int its = 0;
+          PMG_TRY(pmg_cg_solve(mg->coarse, mg->ops[0], mg->u[0], mg->b[0], nullptr, &its, (pmg_stream)s));
+        }
+      }
+      launch_to_f32(n0, mg->u[0], nullptr, mg->u32[0], s);
+    }
+    else
+    {
+      pmg_chebyshev sm = mg->smoothers[0];
+      PMG_TRY(cheb_iterate_f32(mg->w32[0], mg->ops[0], mg->dinv32[0], n0, sm->eig_max, sm->max_iter, mg->u32[0],
+                               mg->b32[0], ResidualNone, true, s, nullptr));
+    }
+  }
+  for (int i = 0; i < L - 1; ++i)
+  {
+    {
+      Range rg("pmg:prolong");
+      PMG_TRY(prolong_add_f32(mg->interps[i], mg->M1_32[i], mg->u32[i], mg->u32[i + 1], s));
+    }
+    Range rg("pmg:post_smooth");
+    pmg_chebyshev sm = mg->smoothers[i + 1];
+    PMG_TRY(cheb_iterate_f32(mg->w32[i + 1], mg->ops[i + 1], mg->dinv32[i + 1], mg->layouts[i + 1]->size_local,
+                             sm->eig_max, sm->max_iter, mg->u32[i + 1], mg->b32[i + 1], ResidualNone, false, s,
+                             nullptr));
+  }
+  launch_from_f32(nf, mg->u32[L - 1], y, !y_zero, s);
+  for (int i = 0; i < L; ++i)
+    mg->counts[i] = (int)(laplacian_launches(mg->ops[i]) - before[i]);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
 // src/pmg.hpp:56-155 (lean form, see the file header)
 int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStream_t s)
 {
@@ -232,6 +413,8 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
   PMG_REQUIRE((int)mg->ops.size() == L && (int)mg->smoothers.size() == L
                   && (int)mg->interps.size() == L - 1,
               "MultigridPreconditioner: operators / solvers / interpolators not set");
+  if (mg->precision == PMG_PRECISION_FP32)
+    return mg_apply_f32(mg, rhs, y, y_zero, s);
   std::vector<long long> before(L);
   for (int i = 0; i < L; ++i)
     before[i] = laplacian_launches(mg->ops[i]);
@@ -648,6 +831,7 @@ extern "C" int pmg_multigrid_destroy(pmg_multigrid mg)
     (void)hipGraphExecDestroy(g.exec);
   if (mg->capture_stream)
     (void)hipStreamDestroy(mg->capture_stream);
+  free_f32(mg);
   delete mg;
   return PMG_OK;
 }
@@ -678,6 +862,9 @@ extern "C" int pmg_multigrid_set_interpolators(pmg_multigrid mg, const pmg_inter
 {
   PMG_REQUIRE(mg && (interp || mg->L == 1), "pmg_multigrid_set_interpolators: NULL argument");
   drop_graphs(mg);
+  for (float* p : mg->M1_32) // the float transfer tables follow the interpolators
+    (void)hipFree(p);
+  mg->M1_32.clear();
   mg->interps.clear();
   for (int i = 0; i < mg->L - 1; ++i)
   {
@@ -768,6 +955,10 @@ long long capture_config(pmg_multigrid mg)
   }
   if (mg->coarse || mg->coarse_fn) // Krylov coarse solve / caller's solver: host in the loop
     return -1;
+  mix((uint64_t)mg->precision);
+  if (mg->precision == PMG_PRECISION_FP32) // the float diagonals are converted when the cycle is captured
+    for (int i = 0; i < mg->L; ++i)
+      mix((uint64_t)laplacian_diag_version(mg->ops[i]));
   if (mg->coarse_amg)
   {
     const long long st = amg_capture_state(mg->coarse_amg);
@@ -798,6 +989,8 @@ int mg_apply_graph(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, 
       *done = true;
       return PMG_OK;
     }
+  if (mg->precision == PMG_PRECISION_FP32) // allocations and conversions on the caller's stream, outside the capture
+    PMG_TRY(mg_prepare_f32(mg, s));
   if (!mg->capture_stream)
     PMG_HIP(hipStreamCreateWithFlags(&mg->capture_stream, hipStreamNonBlocking));
   PMG_HIP(hipStreamBeginCapture(mg->capture_stream, hipStreamCaptureModeRelaxed));
@@ -834,6 +1027,20 @@ extern "C" int pmg_multigrid_set_graph(pmg_multigrid mg, int enable)
   mg->graph_mode = enable < 0 ? -1 : (enable != 0 ? 1 : 0);
   return PMG_OK;
 }
+
+extern "C" int pmg_multigrid_set_precision(pmg_multigrid mg, int precision)
+{
+  PMG_REQUIRE(mg, "pmg_multigrid_set_precision: NULL argument");
+  PMG_REQUIRE(precision == PMG_PRECISION_FP64 || precision == PMG_PRECISION_FP32,
+              "pmg_multigrid_set_precision: unknown precision %d (PMG_PRECISION_FP64 or PMG_PRECISION_FP32)", precision);
+  if (precision == PMG_PRECISION_FP32)
+    PMG_TRY(mg_check_f32(mg, "pmg_multigrid_set_precision"));
+  drop_graphs(mg);
+  mg->precision = precision;
+  return PMG_OK;
+}
+
+extern "C" int pmg_multigrid_precision(pmg_multigrid mg) { return mg ? mg->precision : PMG_ERR_INVALID; }
 
 extern "C" long long pmg_multigrid_graph_replays(pmg_multigrid mg) { return mg ? mg->graph_replays : -1; }
 

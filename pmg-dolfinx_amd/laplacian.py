@@ -123,6 +123,19 @@ class MatFreeLaplacian:
     def __call__(self, x: Vector, y: Vector):  # operator()(in, out), :462-482
         call("pmg_laplacian_apply", self._handle, ptr(x.data), ptr(y.data), current_stream())
 
+    def apply_fp32(self, x, y):
+        """y = A x in FP32 (``pmg_laplacian_apply_f32``) on float32 device tensors of the layout's total size;
+        y is overwritten.  Single domain only."""
+        import torch
+
+        n = self.layout.size_local + self.layout.num_ghosts
+        for name, t in (("x", x), ("y", y)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError(f"{name} must be a contiguous float32 torch tensor")
+            if t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} entries, the layout {n}")
+        call("pmg_laplacian_apply_f32", self._handle, vp(x.data_ptr()), vp(y.data_ptr()), current_stream())
+
     def get_diag_inverse(self, diag_inv: Vector):  # :484-488
         call("pmg_laplacian_get_diag_inverse", self._handle, ptr(diag_inv.data), current_stream())
 

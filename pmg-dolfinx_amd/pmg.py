@@ -100,6 +100,21 @@ class MultigridPreconditioner:
         on several ranks when the capture holds nothing but kernels); see ``pmg_multigrid_set_graph``."""
         call("pmg_multigrid_set_graph", self._handle, -1 if enable is None else (1 if enable else 0))
 
+    PRECISIONS = {"fp64": 0, "fp32": 1}
+
+    def set_precision(self, precision: str):
+        """``"fp32"``: run the smoothers, operators and transfers of every level in FP32 (the caller's vectors
+        stay FP64; a non-zero initial guess is handled by defect correction); ``"fp64"`` (default) restores
+        the FP64 cycle.  Single domain only; see ``pmg_multigrid_set_precision``."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}, not {precision!r}")
+        call("pmg_multigrid_set_precision", self._handle, self.PRECISIONS[precision])
+
+    @property
+    def precision(self) -> str:
+        code = call("pmg_multigrid_precision", self._handle)
+        return {v: k for k, v in self.PRECISIONS.items()}[code]
+
     def graph_replays(self) -> int:
         return call("pmg_multigrid_graph_replays", self._handle)
 
