@@ -312,9 +312,10 @@ int pmg_laplacian_destroy(pmg_laplacian op);
 int pmg_laplacian_apply(pmg_laplacian op, double* in, double* out, pmg_stream stream);
 /* The same application in FP32 (the operator of the FP32 V-cycle, pmg_multigrid_set_precision): `in` and `out` are
  * device arrays of size_local floats; `out` is overwritten, Dirichlet rows are out = in, interior and boundary cell
- * lists are both applied.  The geometry tensor is computed in FP64 from the mesh, multiplied by kappa and rounded to
- * float once -- 24 bytes per quadrature point, built on the first FP32 use and freed with the operator; the patch
- * plan and its launches are the FP64 apply's, the cell sums are float.  Refused with PMG_ERR_INVALID: a layout with
+ * lists are both applied.  The geometry tensor is computed in FP64 from the mesh and rounded to float once -- 24 bytes
+ * per quadrature point, built on the first FP32 use and freed with the operator; kappa is read from the caller's array
+ * in every application (as in pmg_laplacian_apply: the caller may change it between two).  The patch plan and its
+ * launches are the FP64 apply's, the cell sums are float.  Refused with PMG_ERR_INVALID: a layout with
  * ghosts or a communicator (FP32 is single-domain only), an operator in batched-geometry mode.  The geometry mode
  * (affine cells) and the chain form do not apply: the float form always streams its stored tensor. */
 int pmg_laplacian_apply_f32(pmg_laplacian op, float* in, float* out, pmg_stream stream);
@@ -469,6 +470,13 @@ int pmg_interpolator_interpolate_add(pmg_interpolator ip, double* coarse, double
  * weighted transpose), updates the ghosts of `fine`, zeroes `coarse` first. */
 int pmg_interpolator_reverse_interpolate(pmg_interpolator ip, double* fine, double* coarse,
                                          pmg_stream stream);
+/* The two transfers of the FP32 V-cycle (pmg_multigrid_set_precision) on float device arrays of the layouts' sizes:
+ * fine += P coarse, and coarse = R (fine - fine_sub) (`coarse` is overwritten; fine_sub may be NULL: coarse = R fine).
+ * The float copy of the 1-D table is built on the first FP32 use and freed with the interpolator.  Refused with
+ * PMG_ERR_INVALID: an interpolator created without an operator, a layout with ghosts or a communicator. */
+int pmg_interpolator_interpolate_add_f32(pmg_interpolator ip, const float* coarse, float* fine, pmg_stream stream);
+int pmg_interpolator_reverse_interpolate_f32(pmg_interpolator ip, const float* fine, const float* fine_sub,
+                                             float* coarse, pmg_stream stream);
 
 /* ---- V-cycle (acc::MultigridPreconditioner, src/pmg.hpp:16-184) -----------
  * Levels are ordered coarse -> fine like the reference's vectors.  The handle

@@ -146,6 +146,8 @@ _SIGS = {
     "pmg_interpolator_destroy": (C.c_int, [vp]),
     "pmg_interpolator_interpolate": (C.c_int, [vp, vp, vp, vp]),
     "pmg_interpolator_reverse_interpolate": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_interpolator_interpolate_add_f32": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_interpolator_reverse_interpolate_f32": (C.c_int, [vp, vp, vp, vp, vp]),
     "pmg_multigrid_create": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), vp]),
     "pmg_multigrid_destroy": (C.c_int, [vp]),
     "pmg_multigrid_set_operators": (C.c_int, [vp, C.POINTER(vp)]),

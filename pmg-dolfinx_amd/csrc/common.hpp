@@ -267,7 +267,9 @@ int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s);      // float tensor
 int laplacian_f32_diag(pmg_laplacian op, const float** d, hipStream_t s, bool* changed);
 long long laplacian_diag_version(pmg_laplacian op);
 int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s);
-int transfer_f32_prepare(pmg_interpolator ip, float** M1); // float copy of the 1-D table (caller frees)
+float*& interp_m1_f32(pmg_interpolator ip); // the interpolator's float copy of its 1-D table (nullptr: not built)
+int transfer_f32_supported(pmg_interpolator ip, const char* who); // PMG_OK, or the refusal (no patch form, ghosts)
+int transfer_f32_prepare(pmg_interpolator ip, const float** M1);  // the float table, built on first use (allocates)
 int prolong_add_f32(pmg_interpolator ip, const float* M1, const float* coarse, float* fine, hipStream_t s);
 int restrict_f32(pmg_interpolator ip, const float* M1, const float* fine, const float* fine_sub, float* coarse,
                  hipStream_t s);

@@ -13,6 +13,7 @@ namespace pmg
 {
 int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s);
 TransferView interp_transfer_view(pmg_interpolator ip);
+bool interp_is_patched(pmg_interpolator ip);
 } // namespace pmg
 
 namespace
@@ -394,20 +395,44 @@ void launch_from_f32(int n, const float* in, double* out, bool add, hipStream_t 
 void launch_zero_f32(int n, float* x, hipStream_t s) { ew32(n, Zero32{x}, s); }
 void launch_mask_bc_f32(int n, float* b, const int8_t* bc, hipStream_t s) { ew32(n, MaskBc32{b, bc}, s); }
 
-// The float copy of a transfer's 1-D table (owned by the caller), LDS limits set; single-domain patch form only
-int transfer_f32_prepare(pmg_interpolator ip, float** M1)
+// Can the FP32 transfers run on this interpolator?  (0 = yes, else the refusal has been recorded)
+int transfer_f32_supported(pmg_interpolator ip, const char* who)
 {
+  PMG_REQUIRE(interp_is_patched(ip),
+              "%s: the FP32 transfers need a patch-form interpolator (pmg_interpolator_create_with_operator)", who);
   const TransferView v = interp_transfer_view(ip);
-  const int n = v.ndf * v.ndc;
-  std::vector<double> h(n);
-  PMG_HIP(hipMemcpy(h.data(), v.M1, sizeof(double) * n, hipMemcpyDeviceToHost));
-  std::vector<float> f(h.begin(), h.end());
-  PMG_HIP(hipMalloc(M1, sizeof(float) * n));
-  PMG_HIP(hipMemcpy(*M1, f.data(), sizeof(float) * n, hipMemcpyHostToDevice));
-  const size_t shm = transfer32_shm(v);
-  PMG_REQUIRE(shm <= 160 * 1024, "FP32 transfer kernels need %zu bytes of LDS", shm);
-  if (shm > 48 * 1024)
-    PMG_TRY(transfer32_lds(v.ndc, v.ndf, (int)shm));
+  for (pmg_layout l : {v.lc, v.lf})
+    PMG_REQUIRE(l->num_ghosts == 0 && !l->multi_rank() && !l->win,
+                "%s: the FP32 transfers are single-domain only (a layout has ghosts or a communicator)", who);
+  return PMG_OK;
+}
+
+// The interpolator's float copy of its 1-D table, built (and the LDS limits set) on first use; patch form only
+int transfer_f32_prepare(pmg_interpolator ip, const float** M1)
+{
+  float*& m = interp_m1_f32(ip);
+  if (!m)
+  {
+    const TransferView v = interp_transfer_view(ip);
+    const size_t shm = transfer32_shm(v);
+    PMG_REQUIRE(shm <= 160 * 1024, "FP32 transfer kernels need %zu bytes of LDS", shm);
+    if (shm > 48 * 1024)
+      PMG_TRY(transfer32_lds(v.ndc, v.ndf, (int)shm));
+    const int n = v.ndf * v.ndc;
+    std::vector<double> h(n);
+    PMG_HIP(hipMemcpy(h.data(), v.M1, sizeof(double) * n, hipMemcpyDeviceToHost));
+    std::vector<float> f(h.begin(), h.end());
+    float* d = nullptr;
+    PMG_HIP(hipMalloc(&d, sizeof(float) * n));
+    const hipError_t e = hipMemcpy(d, f.data(), sizeof(float) * n, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+      (void)hipFree(d);
+      return fail(PMG_ERR_HIP, "transfer_f32_prepare: %s", hipGetErrorString(e));
+    }
+    m = d;
+  }
+  *M1 = m;
   return PMG_OK;
 }
 
@@ -508,3 +533,23 @@ int cheb_iterate_f32(const ChebWork32& w, pmg_laplacian A, const float* dinv, in
   return PMG_OK;
 }
 } // namespace pmg
+
+extern "C" int pmg_interpolator_interpolate_add_f32(pmg_interpolator ip, const float* coarse, float* fine,
+                                                    pmg_stream stream)
+{
+  PMG_REQUIRE(ip && coarse && fine, "pmg_interpolator_interpolate_add_f32: NULL argument");
+  PMG_TRY(transfer_f32_supported(ip, "pmg_interpolator_interpolate_add_f32"));
+  const float* M1 = nullptr;
+  PMG_TRY(transfer_f32_prepare(ip, &M1));
+  return prolong_add_f32(ip, M1, coarse, fine, S(stream));
+}
+
+extern "C" int pmg_interpolator_reverse_interpolate_f32(pmg_interpolator ip, const float* fine, const float* fine_sub,
+                                                        float* coarse, pmg_stream stream)
+{
+  PMG_REQUIRE(ip && fine && coarse, "pmg_interpolator_reverse_interpolate_f32: NULL argument");
+  PMG_TRY(transfer_f32_supported(ip, "pmg_interpolator_reverse_interpolate_f32"));
+  const float* M1 = nullptr;
+  PMG_TRY(transfer_f32_prepare(ip, &M1));
+  return restrict_f32(ip, M1, fine, fine_sub, coarse, S(stream));
+}

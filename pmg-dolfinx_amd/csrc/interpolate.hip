@@ -30,6 +30,7 @@ struct pmg_interpolator_s
   int32_t* dmc_own = nullptr;   // ascending copies of dofmaps given in another cell-local node order
   int32_t* dmf_own = nullptr;   // (pmg_interpolator_create_ordered)
   double* M1 = nullptr;       // [ndf][ndc]
+  float* M1_32 = nullptr;     // float copy of M1, built on the first FP32 transfer (cycle_f32.hip)
   double* inv_mult = nullptr; // [fine total], 1/multiplicity (src/interpolate.hpp:172-178)
   int32_t* lcells = nullptr;  // nullptr = identity
   int32_t* bcells = nullptr;
@@ -678,6 +679,7 @@ int restrict_patched(pmg_interpolator ip, double* fine, const double* fine_sub, 
 namespace pmg
 {
 bool interp_is_patched(pmg_interpolator ip) { return ip->patched; }
+float*& interp_m1_f32(pmg_interpolator ip) { return ip->M1_32; }
 
 TransferView interp_transfer_view(pmg_interpolator ip)
 {
@@ -1029,6 +1031,7 @@ extern "C" int pmg_interpolator_destroy(pmg_interpolator ip)
   (void)hipFree(ip->clmaps);
   (void)hipFree(ip->pmult);
   (void)hipFree(ip->M1);
+  (void)hipFree(ip->M1_32);
   (void)hipFree(ip->inv_mult);
   (void)hipFree(ip->lcells);
   (void)hipFree(ip->bcells);

@@ -74,7 +74,7 @@ struct pmg_laplacian_s
   size_t prof_used = 0;
   long long prof_launches = 0;
   // single-precision form of the operator (laplacian_f32.hip; built on first use, freed with the handle)
-  float2* G32 = nullptr;          // [nslots][layer c][3][nd*nd]: kappa * G, rounded once (the default layout of G)
+  float2* G32 = nullptr;          // [nslots][layer c][3][nd*nd]: G (without kappa), rounded once (the default layout of G)
   float* D32 = nullptr;           // [nd*nd]
   float* diag32 = nullptr;        // [size_local + num_ghosts] float copy of diag_inv
   long long diag_version = 0;     // bumped whenever diag_inv changes; diag32 is current while the two agree

@@ -4,11 +4,13 @@
 // Same patch plan as the FP64 apply (laplacian.hip): one workgroup per patch, the patch's x values and y sums in
 // LDS, the colours launched in plan order with plain stores, the merged launch of a small level and of the boundary
 // shell adding with float atomics, bzero cleared first, Dirichlet rows y = x written by their first patch.  What
-// changes is the width of every byte: the stored tensor is float (24 B per quadrature point instead of 48), kappa is
-// folded into it, the vectors are float, and the cell sums meet in LDS with ds_add_f32.
+// changes is the width of every byte: the stored tensor is float (24 B per quadrature point instead of 48), the vectors
+// are float, and the cell sums meet in LDS with ds_add_f32.  kappa is read from the caller's array in every
+// application and multiplies the cell's input, as in the FP64 kernels (the caller may change it between two).
 //
-// The tensor is computed in FP64 from the mesh (the Jacobian of laplacian.hpp) and rounded once, on the first FP32
-// use of the operator; it is never converted from the FP64 tensor (which may not be resident: batched geometry).
+// The tensor (without kappa) is computed in FP64 from the mesh (the Jacobian of laplacian.hpp) and rounded once, on the
+// first FP32 use of the operator; it is never converted from the FP64 tensor (which may not be resident: batched
+// geometry).
 //
 // One kernel form for every degree: the column scheme of laplacian.hip without its build options -- a lane owns the
 // (a, b) column of a cell, keeps the column's values in registers and marches through the nd layers; the x and y
@@ -77,11 +79,11 @@ __device__ __forceinline__ float2 gload32(const float2* p)
     return *p;
 }
 
-// kappa * G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]
+// G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]
 __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __restrict__ pcell,
                                     const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
                                     const double* __restrict__ dphi, const double* __restrict__ w,
-                                    const double* __restrict__ kappa, float2* __restrict__ G)
+                                    float2* __restrict__ G)
 {
   const int nsq = nd * nd, nq = nsq * nd;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,7 +97,7 @@ __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __r
   {
     double K[3][3], detJ;
     jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
-    const double s = kappa[c] * w[q] / detJ;
+    const double s = w[q] / detJ;
     g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
     g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
     g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
@@ -115,7 +117,8 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
     stiffness_f32_kernel(const float* __restrict__ x, float* __restrict__ y, const float2* __restrict__ G,
                          const int32_t* __restrict__ poff, const uint32_t* __restrict__ pdofs,
                          const int32_t* __restrict__ lmap_id, const uint16_t* __restrict__ lmaps,
-                         const int32_t* __restrict__ pncell, const float* __restrict__ Dg, int first, int atomic_out)
+                         const int32_t* __restrict__ pcell, const int32_t* __restrict__ pncell,
+                         const double* __restrict__ kappa, const float* __restrict__ Dg, int first, int atomic_out)
 {
   using Sh = Shape32<P>;
   constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, NG = Sh::NG, WPC = Sh::WPC, WL = Sh::WL;
@@ -126,6 +129,7 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
   __shared__ float sq[NG * WL];
   __shared__ float sgr[NG * WL];
   __shared__ float sgs[NG * WL];
+  __shared__ float skap[K];
 
   const int p = first + blockIdx.x;
   const int t = threadIdx.x;
@@ -168,6 +172,11 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
   }
   if (t < ND * ND)
     sD[t] = Dg[t];
+  for (int i = t; i < K; i += THREADS) // kappa of the patch's cells (empty slots: any finite value, never added)
+  {
+    const int c = pcell[(size_t)p * K + i];
+    skap[i] = (float)kappa[c >= 0 ? c : 0];
+  }
   lds_barrier32();
 
   const int wave = (t >> 6) / WPC, lane = (t & 63) + 64 * ((t >> 6) % WPC);
@@ -216,11 +225,13 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
       gq[d][1] = gload32<NT>(Gb + (o + NQ2));
       gq[d][2] = gload32<NT>(Gb + (o + 2 * NQ2));
     }
+    // kappa multiplies the cell's input once (the operator is linear in it), as in the FP64 kernels
+    const float kap = skap[slotc];
     float u[ND], Aq[ND];
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
-      u[k] = sx[l[k]];
+      u[k] = kap * sx[l[k]];
       Aq[k] = 0.0f;
     }
 #pragma unroll
@@ -328,12 +339,12 @@ void launch_f32(pmg_laplacian op, const float* x, float* y, int first, int count
 {
   if (nt)
     stiffness_f32_kernel<P, true><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
-                                                                      op->lmap_id, op->lmaps, op->pncell, op->D32,
-                                                                      first, atomic_out);
+                                                                      op->lmap_id, op->lmaps, op->pcell, op->pncell,
+                                                                      op->kappa, op->D32, first, atomic_out);
   else
     stiffness_f32_kernel<P, false><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
-                                                                       op->lmap_id, op->lmaps, op->pncell, op->D32,
-                                                                       first, atomic_out);
+                                                                       op->lmap_id, op->lmaps, op->pcell, op->pncell,
+                                                                       op->kappa, op->D32, first, atomic_out);
 }
 
 int launch_patches_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, bool nt,
@@ -381,7 +392,7 @@ int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
   if (n > 0)
     geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
                                                                     op->geom_dofmap, op->dphi_geom, op->gweights,
-                                                                    op->kappa, op->G32);
+                                                                    op->G32);
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }

@@ -95,13 +95,13 @@ struct pmg_multigrid_s
   std::vector<GraphEntry> graphs;
   hipStream_t capture_stream = nullptr;
   long long graph_replays = 0;
-  // FP32 cycle (pmg_multigrid_set_precision): float vectors of every level and float copies of the transfer tables,
-  // allocated on the first FP32 cycle; the operators hold their own float forms (laplacian_f32.hip)
+  // FP32 cycle (pmg_multigrid_set_precision): float vectors of every level, allocated on the first FP32 cycle; the
+  // operators and interpolators hold their own float forms (laplacian_f32.hip, cycle_f32.hip)
   int precision = PMG_PRECISION_FP64;
   std::vector<float*> u32, b32;
   std::vector<ChebWork32> w32;
-  std::vector<float*> M1_32;          // per interpolator (dropped when the interpolators change)
   std::vector<const float*> dinv32;   // per level, the operators' float diagonals (refreshed by mg_prepare_f32)
+  std::vector<const float*> M1_32;    // per interpolator, its float 1-D table (owned by the interpolator)
 };
 
 namespace pmg
@@ -262,12 +262,9 @@ void free_f32(pmg_multigrid mg)
     (void)hipFree(w.z);
     (void)hipFree(w.q);
   }
-  for (float* p : mg->M1_32)
-    (void)hipFree(p);
   mg->u32.clear();
   mg->b32.clear();
   mg->w32.clear();
-  mg->M1_32.clear();
 }
 
 int alloc_vec_f32(pmg_layout l, float** p)
@@ -300,14 +297,9 @@ int mg_prepare_f32(pmg_multigrid mg, hipStream_t s)
       PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].q));
     }
   }
-  if ((int)mg->M1_32.size() != L - 1)
-  {
-    for (float* p : mg->M1_32)
-      (void)hipFree(p);
-    mg->M1_32.assign(L - 1, nullptr);
-    for (int i = 0; i < L - 1; ++i)
-      PMG_TRY(transfer_f32_prepare(mg->interps[i], &mg->M1_32[i]));
-  }
+  mg->M1_32.assign(L - 1, nullptr);
+  for (int i = 0; i < L - 1; ++i)
+    PMG_TRY(transfer_f32_prepare(mg->interps[i], &mg->M1_32[i]));
   mg->dinv32.assign(L, nullptr);
   for (int i = 0; i < L; ++i)
   {
@@ -862,9 +854,6 @@ extern "C" int pmg_multigrid_set_interpolators(pmg_multigrid mg, const pmg_inter
 {
   PMG_REQUIRE(mg && (interp || mg->L == 1), "pmg_multigrid_set_interpolators: NULL argument");
   drop_graphs(mg);
-  for (float* p : mg->M1_32) // the float transfer tables follow the interpolators
-    (void)hipFree(p);
-  mg->M1_32.clear();
   mg->interps.clear();
   for (int i = 0; i < mg->L - 1; ++i)
   {

@@ -61,6 +61,34 @@ class Interpolator:
         call("pmg_interpolator_reverse_interpolate", self._handle, ptr(Q2_vector.data), ptr(Q1_vector.data),
              current_stream())
 
+    def interpolate_add_fp32(self, coarse, fine):
+        """fine += P coarse in FP32 (``pmg_interpolator_interpolate_add_f32``) on float32 device tensors of the two
+        layouts' total sizes.  Patch form (``fine_operator``) and single domain only."""
+        self._check_fp32(coarse=(coarse, self.lc), fine=(fine, self.lf))
+        call("pmg_interpolator_interpolate_add_f32", self._handle, vp(coarse.data_ptr()), vp(fine.data_ptr()),
+             current_stream())
+
+    def reverse_interpolate_fp32(self, fine, coarse, fine_sub=None):
+        """coarse = R (fine - fine_sub) in FP32 (``pmg_interpolator_reverse_interpolate_f32``); ``coarse`` is
+        overwritten, ``fine_sub`` is optional.  Patch form (``fine_operator``) and single domain only."""
+        vecs = dict(fine=(fine, self.lf), coarse=(coarse, self.lc))
+        if fine_sub is not None:
+            vecs["fine_sub"] = (fine_sub, self.lf)
+        self._check_fp32(**vecs)
+        call("pmg_interpolator_reverse_interpolate_f32", self._handle, vp(fine.data_ptr()),
+             vp(fine_sub.data_ptr()) if fine_sub is not None else vp(0), vp(coarse.data_ptr()), current_stream())
+
+    @staticmethod
+    def _check_fp32(**vecs):
+        import torch
+
+        for name, (t, layout) in vecs.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError(f"{name} must be a contiguous float32 torch tensor")
+            n = layout.size_local + layout.num_ghosts
+            if t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} entries, the layout {n}")
+
     def __del__(self):
         try:
             if getattr(self, "_handle", None) is not None:

@@ -6,7 +6,7 @@ usage: python tools/fp32_cycle.py [--n 64] [--orders 1,2,4] [--orders 1,3,6] [--
 
 Timing (measuring-on-mi355x): warm-up first, then `repeats` timed runs of `reps` back-to-back calls bracketed by
 HIP events; the median run is reported.  The FP32 kernel's fraction of 8 TB/s is computed on the byte model
-24N [float G, kappa folded in] + 4N [patch lists] + 9U [x, y, bc] bytes per cell, next to the FP64 model
+24N [float G] + 4N [patch lists] + 9U [x, y, bc] bytes per cell (kappa: 12 B per cell, left out), next to the FP64 model
 48N + 4N + 8 + 17U (bench.py)."""
 import argparse
 import json
