@@ -239,7 +239,12 @@ int pmg_scatter_rev_end(pmg_layout l, double* x, pmg_stream stream);
 /* ---- BLAS-1 (free functions of src/vector.hpp:333-454) ---------------------
  * Ranges follow the reference: set and scale touch owned+ghost entries
  * (:109-115, :413-418); axpy, copy, pointwise_mult and the reductions touch the
- * owned entries only (:398-407, :424-431, :438-447, :334-352). */
+ * owned entries only (:398-407, :424-431, :438-447, :334-352).
+ * Alignment: a vector needs the 8 bytes of a double, no more -- a sub-span of a larger
+ * allocation is a legal argument here and wherever a function takes a vector (smoothers, CG,
+ * the V-cycle).  Operands that all sit on 16-byte boundaries take the double2 kernels, any other
+ * combination the scalar ones, with the same results to rounding.
+ * A NaN in the owned entries comes out of every reduction, norm(linf) included. */
 int pmg_vec_set(pmg_layout l, double* x, double value, pmg_stream stream);
 int pmg_vec_scale(pmg_layout l, double* x, double alpha, pmg_stream stream);
 int pmg_vec_copy(pmg_layout l, double* dst, const double* src, pmg_stream stream);

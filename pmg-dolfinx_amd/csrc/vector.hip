@@ -489,10 +489,12 @@ __device__ inline double wave_sum(double v)
     v += __shfl_down(v, off, 64);
   return v;
 }
+// the maximum that keeps a NaN (fmax drops it: the linf norm of a poisoned vector would come out finite)
+__device__ inline double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
 __device__ inline double wave_max(double v)
 {
   for (int off = 32; off > 0; off >>= 1)
-    v = fmax(v, __shfl_down(v, off, 64));
+    v = nan_max(v, __shfl_down(v, off, 64));
   return v;
 }
 
@@ -542,7 +544,7 @@ __global__ void absmax_partial_kernel(int n, const double* __restrict__ a,
 {
   double acc = 0.0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    acc = fmax(acc, fabs(a[i]));
+    acc = nan_max(acc, fabs(a[i]));
   acc = block_reduce<true>(acc);
   if (threadIdx.x == 0)
     partials[blockIdx.x] = acc;
@@ -553,7 +555,7 @@ __global__ void fold_kernel(int nb, const double* __restrict__ partials, double*
 {
   double acc = 0.0;
   for (int i = threadIdx.x; i < nb; i += blockDim.x)
-    acc = MAX ? fmax(acc, partials[i]) : acc + partials[i];
+    acc = MAX ? nan_max(acc, partials[i]) : acc + partials[i];
   acc = block_reduce<MAX>(acc);
   if (threadIdx.x == 0)
     out[0] = acc;

@@ -768,7 +768,7 @@ __global__ void wcomm_get_kernel(const WCommDev* __restrict__ wp, int m, double*
       if (MODE == 2)
         dst[(size_t)r * m + j] = v;
       else if (MODE == 1)
-        acc = r == 0 ? v : fmax(acc, v);
+        acc = r == 0 ? v : ((acc > v || acc != acc) ? acc : v); // keeps a rank's NaN, which fmax would drop
       else
         acc = r == 0 ? v : acc + v;
     }
