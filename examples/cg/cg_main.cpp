@@ -40,6 +40,7 @@ namespace
 struct Options : examples::RankOptions
 {
   int n = 16, order = 3, cg_its = 20, cheb_its = 30;
+  bool csr = false; // --csr: the eigenvalue estimate on the assembled operator (examples/cg/main.cpp:224-229)
 };
 
 void upload(DeviceVector& v, const std::vector<T>& h)
@@ -122,7 +123,15 @@ void solve(const Options& o)
   cg.store_coefficients(true);
 
   auto t0 = std::chrono::steady_clock::now();
-  int its = cg.solve(op, x, b_d, false);
+  std::unique_ptr<acc::MatrixOperator<T>> mat; // :224: the reference's estimate runs on its MatrixOperator
+  if (o.csr)
+  {
+    mat = std::make_unique<acc::MatrixOperator<T>>(op, map);
+    if (root)
+      std::printf("CSR nnz = %zu\n", mat->nnz());
+    t0 = std::chrono::steady_clock::now();
+  }
+  int its = mat ? cg.solve(*mat, x, b_d, false) : cg.solve(op, x, b_d, false);
   hip_check(hipDeviceSynchronize(), "sync");
   const double t_cg = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
@@ -204,6 +213,8 @@ int main(int argc, char** argv)
         o.order = std::atoi(next());
       else if (!std::strcmp(argv[i], "--cg-its"))
         o.cg_its = std::atoi(next());
+      else if (!std::strcmp(argv[i], "--csr"))
+        o.csr = true;
       else if (!std::strcmp(argv[i], "--cheb-its"))
         o.cheb_its = std::atoi(next());
       else if (!std::strcmp(argv[i], "--ranks"))
@@ -220,7 +231,7 @@ int main(int argc, char** argv)
         o.id_file = next();
       else
       {
-        std::cout << "usage: cg [--n cells_per_direction | --ndofs N_per_rank] [--degree P] [--cg-its N] [--cheb-its N]\n"
+        std::cout << "usage: cg [--n cells_per_direction | --ndofs N_per_rank] [--degree P] [--cg-its N] [--cheb-its N] [--csr]\n"
                      "          [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows] [--comm rccl|windows]\n";
         return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
       }

@@ -10,6 +10,7 @@
 //   --amg            coarse solver on the degree-1 level (:331-335): CG <= 60 iterations, rtol 1e-5,
 //                    preconditioned by the library's algebraic multigrid (hypre's role)
 //   --amg-cycles N   the same hierarchy as N stationary AMG cycles instead of the Krylov solve
+//   --csr [LEVELS]   the listed levels (comma-separated indices; default all) as assembled CSR matrices
 //   --coarse-cg      Jacobi-preconditioned CG (60 iterations) as the coarse solver
 //   --pcg            additionally solve with CG preconditioned by the cycle (random right-hand side
 //                    with --random-rhs)
@@ -79,6 +80,8 @@ struct Options : examples::RankOptions
   std::string output;
   pmg_amd::NodeOrder node_order = pmg_amd::NodeOrder::ascending; // of the dofmaps handed to the library
   bool amg_gather = false; // --amg-setup gathered
+  bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
+  std::vector<int> csr_levels; // empty with --csr: every level
 };
 using examples::parse3;
 
@@ -158,6 +161,20 @@ void solve(const Options& o)
     operators[i]->assemble_rhs(f, *bs[i]); // :289-300
   }
 
+  // --csr: the listed levels (default: all) as assembled matrices, the reference's solve<acc::MatrixOperator<T>>
+  // (examples/pmg/main.cpp:285,457-458); the eigenvalue estimate, the smoother and the residual of such a level run
+  // on the matrix, the transfers stay on the matrix-free operator's patches
+  std::vector<std::shared_ptr<acc::MatrixOperator<T>>> matrices(V.size());
+  if (o.csr)
+    for (std::size_t i = 0; i < V.size(); i++)
+    {
+      if (!o.csr_levels.empty() && std::find(o.csr_levels.begin(), o.csr_levels.end(), (int)i) == o.csr_levels.end())
+        continue;
+      matrices[i] = std::make_shared<acc::MatrixOperator<T>>(*operators[i], maps[i]);
+      if (root)
+        std::printf("Level %zu: CSR nnz = %zu, A norm = %.15e\n", i, matrices[i]->nnz(), matrices[i]->norm());
+    }
+
   // ---------------------------------------------------------------------------------------------
   // From here to the end of the cycle loop: examples/pmg/main.cpp:303-367 (logging calls dropped,
   // Chebyshev degree and cycle count from the command line).
@@ -177,7 +194,7 @@ void solve(const Options& o)
     DeviceVector y(maps[i], 1);
     y.set(T{1.0});
 
-    [[maybe_unused]] int its = cg.solve(*operators[i], x, y, false);
+    [[maybe_unused]] int its = matrices[i] ? cg.solve(*matrices[i], x, y, false) : cg.solve(*operators[i], x, y, false);
     std::vector<T> eign = cg.compute_eigenvalues();
     std::sort(eign.begin(), eign.end());
     if (root)
@@ -235,6 +252,10 @@ void solve(const Options& o)
     coarse_cg->set_tolerance(1e-5);
     check(pmg_multigrid_set_coarse_solver(pmg.handle(), coarse_cg->handle()));
   }
+
+  for (std::size_t i = 0; i < V.size(); i++)
+    if (matrices[i])
+      pmg.set_level_matrix((int)i, matrices[i]->matrix_handle());
 
   if (o.fp32_cycle)
   {
@@ -377,6 +398,16 @@ int main(int argc, char** argv)
         o.graph = true;
       else if (!std::strcmp(argv[i], "--fp32-cycle"))
         o.fp32_cycle = true;
+      else if (!std::strcmp(argv[i], "--csr"))
+      {
+        o.csr = true;
+        if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') // optional list of level indices
+        {
+          std::stringstream ss(argv[++i]);
+          for (std::string tok; std::getline(ss, tok, ',');)
+            o.csr_levels.push_back(std::atoi(tok.c_str()));
+        }
+      }
       else if (!std::strcmp(argv[i], "--coarse-cg"))
         o.coarse_cg = true;
       else if (!std::strcmp(argv[i], "--amg"))
@@ -432,7 +463,7 @@ int main(int argc, char** argv)
       else
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
-                     "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle]\n"
+                     "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"

@@ -46,6 +46,7 @@ typedef struct pmg_cg_s* pmg_cg;
 typedef struct pmg_interpolator_s* pmg_interpolator;
 typedef struct pmg_multigrid_s* pmg_multigrid;
 typedef struct pmg_amg_s* pmg_amg;
+typedef struct pmg_matrix_s* pmg_matrix;
 
 const char* pmg_last_error(void);
 int pmg_version(void);
@@ -433,6 +434,50 @@ int pmg_cg_coefficients(pmg_cg s, double* alphas, double* betas, int capacity);
 int pmg_cg_compute_eigenvalues(pmg_cg s, double* eigs, int capacity);
 int pmg_cg_residual(pmg_cg s, double* rnorm);
 
+/* ---- assembled operator (acc::MatrixOperator, src/csr.hpp:58-131,205-260) ----
+ * The BC-treated stiffness matrix in CSR on the device, applied by SpMV: the second operator type behind the
+ * reference's interface (examples/pmg/main.cpp:69,285,457-458 solve<MatrixOperator>; examples/cg/main.cpp:224;
+ * examples/mat_free/main.cpp:270-288 --mat_comp; test/test_csr.cpp).
+ *
+ * pmg_matrix_create_from_laplacian restates MatrixOperator(a, bcs), src/csr.hpp:66-131, from what the operator
+ * already holds -- its own (ascending) copy of the dofmap, the stored geometry tensor, the caller's kappa and BC
+ * marker -- so the matrix lives in the operator's dof numbering and the cell-local node order the operator was
+ * created with does not change it.
+ *   pattern: dolfinx's create_sparsity_pattern (:76-77) -- row i couples to every dof that shares a cell with i --,
+ *            columns sorted within a row, int32 indices, built once on the host.  Dirichlet rows and columns stay in
+ *            the pattern as explicit zeros with a unit diagonal (:84-86), so nnz equals the reference's.
+ *   values:  one HIP kernel evaluates the element matrices in closed form and sums them row by row (a sub-wavefront
+ *            per row gathers from the cells incident to the row: no atomics, two assemblies give the same bits).
+ * kappa is read at ASSEMBLY time only (unlike pmg_laplacian_apply, which reads it in every application):
+ * pmg_matrix_update_values re-evaluates the values and the inverse diagonal on the existing pattern.  The geometry
+ * mode (affine cells) and the chain form of the operator do not matter: assembly always reads the stored tensor.
+ * `op` must outlive the matrix.  Degrees 1..PMG_MAX_DEGREE.
+ * Refused with PMG_ERR_INVALID (message in pmg_last_error; *out stays NULL): a layout with ghosts or a communicator
+ * (single-domain only; the distributed diag / off-diag form of :114-126 is a follow-up), an operator in
+ * batched-geometry mode (G is not resident), a pattern whose nnz does not fit int32 (the message states the nnz). */
+int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian op, pmg_stream stream);
+int pmg_matrix_destroy(pmg_matrix M);
+int pmg_matrix_update_values(pmg_matrix M, pmg_stream stream);
+/* operator()(x, y), src/csr.hpp:220-260: out = A in, one launch; `out` is overwritten (no zero-fill needed).  No
+ * transpose variant: the operator is symmetric. */
+int pmg_matrix_apply(pmg_matrix M, const double* in, double* out, pmg_stream stream);
+/* get_diag_inverse, src/csr.hpp:100-110,205-209: the owned entries; BC rows give 1. */
+int pmg_matrix_get_diag_inverse(pmg_matrix M, double* diag_inv, pmg_stream stream);
+/* num_rows and nnz of src/csr.hpp:91-93 (the reference's nnz() accessor); device bytes held by the handle. */
+long long pmg_matrix_rows(pmg_matrix M);
+long long pmg_matrix_nnz(pmg_matrix M);
+long long pmg_matrix_bytes(pmg_matrix M);
+/* The "A norm" logged at src/csr.hpp:95-99: sqrt(sum of squared values). */
+int pmg_matrix_frobenius_norm(pmg_matrix M, double* norm);
+/* Host copy of the device arrays the reference uploads at src/csr.hpp:114-130 (tests).  NULL arrays: sizes only. */
+int pmg_matrix_export(pmg_matrix M, long long* rows, long long* nnz, int32_t* row_ptr, int32_t* cols, double* values);
+/* Chebyshev::solve / CGSolver::solve with an acc::MatrixOperator as the operator (src/chebyshev.hpp:46-91,
+ * src/cg.hpp:147-222 are templated on it): the semantics of pmg_chebyshev_solve / pmg_cg_solve with the matrix's
+ * product and the matrix's own inverse diagonal. */
+int pmg_chebyshev_solve_matrix(pmg_chebyshev s, pmg_matrix M, double* x, const double* b, pmg_stream stream);
+int pmg_cg_solve_matrix(pmg_cg s, pmg_matrix M, double* x, const double* b, pmg_multigrid precond, int* iterations,
+                        pmg_stream stream);
+
 /* ---- p-transfer (Interpolator<T>, src/interpolate.hpp:93-329) -------------
  * Coarse (Q1) and fine (Q2) spaces on the same cells; dofmaps as for the
  * operator; lcells/bcells as there. */
@@ -613,6 +658,16 @@ int pmg_multigrid_apply_counts(pmg_multigrid mg, int* counts, int capacity);
 #define PMG_PRECISION_FP64 0
 #define PMG_PRECISION_FP32 1
 int pmg_multigrid_set_precision(pmg_multigrid mg, int precision);
+/* set_operators with acc::MatrixOperator levels (src/pmg.hpp:48 in solve<MatrixOperator>,
+ * examples/pmg/main.cpp:285,348-355), one opt-in switch per level: every operator application the cycle issues on
+ * `level` -- the smoother's, and whatever forms that level's residual -- becomes the matrix's product with the
+ * matrix's inverse diagonal; NULL removes the matrix again.  The level's pmg_laplacian stays attached and the
+ * transfers keep running on its patches.  pmg_multigrid_apply_counts keeps counting applications per level whichever
+ * form ran them.  The set of level matrices is part of the graph key (a cached graph is never replayed after it
+ * changes).  Refused with PMG_ERR_INVALID: a matrix on another layout than the level's; a matrix together with
+ * PMG_PRECISION_FP32, in either order (there is no FP32 matrix).  A coarse AMG / CG / callback solver is unaffected.
+ * `M` must outlive `mg` or be removed first. */
+int pmg_multigrid_set_level_matrix(pmg_multigrid mg, int level, pmg_matrix M);
 int pmg_multigrid_precision(pmg_multigrid mg);
 
 #ifdef __cplusplus

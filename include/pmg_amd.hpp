@@ -696,6 +696,58 @@ private:
   pmg_laplacian _op = nullptr;
 };
 
+/// acc::MatrixOperator<T> (src/csr.hpp:58-260): the BC-treated stiffness matrix assembled into CSR on the device
+/// and applied by SpMV.  Where the reference assembles from the form (MatrixOperator(a, bcs), :66-131) this one
+/// assembles from the matrix-free operator of the same form -- its geometry tensor, dofmap, coefficient and BC
+/// marker -- on the index map of the level.  Single domain only.  `A` must outlive the matrix.
+template <typename T>
+class MatrixOperator
+{
+  static_assert(std::is_same_v<T, double>, "pmg_amd: the library computes in double");
+
+public:
+  using value_type = T;
+
+  MatrixOperator(MatFreeLaplacian<T>& A, std::shared_ptr<const IndexMap> map) : _A(&A), _map(std::move(map))
+  {
+    check(pmg_matrix_create_from_laplacian(&_m, A.handle(_map), nullptr));
+  }
+  MatrixOperator(const MatrixOperator&) = delete;
+  MatrixOperator& operator=(const MatrixOperator&) = delete;
+  ~MatrixOperator() { pmg_matrix_destroy(_m); }
+
+  /// y = A x (:220-260)
+  template <typename Vector>
+  void operator()(Vector& x, Vector& y)
+  {
+    require_same_map(x, y);
+    check(pmg_matrix_apply(_m, x.array().data(), y.mutable_array().data(), nullptr));
+  }
+  template <typename Vector>
+  void get_diag_inverse(Vector& diag_inv) // :205-209
+  {
+    check(pmg_matrix_get_diag_inverse(_m, diag_inv.mutable_array().data(), nullptr));
+  }
+  /// Re-assemble the values after the coefficient changed in place (it is read at assembly time only).
+  void update_values() { check(pmg_matrix_update_values(_m, nullptr)); }
+  std::size_t nnz() const { return (std::size_t)pmg_matrix_nnz(_m); } // :92-93
+  std::size_t rows() const { return (std::size_t)pmg_matrix_rows(_m); }
+  T norm() const // the "A norm" of :95-99
+  {
+    double r = 0;
+    check(pmg_matrix_frobenius_norm(_m, &r));
+    return r;
+  }
+  pmg_matrix matrix_handle() const { return _m; }
+  MatFreeLaplacian<T>& laplacian() { return *_A; }
+  const std::shared_ptr<const IndexMap>& map() const { return _map; }
+
+private:
+  MatFreeLaplacian<T>* _A;
+  std::shared_ptr<const IndexMap> _map;
+  pmg_matrix _m = nullptr;
+};
+
 /// acc::Chebyshev<Vector> (src/chebyshev.hpp:19-106).
 template <typename Vector>
 class Chebyshev
@@ -714,7 +766,10 @@ public:
   template <typename Operator>
   void solve(Operator& A, Vector& x, const Vector& b, bool /*verbose*/ = false) // :46-91
   {
-    check(pmg_chebyshev_solve(_s, A.handle(x.map()), x.mutable_array().data(), b.array().data(), nullptr));
+    if constexpr (requires { A.matrix_handle(); }) // acc::MatrixOperator
+      check(pmg_chebyshev_solve_matrix(_s, A.matrix_handle(), x.mutable_array().data(), b.array().data(), nullptr));
+    else
+      check(pmg_chebyshev_solve(_s, A.handle(x.map()), x.mutable_array().data(), b.array().data(), nullptr));
   }
   pmg_chebyshev handle() const { return _s; }
 
@@ -747,7 +802,11 @@ public:
   int solve(Operator& A, Vector& x, const Vector& b, bool /*verbose*/ = false)
   {
     int its = 0;
-    check(pmg_cg_solve(_s, A.handle(x.map()), x.mutable_array().data(), b.array().data(), nullptr, &its, nullptr));
+    if constexpr (requires { A.matrix_handle(); }) // acc::MatrixOperator
+      check(pmg_cg_solve_matrix(_s, A.matrix_handle(), x.mutable_array().data(), b.array().data(), nullptr, &its,
+                                nullptr));
+    else
+      check(pmg_cg_solve(_s, A.handle(x.map()), x.mutable_array().data(), b.array().data(), nullptr, &its, nullptr));
     return its;
   }
   /// CG preconditioned by one V-cycle per iteration (BASELINE config 2; not in the reference).
@@ -756,8 +815,12 @@ public:
   int solve(Operator& A, Vector& x, const Vector& b, MG& precond, bool /*verbose*/ = false)
   {
     int its = 0;
-    check(pmg_cg_solve(_s, A.handle(x.map()), x.mutable_array().data(), b.array().data(), precond.handle(), &its,
-                       nullptr));
+    if constexpr (requires { A.matrix_handle(); }) // acc::MatrixOperator
+      check(pmg_cg_solve_matrix(_s, A.matrix_handle(), x.mutable_array().data(), b.array().data(), precond.handle(),
+                                &its, nullptr));
+    else
+      check(pmg_cg_solve(_s, A.handle(x.map()), x.mutable_array().data(), b.array().data(), precond.handle(), &its,
+                         nullptr));
     return its;
   }
   std::vector<T> alphas() const { return coefficients().first; } // :118
@@ -987,6 +1050,13 @@ public:
   /// PMG_PRECISION_FP32: the cycle's smoothers, operators and transfers run in FP32, the vectors handed in stay
   /// FP64 (pmg_multigrid_set_precision; single domain only).  PMG_PRECISION_FP64 (default) restores the FP64 cycle.
   void set_precision(int precision) { check(pmg_multigrid_set_precision(_mg, precision)); }
+  /// One level on an assembled matrix (pmg_multigrid_set_level_matrix; nullptr removes it): the mixed hierarchy, next
+  /// to Operator = acc::MatrixOperator<T>, which assembles every level.
+  void set_level_matrix(int level, pmg_matrix M)
+  {
+    wire();
+    check(pmg_multigrid_set_level_matrix(_mg, level, M));
+  }
   /// x = rhs, y = initial guess in / result out (:56-155).  With verbose the final
   /// residual norm is computed and returned (the reference prints it, :147-150); else 0.
   T apply(const Vector& x, Vector& y, bool verbose = false)
@@ -1037,7 +1107,12 @@ private:
     std::vector<pmg_interpolator> ip;
     for (std::size_t i = 0; i < L; ++i)
     {
-      ops.push_back(_operators[i]->handle(_maps[i]));
+      // Operator = acc::MatrixOperator<T> (the reference's solve<MatrixOperator>, examples/pmg/main.cpp:285): the
+      // level keeps the matrix-free operator the matrix was assembled from (the transfers run on its patches)
+      if constexpr (requires(Operator& o) { o.matrix_handle(); })
+        ops.push_back(_operators[i]->laplacian().handle(_maps[i]));
+      else
+        ops.push_back(_operators[i]->handle(_maps[i]));
       sm.push_back(_solvers[i]->handle());
     }
     for (std::size_t i = 0; i + 1 < L; ++i)
@@ -1045,6 +1120,9 @@ private:
     check(pmg_multigrid_set_operators(_mg, ops.data()));
     check(pmg_multigrid_set_solvers(_mg, sm.data()));
     check(pmg_multigrid_set_interpolators(_mg, ip.data()));
+    if constexpr (requires(Operator& o) { o.matrix_handle(); })
+      for (std::size_t i = 0; i < L; ++i)
+        check(pmg_multigrid_set_level_matrix(_mg, (int)i, _operators[i]->matrix_handle()));
     _wired = true;
   }
   std::vector<std::shared_ptr<const IndexMap>> _maps;

@@ -178,13 +178,27 @@ _SIGS = {
     "pmg_multigrid_apply_counts": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int]),
     "pmg_multigrid_set_graph": (C.c_int, [vp, C.c_int]),
     "pmg_multigrid_graph_replays": (C.c_longlong, [vp]),
+    "pmg_matrix_create_from_laplacian": (C.c_int, [C.POINTER(vp), vp, vp]),
+    "pmg_matrix_destroy": (C.c_int, [vp]),
+    "pmg_matrix_update_values": (C.c_int, [vp, vp]),
+    "pmg_matrix_apply": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_matrix_get_diag_inverse": (C.c_int, [vp, vp, vp]),
+    "pmg_matrix_rows": (C.c_longlong, [vp]),
+    "pmg_matrix_nnz": (C.c_longlong, [vp]),
+    "pmg_matrix_bytes": (C.c_longlong, [vp]),
+    "pmg_matrix_frobenius_norm": (C.c_int, [vp, c_dp]),
+    "pmg_matrix_export": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_ip, c_ip, c_dp]),
+    "pmg_chebyshev_solve_matrix": (C.c_int, [vp, vp, vp, vp, vp]),
+    "pmg_cg_solve_matrix": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
+    "pmg_multigrid_set_level_matrix": (C.c_int, [vp, C.c_int, vp]),
 }
 
 # functions whose int return value is a count, not a status
 _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplacian_geometry_bytes", "pmg_comm_rank", "pmg_comm_size", "pmg_comm_capture_overlaps", "pmg_cg_coefficients", "pmg_cg_compute_eigenvalues", "pmg_multigrid_apply_counts", "pmg_version",
                 "pmg_laplacian_degree", "pmg_multigrid_precision", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
-                "pmg_laplacian_node_order", "pmg_layout_forward_scatters"}
+                "pmg_laplacian_node_order", "pmg_layout_forward_scatters",
+                "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes"}
 
 _lib = None
 

@@ -38,8 +38,10 @@ class CGSolver:
         call("pmg_cg_set_flexible", self._handle, int(bool(val)))
 
     def solve(self, A, x: Vector, b: Vector, verbose: bool = False, preconditioner=None) -> int:  # :147-222
+        from .matrix import MatrixOperator
+
         its = C.c_int()
-        call("pmg_cg_solve", self._handle, A.handle, ptr(x.data), ptr(b.data),
+        call("pmg_cg_solve_matrix" if isinstance(A, MatrixOperator) else "pmg_cg_solve", self._handle, A.handle, ptr(x.data), ptr(b.data),
              preconditioner.handle if preconditioner is not None else vp(0), C.byref(its), current_stream())
         return its.value
 

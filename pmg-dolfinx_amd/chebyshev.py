@@ -24,7 +24,10 @@ class Chebyshev:
         call("pmg_chebyshev_set_max_iterations", self._handle, int(max_iter))
 
     def solve(self, A, x: Vector, b: Vector, verbose: bool = False):  # :46-91
-        call("pmg_chebyshev_solve", self._handle, A.handle, ptr(x.data), ptr(b.data), current_stream())
+        from .matrix import MatrixOperator
+
+        fn = "pmg_chebyshev_solve_matrix" if isinstance(A, MatrixOperator) else "pmg_chebyshev_solve"
+        call(fn, self._handle, A.handle, ptr(x.data), ptr(b.data), current_stream())
 
     def __del__(self):
         try:

@@ -2869,6 +2869,23 @@ extern "C" int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_s
   return PMG_OK;
 }
 
+namespace pmg
+{
+// used by matrix.hip: the resident tensor as [ncells][nq][6] with q in the library's own (ascending) node order,
+// whatever order the operator was created with -- the assembled matrix lives in the operator's dof numbering
+int laplacian_geometry_ascending(pmg_laplacian op, double* G_out, hipStream_t s)
+{
+  PMG_REQUIRE(op->batch_patches == 0, "the geometry tensor is not resident (batched-geometry mode)");
+  PMG_HIP(hipMemsetAsync(G_out, 0, sizeof(double) * 6 * (size_t)op->ncells * op->N, s));
+  const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
+  if (n > 0)
+    geometry_export_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(0, nslots, op->nd, op->K, op->pcell, nullptr,
+                                                                     op->G, G_out);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+} // namespace pmg
+
 extern "C" int pmg_laplacian_assemble_rhs(pmg_laplacian op, const double* f, double* b,
                                           pmg_stream stream)
 {

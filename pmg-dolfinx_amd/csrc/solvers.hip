@@ -43,6 +43,10 @@ void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, 
 bool laplacian_wants_zeroed_output(pmg_laplacian op);
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
+// matrix.hip -- the assembled form of a level's operator
+int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s);
+const double* matrix_diag_inv(pmg_matrix M);
+pmg_layout matrix_layout(pmg_matrix M);
 } // namespace pmg
 
 struct pmg_chebyshev_s
@@ -80,6 +84,10 @@ struct pmg_multigrid_s
   pmg_coarse_solve_fn coarse_fn = nullptr;
   void* coarse_user = nullptr;
   pmg_amg coarse_amg = nullptr;
+  // assembled levels (pmg_multigrid_set_level_matrix): where mats[i] is set, the matrix's product and inverse diagonal
+  // stand for every application of ops[i] in the cycle; mat_applies[i] counts them for pmg_multigrid_apply_counts
+  std::vector<pmg_matrix> mats;
+  std::vector<long long> mat_applies;
   // hipGraph replay of the cycle (pmg_multigrid_set_graph): one executable graph per
   // (rhs, y, zero-guess, configuration) seen
   struct GraphEntry
@@ -217,6 +225,36 @@ int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, in
                       s, split, laplacian_wants_zeroed_output(A) ? &apply_zeroed : nullptr, l->total(), track_ghosts,
                       x_ghosts_current ? &apply_local : nullptr);
 }
+
+// the same smoother on the assembled operator `M`: its product, its own inverse diagonal (single domain: no ghosts);
+// *applies (optional) counts the products issued
+int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b, int need_r, bool x_zero,
+                      hipStream_t s, bool* split = nullptr, long long* applies = nullptr)
+{
+  pmg_layout l = sm->layout;
+  PMG_REQUIRE(matrix_layout(M) == l, "Chebyshev: matrix and smoother layouts differ");
+  const ChebWork w{sm->r, sm->z, sm->q};
+  const ApplyFn apply = [M, s, applies](double* in, double* out)
+  {
+    if (applies)
+      ++*applies;
+    return matrix_apply(M, in, out, s);
+  };
+  return cheb_iterate(w, apply, matrix_diag_inv(M), l->size_local, sm->eig_max, sm->max_iter, x, b, need_r, x_zero, s,
+                      split);
+}
+
+// the smoother of level i on whichever form of the operator the level has (pmg_multigrid_set_level_matrix)
+int level_smooth(pmg_multigrid mg, int i, double* x, const double* b, int need_r, bool x_zero, hipStream_t s,
+                 bool* split = nullptr, bool track_ghosts = false, bool x_ghosts_current = false)
+{
+  if (mg->mats[i])
+    return cheb_solve_matrix(mg->smoothers[i], mg->mats[i], x, b, need_r, x_zero, s, split, &mg->mat_applies[i]);
+  return cheb_solve(mg->smoothers[i], mg->ops[i], x, b, need_r, x_zero, s, split, track_ghosts, x_ghosts_current);
+}
+
+// applications of level i's operator so far, in either form
+long long level_applies(pmg_multigrid mg, int i) { return laplacian_launches(mg->ops[i]) + mg->mat_applies[i]; }
 
 // Exchange bookkeeping on several ranks (round 4).  u_i leaves its pre-smooth with current ghosts (the smoother adds
 // the ghosts of every applied correction, cheb_iterate); the patch form of the prolongation computes the correction on
@@ -409,7 +447,7 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
     return mg_apply_f32(mg, rhs, y, y_zero, s);
   std::vector<long long> before(L);
   for (int i = 0; i < L; ++i)
-    before[i] = laplacian_launches(mg->ops[i]);
+    before[i] = level_applies(mg, i);
   // u[L-1] = y, b[L-1] = rhs (:65,68) -- used in place; u[i<L-1] = 0 (:63-64) is
   // folded into the smoothers' x_zero path.
   Range cycle("pmg:vcycle");
@@ -422,9 +460,9 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
     {
       Range rg("pmg:pre_smooth");
       // (several ranks: the iterate leaves the pre-smooth with current ghosts, see `local_correction` below)
-      PMG_TRY(cheb_solve(mg->smoothers[i], mg->ops[i], mg->u[i], bi,
-                         interp_restricts_difference(mg->interps[i - 1]) ? ResidualSplit : ResidualUpdated, zero, s,
-                         &split, local_correction(mg, i))); // :83-87
+      PMG_TRY(level_smooth(mg, i, mg->u[i], bi,
+                           interp_restricts_difference(mg->interps[i - 1]) ? ResidualSplit : ResidualUpdated, zero, s,
+                           &split, local_correction(mg, i))); // :83-87
     }
     Range rg("pmg:restrict");
     if (split) // the residual r - q is formed by the restriction's gather
@@ -456,7 +494,7 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
       }
     }
     else
-      PMG_TRY(cheb_solve(mg->smoothers[0], mg->ops[0], mg->u[0], b0, ResidualNone, zero, s)); // :109
+      PMG_TRY(level_smooth(mg, 0, mg->u[0], b0, ResidualNone, zero, s)); // :109
   }
   for (int i = 0; i < L - 1; ++i)
   {
@@ -474,11 +512,11 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
     Range rg("pmg:post_smooth");
     const double* bi = (i + 1 == L - 1) ? rhs : mg->b[i + 1];
     // with local_correction the ghosts of u are current here: the post-smooth's first application needs no exchange
-    PMG_TRY(cheb_solve(mg->smoothers[i + 1], mg->ops[i + 1], mg->u[i + 1], bi, ResidualNone, false, s, nullptr, false,
-                       local_correction(mg, i + 1))); // :138
+    PMG_TRY(level_smooth(mg, i + 1, mg->u[i + 1], bi, ResidualNone, false, s, nullptr, false,
+                         local_correction(mg, i + 1))); // :138
   }
   for (int i = 0; i < L; ++i)
-    mg->counts[i] = (int)(laplacian_launches(mg->ops[i]) - before[i]);
+    mg->counts[i] = (int)(level_applies(mg, i) - before[i]);
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }
@@ -525,6 +563,13 @@ extern "C" int pmg_chebyshev_solve(pmg_chebyshev sm, pmg_laplacian A, double* x,
 {
   PMG_REQUIRE(sm && A && x && b, "pmg_chebyshev_solve: NULL argument");
   return cheb_solve(sm, A, x, b, ResidualNone, false, S(stream));
+}
+
+extern "C" int pmg_chebyshev_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b,
+                                          pmg_stream stream)
+{
+  PMG_REQUIRE(sm && M && x && b, "pmg_chebyshev_solve_matrix: NULL argument");
+  return cheb_solve_matrix(sm, M, x, b, ResidualNone, false, S(stream));
 }
 
 // -------------------------------------------------------------------- CG --
@@ -693,6 +738,23 @@ extern "C" int pmg_cg_solve(pmg_cg cg, pmg_laplacian A, double* x, const double*
   return cg_iterate(cg, apply, laplacian_diag_inv(A), precond ? &vcycle : nullptr, cg->flexible, x, b, iterations, s);
 }
 
+extern "C" int pmg_cg_solve_matrix(pmg_cg cg, pmg_matrix M, double* x, const double* b, pmg_multigrid precond,
+                                   int* iterations, pmg_stream stream)
+{
+  PMG_REQUIRE(cg && M && x && b, "pmg_cg_solve_matrix: NULL argument");
+  PMG_REQUIRE(matrix_layout(M) == cg->layout, "pmg_cg_solve_matrix: matrix and solver layouts differ");
+  hipStream_t s = S(stream);
+  const ApplyFn apply = [M, s](double* in, double* out) { return matrix_apply(M, in, out, s); };
+  const PrecondFn vcycle = [precond, s](double* z, const double* r) -> int
+  {
+    bool done = false;
+    if (use_graph(precond))
+      PMG_TRY(mg_apply_graph(precond, r, z, true, s, &done));
+    return done ? PMG_OK : mg_apply(precond, r, z, true, s);
+  };
+  return cg_iterate(cg, apply, matrix_diag_inv(M), precond ? &vcycle : nullptr, cg->flexible, x, b, iterations, s);
+}
+
 extern "C" int pmg_cg_set_flexible(pmg_cg cg, int flag)
 {
   PMG_REQUIRE(cg, "pmg_cg_set_flexible: NULL argument");
@@ -760,6 +822,8 @@ extern "C" int pmg_multigrid_create(pmg_multigrid* out, int nlevels, const pmg_l
   mg->u.assign(nlevels, nullptr);
   mg->b.assign(nlevels, nullptr);
   mg->counts.assign(nlevels, 0);
+  mg->mats.assign(nlevels, nullptr);
+  mg->mat_applies.assign(nlevels, 0);
   for (int i = 0; i < nlevels - 1; ++i) // src/pmg.hpp:35-41 (finest level: caller's vectors)
   {
     PMG_TRY(alloc_vec(layouts[i], &mg->u[i]));
@@ -932,6 +996,7 @@ long long capture_config(pmg_multigrid mg)
     // cache as well; this covers an object replaced by another one at the same address only by accident)
     mix((uint64_t)(uintptr_t)mg->ops[i]);
     mix((uint64_t)(uintptr_t)mg->smoothers[i]);
+    mix((uint64_t)(uintptr_t)mg->mats[i]); // the set of assembled levels
     mix((uint64_t)(uintptr_t)l->comm);
     mix((uint64_t)(uintptr_t)l->win);
     if (i + 1 < mg->L)
@@ -1023,9 +1088,32 @@ extern "C" int pmg_multigrid_set_precision(pmg_multigrid mg, int precision)
   PMG_REQUIRE(precision == PMG_PRECISION_FP64 || precision == PMG_PRECISION_FP32,
               "pmg_multigrid_set_precision: unknown precision %d (PMG_PRECISION_FP64 or PMG_PRECISION_FP32)", precision);
   if (precision == PMG_PRECISION_FP32)
+  {
+    for (int i = 0; i < mg->L; ++i)
+      PMG_REQUIRE(!mg->mats[i],
+                  "pmg_multigrid_set_precision: level %d has an assembled matrix and there is no FP32 matrix "
+                  "(pmg_multigrid_set_level_matrix(mg, %d, NULL) removes it)", i, i);
     PMG_TRY(mg_check_f32(mg, "pmg_multigrid_set_precision"));
+  }
   drop_graphs(mg);
   mg->precision = precision;
+  return PMG_OK;
+}
+
+extern "C" int pmg_multigrid_set_level_matrix(pmg_multigrid mg, int level, pmg_matrix M)
+{
+  PMG_REQUIRE(mg, "pmg_multigrid_set_level_matrix: NULL argument");
+  PMG_REQUIRE(level >= 0 && level < mg->L, "pmg_multigrid_set_level_matrix: level %d of %d", level, mg->L);
+  if (M)
+  {
+    PMG_REQUIRE(matrix_layout(M) == mg->layouts[level],
+                "pmg_multigrid_set_level_matrix: the matrix is not on level %d's layout", level);
+    PMG_REQUIRE(mg->precision != PMG_PRECISION_FP32,
+                "pmg_multigrid_set_level_matrix: the cycle runs in FP32 and there is no FP32 matrix "
+                "(pmg_multigrid_set_precision(mg, PMG_PRECISION_FP64) first)");
+  }
+  drop_graphs(mg);
+  mg->mats[level] = M;
   return PMG_OK;
 }
 
@@ -1047,7 +1135,10 @@ extern "C" int pmg_multigrid_apply(pmg_multigrid mg, const double* rhs, double* 
   {
     const int L = mg->L;
     pmg_chebyshev sm = mg->smoothers[L - 1];
-    PMG_TRY(laplacian_apply(mg->ops[L - 1], y, sm->q, s));
+    if (mg->mats[L - 1]) // the level's residual in the level's form
+      PMG_TRY(matrix_apply(mg->mats[L - 1], y, sm->q, s));
+    else
+      PMG_TRY(laplacian_apply(mg->ops[L - 1], y, sm->q, s));
     launch_axpy(mg->layouts[L - 1]->size_local, sm->r, -1.0, sm->q, rhs, s);
     double v;
     PMG_TRY(dot_host(mg->layouts[L - 1], sm->r, sm->r, &v, s));

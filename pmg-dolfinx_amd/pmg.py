@@ -40,6 +40,15 @@ class MultigridPreconditioner:
     def set_interpolators(self, interpolators):  # :50-53
         self._set("pmg_multigrid_set_interpolators", interpolators, "interpolators")
 
+    def set_level_matrix(self, level: int, matrix):
+        """Run every operator application of ``level`` on the assembled :class:`MatrixOperator` ``matrix`` (its
+        product, its inverse diagonal); ``None`` removes it again.  See ``pmg_multigrid_set_level_matrix``."""
+        level = int(level)
+        if level < 0:
+            level += len(self.layouts)
+        call("pmg_multigrid_set_level_matrix", self._handle, level, matrix.handle if matrix is not None else None)
+        self._keep.setdefault("matrices", {})[level] = matrix
+
     def set_coarse_solver(self, solver):  # :46
         """The reference's CoarseSolver concept is "anything with ``solve(x, b)``" (``src/amg.hpp:67``,
         called at ``src/pmg.hpp:106-107``); ``None`` restores the level-0 smoother (``:108-109``).

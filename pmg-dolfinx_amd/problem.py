@@ -11,6 +11,7 @@ from .cg import CGSolver
 from .chebyshev import Chebyshev
 from .interpolate import Interpolator
 from .laplacian import MatFreeLaplacian
+from .matrix import MatrixOperator
 from .mesh import BoxPartition, basix_node_permutation, default_proc_dims, dofmap_in_node_order
 from .pmg import MultigridPreconditioner
 from .vector import Layout, Vector
@@ -24,7 +25,7 @@ def make_layout(lv, group=None, device="cuda", comm=None) -> Layout:
 class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
-                 node_order="ascending", level_hook=None):
+                 node_order="ascending", level_hook=None, assembled_levels=()):
         import torch
 
         self.orders = tuple(int(p) for p in orders)
@@ -101,6 +102,12 @@ class PoissonHierarchy:
         self.mg.set_solvers(self.smoothers)
         self.mg.set_operators(self.operators)
         self.mg.set_interpolators(self.interpolators)
+        # assembled levels (solve<acc::MatrixOperator>, examples/pmg/main.cpp:285): opt-in, level by level
+        self.matrices = {}
+        for i in assembled_levels:
+            i = int(i) % len(self.orders)
+            self.matrices[i] = MatrixOperator(self.operators[i])
+            self.mg.set_level_matrix(i, self.matrices[i])
 
     @property
     def fine_ndofs_owned(self):
