@@ -5,11 +5,14 @@
 // (:267-268).  --mat_comp compares y with the product of the assembled CSR operator
 // (acc::MatrixOperator, as the reference does, :270-288; any degree) and, at degree 1, also
 // with the 7-point stencil the collocated P=1 operator reduces to, evaluated on the host.
+// --kappa-field sets the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z on the operator (not in the
+// reference); the stencil comparison, which is for a constant coefficient, is then left out.
 // Single rank.
 #include "../common/box_mesh.hpp"
 #include "pmg_amd.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +26,7 @@ int main(int argc, char** argv)
 {
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
-  bool mat_comp = false;
+  bool mat_comp = false, kappa_field = false;
   std::size_t batch_size = 0; // :38,46-50: cells whose geometry tensor is held at a time (0 = all, resident)
   for (int i = 1; i < argc; ++i)
   {
@@ -38,12 +41,14 @@ int main(int argc, char** argv)
       nreps = std::atoi(next());
     else if (!std::strcmp(argv[i], "--mat_comp"))
       mat_comp = true;
+    else if (!std::strcmp(argv[i], "--kappa-field"))
+      kappa_field = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
       batch_size = std::strtoull(next(), nullptr, 10);
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells]\n";
+                   "[--batch_size cells] [--kappa-field]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -74,6 +79,20 @@ int main(int argc, char** argv)
                                 bcells, bc.span(), batch_size);
     DeviceVector u(map, 1), y(map, 1);
     u.set(1.0);
+    if (kappa_field)
+    {
+      std::vector<double> kh(V.ndofs);
+      for (std::size_t d = 0; d < kh.size(); ++d)
+        kh[d] = 1.0 + 0.5 * std::sin(2 * M_PI * V.x[3 * d]) * std::cos(2 * M_PI * V.x[3 * d + 1]) + V.x[3 * d + 2];
+      DeviceVector kq(map, 1);
+      kq.copy_from_host(kh);
+      op.set_coefficient_field(kq);
+      // u = 1 lies in the kernel of the operator away from the boundary whatever the coefficient: a vector that
+      // shows the field everywhere
+      for (std::size_t d = 0; d < kh.size(); ++d)
+        kh[d] = std::sin(1.0 + 3 * V.x[3 * d] + 5 * V.x[3 * d + 1] * V.x[3 * d + 2]);
+      u.copy_from_host(kh);
+    }
     op(u, y); // creates the handle (geometry, patches) and warms up
     hip_check(hipDeviceSynchronize(), "sync");
     auto t1 = std::chrono::steady_clock::now();
@@ -114,7 +133,7 @@ int main(int argc, char** argv)
       std::printf("CSR Matvec: %d reps, %.3f us per apply\n", nreps, ms * 1e3 / nreps);
       std::printf("CSR nnz = %zu\n", mat.nnz());
       acc::axpy(ec, -1.0, y, zc);
-      if (degree != 1)
+      if (degree != 1 || kappa_field)
       {
         std::printf("Norm of z = %.15e\n", acc::norm(zc));
         std::printf("Norm of error = %.3e\n", acc::norm(ec));

@@ -80,6 +80,7 @@ struct Options : examples::RankOptions
   std::string output;
   pmg_amd::NodeOrder node_order = pmg_amd::NodeOrder::ascending; // of the dofmaps handed to the library
   bool amg_gather = false; // --amg-setup gathered
+  bool kappa_field = false;    // --kappa-field: the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z
   bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
   std::vector<int> csr_levels; // empty with --csr: every level
 };
@@ -148,9 +149,18 @@ void solve(const Options& o)
     operators[i] = std::make_shared<acc::MatFreeLaplacian<T>>(
         order[i], device_constants, device_dofmaps[i], geom_x, geom_x_dofmap, geometry_dphi_d_span[i],
         Gweights_d_span[i], lcells, bcells, bc_marker_d_span[i], 0, o.node_order); // :270-272
+    const examples::PartitionLevel& lv = V[i]->lv;
+    if (o.kappa_field) // -div(kappa kq(x) grad u): the field at this level's dof coordinates, before the diagonal
+    {
+      std::vector<T> kh(lv.ndofs());
+      for (std::int32_t d = 0; d < lv.ndofs(); ++d)
+        kh[d] = 1.0 + 0.5 * std::sin(2 * M_PI * lv.x[3 * d]) * std::cos(2 * M_PI * lv.x[3 * d + 1]) + lv.x[3 * d + 2];
+      DeviceVector kq(maps[i], 1);
+      hip_check(hipMemcpy(kq.mutable_array().data(), kh.data(), sizeof(T) * kh.size(), hipMemcpyHostToDevice), "H2D");
+      operators[i]->set_coefficient_field(kq);
+    }
     operators[i]->compute_diag_inverse(maps[i]);                  // replaces :274-279 (no CSR)
 
-    const examples::PartitionLevel& lv = V[i]->lv;
     std::vector<T> fh(lv.ndofs());
     const double pi = M_PI, c2 = (4.0 + 9.0 + 16.0) * pi * pi;
     for (std::int32_t d = 0; d < lv.ndofs(); ++d)
@@ -398,6 +408,8 @@ int main(int argc, char** argv)
         o.graph = true;
       else if (!std::strcmp(argv[i], "--fp32-cycle"))
         o.fp32_cycle = true;
+      else if (!std::strcmp(argv[i], "--kappa-field"))
+        o.kappa_field = true;
       else if (!std::strcmp(argv[i], "--csr"))
       {
         o.csr = true;
@@ -464,6 +476,7 @@ int main(int argc, char** argv)
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
                      "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
+                     "           [--kappa-field]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"

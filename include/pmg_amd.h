@@ -267,7 +267,8 @@ int pmg_vec_norm(pmg_layout l, const double* a, int norm_type, double* result, p
  * Arguments mirror the reference constructor (:289-297); all arrays are device
  * pointers except the two cell lists, which are host arrays like the
  * reference's std::vector<int>:
- *   kappa          [ncells]               DG-0 coefficient per cell
+ *   kappa          [ncells]               DG-0 coefficient per cell (times the nodal field of
+ *                  pmg_laplacian_set_coefficient_field, when one is set -- "variable coefficient" below)
  *   dofmap         [ncells * (degree+1)^3] local dof of (cell, t), t = a*nd^2+b*nd+c with a, b, c the
  *                  node numbers along x, y, z by ASCENDING coordinate (a basix / dolfinx dofmap numbers
  *                  the 1-D nodes endpoints first: use pmg_laplacian_create_ordered for it)
@@ -334,12 +335,41 @@ int pmg_laplacian_set_diag_inverse(pmg_laplacian op, const double* diag_inv, pmg
 int pmg_laplacian_compute_diag_inverse(pmg_laplacian op, pmg_stream stream);
 /* The precomputed geometry tensor in the reference's layout [ncells][nq][6]
  * (:99-111), for parity tests.  `G_out` is a device array; q = ja*nd^2 + jb*nd + jc in the node order
- * the operator was created with (ascending unless pmg_laplacian_create_ordered said otherwise). */
+ * the operator was created with (ascending unless pmg_laplacian_create_ordered said otherwise).  It is the tensor
+ * as the kernels read it: with a coefficient field set, G_q carries the field's value at its point. */
 int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream stream);
+/* Variable coefficient: -div(kappa(x) grad u) with kappa a function of the operator's own space (not in the
+ * reference, whose coefficient is one value per cell).  With GLL collocation the quadrature points are the nodes, so
+ * such a coefficient is one value per (cell, point), kq[dof(cell, q)], and it is folded into the stored tensor where
+ * the tensor is built: every form of the apply streams the same 48 bytes per point as without a field, and the
+ * diagonal, the assembled matrix (pmg_matrix_*) and the AMG set-up read that one tensor.  The effective coefficient
+ * is kappa[cell] * kq[dof(cell, q)]: the per-cell array keeps its meaning and is still read in every application.
+ *
+ * `kq` is a device array of size_local owned nodal values in the operator's dof numbering (entries beyond size_local
+ * are ignored); the library copies them and fills the ghost entries of its copy with the layout's own forward
+ * scatter, so a caller on several ranks need not have scattered the array -- there the call is collective -- and
+ * may free it on return.  kq = NULL removes the field and restores the tensor without one bit for bit.  Every owned
+ * entry must be finite and greater than 0 (one small reduction, summed over the ranks); otherwise PMG_ERR_INVALID
+ * and nothing has changed.  The call rebuilds what depends on the tensor: the resident FP64 tensor (in batched-
+ * geometry mode every application folds the field in as it recomputes its batch), the float tensor if it has been
+ * built, and the inverse diagonal if it came from pmg_laplacian_compute_diag_inverse (a diagonal installed with
+ * pmg_laplacian_set_diag_inverse is left alone).  An assembled matrix follows with pmg_matrix_update_values; a
+ * smoother's eigenvalue bound and an AMG hierarchy are the caller's to renew.  All buffers are rebuilt in place and
+ * keep their addresses, so a captured V-cycle graph over the resident tensor stays valid (an FP32 cycle re-captures
+ * because the diagonal changed; in batched-geometry mode the captured geometry launches carry the field's address,
+ * and setting the first field or removing it re-captures).  Like the other set-up calls it allocates and
+ * synchronises the stream: not inside a stream capture (refused).  The affine geometry mode streams one tensor per
+ * cell and cannot carry a field: pmg_laplacian_set_geometry_mode(op, 1) is refused while a field is set, and
+ * setting a field is refused in affine mode (PMG_ERR_INVALID both ways).
+ * pmg_laplacian_has_coefficient_field: 1 / 0. */
+int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const double* kq, pmg_stream stream);
+int pmg_laplacian_has_coefficient_field(pmg_laplacian op);
 /* GLL-collocated load vector b_i = sum_cells kappa * w_q * detJ_q * f_i at q = i
  * (what dolfinx assemble_vector does for L = inner(f, v)*dx with the GLL rule,
  * examples/pmg/poisson.py:40; examples/pmg/main.cpp:289-295), then set_bc:
- * b[bc] = 0.  `f` holds the nodal values of the source term. */
+ * b[bc] = 0.  `f` holds the nodal values of the source term.  The scaling is by the per-cell kappa only (the
+ * reference's manufactured load), also when a coefficient field is set: a caller with a field passes the nodal
+ * values of its own f. */
 int pmg_laplacian_assemble_rhs(pmg_laplacian op, const double* f, double* b, pmg_stream stream);
 int pmg_laplacian_degree(pmg_laplacian op);
 /* Geometry mode of the apply.  0 (default): the reference's data structure, the
@@ -347,7 +377,8 @@ int pmg_laplacian_degree(pmg_laplacian op);
  * 1: affine cells -- when every cell is a parallelepiped, G_q = w_q * Gc with one
  * constant tensor per cell, so the kernel reads 48 bytes per CELL instead (same
  * result to rounding; not in the reference; SURVEY.md 8d calls this byte model
- * separate from storedG).  Fails if the mesh has a non-affine cell. */
+ * separate from storedG).  Fails if the mesh has a non-affine cell, or while a
+ * coefficient field is set (pmg_laplacian_set_coefficient_field). */
 int pmg_laplacian_is_affine(pmg_laplacian op);
 int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode);
 /* Geometry batching (src/laplacian.hpp:383-396; examples/mat_free/main.cpp:34-50 --batch_size):

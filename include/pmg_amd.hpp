@@ -648,8 +648,22 @@ public:
   {
     check(pmg_laplacian_compute_diag_inverse(handle(map), nullptr));
   }
+  /// Variable coefficient (pmg_laplacian_set_coefficient_field; not in the reference): the owned entries of kq are
+  /// positive nodal values, the operator becomes -div(kappa[cell] * kq(x) grad u).  The tensor, its float form and a
+  /// computed inverse diagonal follow; an assembled MatrixOperator follows with update_values().
+  template <typename Vector>
+  void set_coefficient_field(const Vector& kq)
+  {
+    check(pmg_laplacian_set_coefficient_field(handle(kq.map()), kq.array().data(), nullptr));
+  }
+  void clear_coefficient_field()
+  {
+    if (_op)
+      check(pmg_laplacian_set_coefficient_field(_op, nullptr, nullptr));
+  }
+  bool has_coefficient_field() const { return _op && pmg_laplacian_has_coefficient_field(_op) == 1; }
   /// b = GLL-collocated load vector of the nodal source f, BC rows zeroed
-  /// (assemble_vector + set_bc, examples/pmg/main.cpp:289-300).
+  /// (assemble_vector + set_bc, examples/pmg/main.cpp:289-300).  The scaling is by the per-cell coefficient only.
   template <typename Vector>
   void assemble_rhs(const Vector& f, Vector& b)
   {

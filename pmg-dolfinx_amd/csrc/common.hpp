@@ -264,6 +264,7 @@ int cheb_iterate_f32(const ChebWork32& w, pmg_laplacian A, const float* dinv, in
                      float* x, const float* b, int need_r, bool x_zero, hipStream_t s, bool* split);
 int laplacian_f32_supported(pmg_laplacian op, const char* who); // PMG_OK, or the refusal (ghosts, batched geometry)
 int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s);      // float tensor and table on first use (allocates)
+int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s);      // recompute the float tensor in place (if it exists)
 int laplacian_f32_diag(pmg_laplacian op, const float** d, hipStream_t s, bool* changed);
 long long laplacian_diag_version(pmg_laplacian op);
 int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s);

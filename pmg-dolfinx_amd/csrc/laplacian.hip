@@ -205,12 +205,15 @@ __device__ __forceinline__ size_t gpos(int nd, int K, long long slot, int q, int
 }
 
 // G for the patch slots [slot0, slot0 + nslots) and every q, paired layout (absolute positions:
-// in batch mode G points `slot0` slots before its buffer)
+// in batch mode G points `slot0` slots before its buffer).  kfield (optional): the nodal coefficient, one value per
+// local dof; G_q is scaled by its value at the point's own dof (GLL collocation: the points are the nodes).  Threads
+// of a wavefront walk q, so the dofmap read is contiguous; the kfield gather follows the dofmap like the apply's x.
 __global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K,
                                 const int32_t* __restrict__ pcell,
                                 const double* __restrict__ xgeom,
                                 const int32_t* __restrict__ geom_dofmap,
                                 const double* __restrict__ dphi, const double* __restrict__ w,
+                                const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
                                 double2* __restrict__ G)
 {
   const int nq = nd * nd * nd;
@@ -227,6 +230,8 @@ __global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K
     double K[3][3], detJ;
     jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
     double s = w[q] / detJ;
+    if (kfield)
+      s *= kfield[dofmap[(size_t)c * nq + q]];
     g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s; // :99-111
     g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
     g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
@@ -2067,7 +2072,8 @@ const double2* batch_geometry(pmg_laplacian op, int first, int count, hipStream_
   if (n > 0)
     geometry_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)first * op->K, nslots, op->nd, op->K,
                                                               op->pcell, op->xgeom, op->geom_dofmap,
-                                                              op->dphi_geom, op->gweights, base);
+                                                              op->dphi_geom, op->gweights, op->kfield, op->dofmap,
+                                                              base);
   return base;
 }
 
@@ -2360,8 +2366,11 @@ long long laplacian_capture_state(pmg_laplacian op)
 {
   if (op->profiling)
     return -1;
+  // (batched geometry: the captured geometry launches carry the field's address; the resident tensor is rebuilt in
+  // place by pmg_laplacian_set_coefficient_field, so a graph over it stays valid)
+  const long long field = op->batch_patches > 0 ? (op->kfield_epoch & 0x3fff) << 44 : 0;
   return ((long long)op->geometry_mode << 40) ^ ((long long)op->batch_patches << 8) ^ (long long)(op->have_diag ? 1 : 0)
-         ^ (long long)(op->chain_on ? 2 : 0);
+         ^ (long long)(op->chain_on ? 2 : 0) ^ field;
 }
 
 PatchView laplacian_patches(pmg_laplacian op)
@@ -2749,6 +2758,7 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->qperm);
   (void)hipFree(op->D);
   (void)hipFree(op->Gaff);
+  (void)hipFree(op->kfield);
   (void)hipFree(op->W1);
   (void)hipFree(op->dphi_geom);
   (void)hipFree(op->gweights);
@@ -2802,6 +2812,9 @@ extern "C" int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode)
   if (mode == 1)
   {
     PMG_REQUIRE(op->all_affine, "pmg_laplacian_set_geometry_mode: the mesh has non-affine cells");
+    PMG_REQUIRE(!op->kfield, "pmg_laplacian_set_geometry_mode: the affine mode streams one tensor per cell and cannot "
+                             "carry the coefficient field (remove it with pmg_laplacian_set_coefficient_field(op, "
+                             "NULL, stream) first)");
   }
   op->geometry_mode = mode;
   return PMG_OK;
@@ -2831,6 +2844,7 @@ extern "C" int pmg_laplacian_set_diag_inverse(pmg_laplacian op, const double* di
   PMG_HIP(hipMemcpyAsync(op->diag_inv, diag_inv, sizeof(double) * op->layout->total(),
                          hipMemcpyDeviceToDevice, S(stream)));
   op->have_diag = true;
+  op->diag_computed = false;
   op->diag_version++;
   return PMG_OK;
 }
@@ -2851,7 +2865,85 @@ extern "C" int pmg_laplacian_compute_diag_inverse(pmg_laplacian op, pmg_stream s
     diag_invert_kernel<<<(total + 255) / 256, 256, 0, s>>>(total, op->bc, op->diag_inv);
   PMG_HIP(hipGetLastError());
   op->have_diag = true;
+  op->diag_computed = true;
   op->diag_version++;
+  return PMG_OK;
+}
+
+// number of entries of kq[0, n) that are not finite and positive, added to *bad (zeroed by the caller)
+__global__ void coefficient_check_kernel(int n, const double* __restrict__ kq, double* __restrict__ bad)
+{
+  int mine = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+  {
+    const double v = kq[i];
+    mine += !(v > 0.0 && v <= 1.79769313486231570e308); // NaN fails the first comparison, +inf the second
+  }
+  if (mine)
+    atomicAdd(bad, (double)mine);
+}
+
+extern "C" int pmg_laplacian_has_coefficient_field(pmg_laplacian op) { return op ? (op->kfield ? 1 : 0) : -1; }
+
+extern "C" int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const double* kq, pmg_stream stream)
+{
+  PMG_REQUIRE(op, "pmg_laplacian_set_coefficient_field: NULL argument");
+  hipStream_t s = S(stream);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  PMG_HIP(hipStreamIsCapturing(s, &cap));
+  PMG_REQUIRE(cap == hipStreamCaptureStatusNone,
+              "pmg_laplacian_set_coefficient_field: not inside a stream capture (it allocates and synchronises)");
+  pmg_layout l = op->layout;
+  double* released = nullptr;
+  if (!kq)
+  {
+    if (!op->kfield)
+      return PMG_OK;
+    released = op->kfield;
+    op->kfield = nullptr;
+    op->kfield_epoch++;
+  }
+  else
+  {
+    PMG_REQUIRE(op->geometry_mode == 0,
+                "pmg_laplacian_set_coefficient_field: the affine mode streams one tensor per cell and cannot carry a "
+                "field (return to the stored tensor with pmg_laplacian_set_geometry_mode(op, 0) first)");
+    // every owned entry finite and > 0, on every rank (the count is summed over the ranks: all of them refuse, or
+    // none)
+    double* bad = red_slot(l, 0);
+    PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
+    if (l->size_local > 0)
+      coefficient_check_kernel<<<std::min((l->size_local + 255) / 256, 1024), 256, 0, s>>>(l->size_local, kq, bad);
+    PMG_HIP(hipGetLastError());
+    PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
+    double nbad = 0.0;
+    PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
+    if (nbad != 0.0)
+      return fail(PMG_ERR_INVALID,
+                  "pmg_laplacian_set_coefficient_field: %lld entries of the field are not finite and greater than 0",
+                  (long long)nbad);
+    if (!op->kfield)
+    {
+      PMG_HIP(hipMalloc(&op->kfield, sizeof(double) * (l->total() ? l->total() : 1)));
+      op->kfield_epoch++;
+    }
+    PMG_HIP(hipMemcpyAsync(op->kfield, kq, sizeof(double) * l->size_local, hipMemcpyDeviceToDevice, s));
+    if (l->num_ghosts > 0)
+    {
+      PMG_HIP(hipMemsetAsync(op->kfield + l->size_local, 0, sizeof(double) * l->num_ghosts, s));
+      PMG_TRY(scatter_fwd_whole(l, op->kfield, s));
+    }
+  }
+  // what depends on G, each in its own buffer (a captured graph of this operator's launches stays valid)
+  if (op->batch_patches == 0 && op->npatch > 0)
+    batch_geometry(op, 0, op->npatch, s);
+  PMG_HIP(hipGetLastError());
+  PMG_TRY(laplacian_f32_refresh(op, s));
+  if (op->have_diag && op->diag_computed)
+    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
+  PMG_HIP(hipStreamSynchronize(s)); // the caller may free kq on return
+  if (released)
+    PMG_HIP(hipFree(released));
   return PMG_OK;
 }
 

@@ -23,6 +23,11 @@ struct pmg_laplacian_s
   int32_t* qperm = nullptr;      // [N] device: caller's cell-local number -> ascending; nullptr = identity
   // owned
   double2* G = nullptr;        // [nslots][3][N]
+  // nodal coefficient (pmg_laplacian_set_coefficient_field): folded into G, and into the float tensor, where they are
+  // built (geometry_kernel); nullptr = none
+  double* kfield = nullptr;    // [size_local + num_ghosts], ghosts filled by the layout's forward scatter
+  long long kfield_epoch = 0;  // bumped when kfield is allocated or freed (laplacian_capture_state, batch mode)
+  bool diag_computed = false;  // diag_inv came from pmg_laplacian_compute_diag_inverse (it follows a change of field)
   double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell
   double* W1 = nullptr;        // [nd] 1-D GLL weights
   bool all_affine = false;     // every listed cell is a parallelepiped
@@ -74,7 +79,7 @@ struct pmg_laplacian_s
   size_t prof_used = 0;
   long long prof_launches = 0;
   // single-precision form of the operator (laplacian_f32.hip; built on first use, freed with the handle)
-  float2* G32 = nullptr;          // [nslots][layer c][3][nd*nd]: G (without kappa), rounded once (the default layout of G)
+  float2* G32 = nullptr;          // [nslots][layer c][3][nd*nd]: G (without kappa, with the coefficient field), rounded once (the default layout of G)
   float* D32 = nullptr;           // [nd*nd]
   float* diag32 = nullptr;        // [size_local + num_ghosts] float copy of diag_inv
   long long diag_version = 0;     // bumped whenever diag_inv changes; diag32 is current while the two agree

@@ -79,10 +79,12 @@ __device__ __forceinline__ float2 gload32(const float2* p)
     return *p;
 }
 
-// G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]
+// G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]; kfield (optional) is
+// the nodal coefficient, folded in as in geometry_kernel, in double, before the one rounding
 __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __restrict__ pcell,
                                     const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
                                     const double* __restrict__ dphi, const double* __restrict__ w,
+                                    const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
                                     float2* __restrict__ G)
 {
   const int nsq = nd * nd, nq = nsq * nd;
@@ -97,7 +99,9 @@ __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __r
   {
     double K[3][3], detJ;
     jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
-    const double s = w[q] / detJ;
+    double s = w[q] / detJ;
+    if (kfield)
+      s *= kfield[dofmap[(size_t)c * nq + q]];
     g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
     g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
     g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
@@ -380,6 +384,20 @@ int laplacian_f32_supported(pmg_laplacian op, const char* who)
   return PMG_OK;
 }
 
+// The float tensor, (re)computed in place from the geometry and the coefficient field (if one is set)
+int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s)
+{
+  if (!op->G32)
+    return PMG_OK;
+  const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
+  if (n > 0)
+    geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
+                                                                    op->geom_dofmap, op->dphi_geom, op->gweights,
+                                                                    op->kfield, op->dofmap, op->G32);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
 // The float tensor and 1-D table, built on the first FP32 use (outside any stream capture: it allocates)
 int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
 {
@@ -389,12 +407,7 @@ int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
   PMG_HIP(hipMalloc(&op->G32, sizeof(float2) * 3 * (size_t)(n > 0 ? n : 1)));
   PMG_HIP(hipMalloc(&op->D32, sizeof(float) * op->nd * op->nd));
   to_float_kernel<<<1, 256, 0, s>>>(op->nd * op->nd, op->D, op->D32);
-  if (n > 0)
-    geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
-                                                                    op->geom_dofmap, op->dphi_geom, op->gweights,
-                                                                    op->G32);
-  PMG_HIP(hipGetLastError());
-  return PMG_OK;
+  return laplacian_f32_refresh(op, s);
 }
 
 // float copy of the operator's diagonal inverse, refreshed when the diagonal has changed since; `*changed` (optional)

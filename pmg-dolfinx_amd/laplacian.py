@@ -146,8 +146,28 @@ class MatFreeLaplacian:
         """Matrix-free replacement of the CSR detour of ``examples/pmg/main.cpp:274-279``."""
         call("pmg_laplacian_compute_diag_inverse", self._handle, current_stream())
 
+    def set_coefficient_field(self, v):
+        """Nodal coefficient kq (``pmg_laplacian_set_coefficient_field``): the operator becomes
+        -div(kappa[cell] * kq(x) grad u).  ``v`` is a ``Vector`` of the operator's layout whose owned entries are
+        the values at the dofs (all finite and > 0; its ghost entries are not read, the library scatters its own
+        copy), or ``None`` to remove the field.  The tensor, its float form and a computed inverse diagonal are
+        rebuilt; not inside a stream capture."""
+        if v is None:
+            call("pmg_laplacian_set_coefficient_field", self._handle, None, current_stream())
+            return
+        if not isinstance(v, Vector):
+            raise TypeError("set_coefficient_field takes a Vector of the operator's layout, or None")
+        n = self.layout.size_local + self.layout.num_ghosts
+        if v.data.numel() != n:
+            raise ValueError(f"the field has {v.data.numel()} entries, the operator's layout {n}")
+        call("pmg_laplacian_set_coefficient_field", self._handle, ptr(v.data), current_stream())
+
+    def has_coefficient_field(self) -> bool:
+        return bool(call("pmg_laplacian_has_coefficient_field", self._handle))
+
     def geometry(self):
-        """G in the reference layout [ncells, nq, 6] (device tensor)."""
+        """G in the reference layout [ncells, nq, 6] (device tensor), as the kernels read it (with the
+        coefficient field, if one is set)."""
         import torch
 
         N = (self.degree + 1) ** 3

@@ -25,7 +25,11 @@ def make_layout(lv, group=None, device="cuda", comm=None) -> Layout:
 class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
-                 node_order="ascending", level_hook=None, assembled_levels=()):
+                 node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None):
+        """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
+        variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
+        operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
+        load vectors keep the per-cell ``kappa`` only (``pmg_laplacian_assemble_rhs``)."""
         import torch
 
         self.orders = tuple(int(p) for p in orders)
@@ -55,6 +59,12 @@ class PoissonHierarchy:
                 raise ValueError("PoissonHierarchy: node_order is 'ascending' or 'basix'")
             op = MatFreeLaplacian(P, self.kappa, dofmap, self.xgeom, self.geom_dofmap, lv.lcells, lv.bcells,
                                   lv.bc_marker, layout, node_order=node_order)  # :270-272
+            if kappa_field is not None:
+                kq = Vector(layout)
+                kq.data.copy_(torch.from_numpy(np.ascontiguousarray(
+                    kappa_field(part.dof_coordinates(P)), dtype=np.float64)))
+                op.set_coefficient_field(kq)
+                del kq
             op.compute_diag_inverse()  # replaces :274-279
             self.levels.append(lv)
             self.layouts.append(layout)
