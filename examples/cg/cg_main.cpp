@@ -9,6 +9,9 @@
 //      x = 1, x[bc] = 1.3 (:275-280), residual norm printed per iteration (src/chebyshev.hpp:62-89).
 // What stands above replaces dolfinx (mesh, function space, index map); the inverse diagonal comes
 // from the matrix-free kernel instead of the assembled CSR operator of :224-229.
+//   --lift             the right-hand side from the ONE operator: assemble_rhs, apply_lifting, set_bc
+//                      (pmg_laplacian_apply_lifting / _set_bc) -- no second operator with an empty marker, no
+//                      full-volume apply for a product whose input lives on the boundary shell
 //   --ranks px,py,pz   one process per GPU and brick on the library's RCCL communicator
 //                      (examples/pmg/run_ranks.sh launches the processes)
 #define PMG_AMD_DOLFINX_NAMESPACE
@@ -40,6 +43,7 @@ namespace
 struct Options : examples::RankOptions
 {
   int n = 16, order = 3, cg_its = 20, cheb_its = 30;
+  bool lift = false; // --lift: b through apply_lifting / set_bc on `op` instead of a second, unconstrained operator
   bool csr = false; // --csr: the eigenvalue estimate on the assembled operator (examples/cg/main.cpp:224-229)
 };
 
@@ -81,8 +85,11 @@ void solve(const Options& o)
   // Create operators (:221-229); the second one carries no Dirichlet rows and serves the lifting
   acc::MatFreeLaplacian<T> op(order, constants_d.span(), dofmap_d.span(), xgeom_d.span(), xdofmap_d.span(), {}, {},
                               lcells, bcells, bc_marker_d.span());
-  acc::MatFreeLaplacian<T> op_free(order, constants_d.span(), dofmap_d.span(), xgeom_d.span(), xdofmap_d.span(), {},
-                                   {}, lcells, bcells, no_marker_d.span());
+  std::unique_ptr<acc::MatFreeLaplacian<T>> op_free;
+  if (!o.lift)
+    op_free = std::make_unique<acc::MatFreeLaplacian<T>>(order, constants_d.span(), dofmap_d.span(), xgeom_d.span(),
+                                                         xdofmap_d.span(), std::span<const T>{}, std::span<const T>{},
+                                                         lcells, bcells, no_marker_d.span());
   op.compute_diag_inverse(map);
 
   // Assemble RHS (:231-236)
@@ -98,10 +105,17 @@ void solve(const Options& o)
     v /= kappa;
   upload(f, fh);
   upload(g, gh);
-  op_free.assemble_rhs(f, b);  // L = inner(f, v) * dx with the GLL rule
-  op_free(g, Ag);              // apply_lifting
-  acc::axpy(b, -1.0, Ag, b);   // b -= A g
+  if (o.lift)
   {
+    op.assemble_rhs(f, b);  // L = inner(f, v) * dx with the GLL rule (marked rows come out 0; set_bc overwrites them)
+    op.apply_lifting(g, b); // b -= A g on the unmarked rows, from the cells that hold a marked dof
+    op.set_bc(g, b);        // b[bc] = g
+  }
+  else
+  {
+    op_free->assemble_rhs(f, b); // L = inner(f, v) * dx with the GLL rule
+    (*op_free)(g, Ag);           // apply_lifting
+    acc::axpy(b, -1.0, Ag, b);   // b -= A g
     std::vector<T> bh = b.data_copy(); // set_bc
     for (std::int32_t d = 0; d < lv.ndofs(); ++d)
       if (lv.bc_marker[d])
@@ -215,6 +229,8 @@ int main(int argc, char** argv)
         o.cg_its = std::atoi(next());
       else if (!std::strcmp(argv[i], "--csr"))
         o.csr = true;
+      else if (!std::strcmp(argv[i], "--lift"))
+        o.lift = true;
       else if (!std::strcmp(argv[i], "--cheb-its"))
         o.cheb_its = std::atoi(next());
       else if (!std::strcmp(argv[i], "--ranks"))
@@ -231,7 +247,7 @@ int main(int argc, char** argv)
         o.id_file = next();
       else
       {
-        std::cout << "usage: cg [--n cells_per_direction | --ndofs N_per_rank] [--degree P] [--cg-its N] [--cheb-its N] [--csr]\n"
+        std::cout << "usage: cg [--n cells_per_direction | --ndofs N_per_rank] [--degree P] [--cg-its N] [--cheb-its N] [--csr] [--lift]\n"
                      "          [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows] [--comm rccl|windows]\n";
         return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
       }

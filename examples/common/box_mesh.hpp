@@ -4,6 +4,7 @@
 // and vertices are numbered lexicographically (x slowest); the dofs of a cell are
 // ordered t = a*nd^2 + b*nd + c like the kernel's thread index (src/laplacian.hpp:173).
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -91,6 +92,60 @@ struct FunctionSpace
         }
   }
 };
+
+/// The nd * nd ascending cell-local node numbers t = a*nd^2 + b*nd + c of the face `local_facet` = 2 * axis + side
+/// (side 0: xi_axis = 0, side 1: xi_axis = 1), in the order of the facet points of pmg_laplacian_assemble_neumann:
+/// s = i*nd + j over the two remaining axes in increasing axis order, by ascending coordinate.
+inline std::vector<std::int32_t> facet_nodes(int P, int local_facet)
+{
+  const int nd = P + 1, axis = local_facet / 2, fixed = (local_facet % 2) ? P : 0;
+  std::vector<std::int32_t> t((std::size_t)nd * nd);
+  for (int i = 0; i < nd; ++i)
+    for (int j = 0; j < nd; ++j)
+      t[(std::size_t)i * nd + j] = axis == 0   ? (fixed * nd + i) * nd + j
+                                   : axis == 1 ? (i * nd + fixed) * nd + j
+                                               : (i * nd + j) * nd + fixed;
+  return t;
+}
+
+/// Exterior faces of a list of cells given by their global cell coordinates in an n[0] x n[1] x n[2] grid:
+/// (cells, local facets = 2 * axis + side), ordered by cell, then facet.
+struct ExteriorFacets
+{
+  std::vector<std::int32_t> cells;
+  std::vector<std::int8_t> local_facets;
+};
+template <typename Coords>
+inline ExteriorFacets exterior_facets(const Coords& cell_coords, const int (&n)[3])
+{
+  ExteriorFacets out;
+  std::int32_t c = 0;
+  for (const auto& cc : cell_coords)
+  {
+    for (int axis = 0; axis < 3; ++axis)
+      for (int side = 0; side < 2; ++side)
+        if (cc[axis] == (side ? n[axis] - 1 : 0))
+        {
+          out.cells.push_back(c);
+          out.local_facets.push_back((std::int8_t)(2 * axis + side));
+        }
+    ++c;
+  }
+  return out;
+}
+/// ... of the whole single-rank mesh (cells lexicographic, x slowest)
+inline ExteriorFacets exterior_facets(const BoxMesh& mesh)
+{
+  const int n = mesh.n;
+  std::vector<std::array<int, 3>> cells;
+  cells.reserve((std::size_t)n * n * n);
+  for (int cx = 0; cx < n; ++cx)
+    for (int cy = 0; cy < n; ++cy)
+      for (int cz = 0; cz < n; ++cz)
+        cells.push_back({cx, cy, cz});
+  const int nn[3] = {n, n, n};
+  return exterior_facets(cells, nn);
+}
 
 /// Cells per direction so that the degree-P space has about `ndofs` dofs
 /// (the drivers' --ndofs, examples/pmg/main.cpp:425-440).

@@ -14,6 +14,8 @@
 //   ghosts grouped by owner rank (ascending), lexicographic inside each owner's box;
 //   cells: owned cells first (lexicographic), then ghost cells.
 #pragma once
+#include "box_mesh.hpp"
+
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -54,6 +56,13 @@ public:
   std::vector<std::array<int, 3>> cell_coords; // global cell coordinates of the local cells
   std::vector<double> xgeom;                    // [npoints][3]
   std::vector<std::int32_t> geom_dofmap;        // [ncells][8], k = i*4 + j*2 + l
+
+  /// exterior faces of every local cell, ghost cells included (box_mesh.hpp; pmg_laplacian_assemble_neumann)
+  ExteriorFacets exterior_facets() const
+  {
+    const int nn[3] = {n[0], n[1], n[2]};
+    return examples::exterior_facets(cell_coords, nn);
+  }
 
   BrickPartition(int n_, std::array<int, 3> dims_, int rank_) : n{n_, n_, n_}, dims(dims_), rank(rank_)
   {

@@ -7,6 +7,9 @@
 // with the 7-point stencil the collocated P=1 operator reduces to, evaluated on the host.
 // --kappa-field sets the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z on the operator (not in the
 // reference); the stencil comparison, which is for a constant coefficient, is then left out.
+// --lift restates the right-hand side the reference's driver has commented out (:252-255): u = the assembled load of
+// f = 0 (:133,143: the interpolation of f is commented out as well), lifted with the boundary value 1.3 (:165) and
+// set_bc -- pmg_laplacian_assemble_rhs, _apply_lifting, _set_bc on the one operator -- instead of u = 1.
 // Single rank.
 #include "../common/box_mesh.hpp"
 #include "pmg_amd.hpp"
@@ -26,7 +29,7 @@ int main(int argc, char** argv)
 {
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
-  bool mat_comp = false, kappa_field = false;
+  bool mat_comp = false, kappa_field = false, lift = false;
   std::size_t batch_size = 0; // :38,46-50: cells whose geometry tensor is held at a time (0 = all, resident)
   for (int i = 1; i < argc; ++i)
   {
@@ -43,12 +46,14 @@ int main(int argc, char** argv)
       mat_comp = true;
     else if (!std::strcmp(argv[i], "--kappa-field"))
       kappa_field = true;
+    else if (!std::strcmp(argv[i], "--lift"))
+      lift = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
       batch_size = std::strtoull(next(), nullptr, 10);
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field]\n";
+                   "[--batch_size cells] [--kappa-field] [--lift]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -92,6 +97,17 @@ int main(int argc, char** argv)
       for (std::size_t d = 0; d < kh.size(); ++d)
         kh[d] = std::sin(1.0 + 3 * V.x[3 * d] + 5 * V.x[3 * d + 1] * V.x[3 * d + 2]);
       u.copy_from_host(kh);
+    }
+    if (lift)
+    {
+      DeviceVector f(map, 1), g(map, 1);
+      f.set(0.0);
+      g.set(1.3); // read on the marked dofs only
+      op.assemble_rhs(f, u);   // fem::assemble_vector(b, *L)
+      op.apply_lifting(g, u);  // fem::apply_lifting(b, {a}, {{bc}}, {}, 1)
+      op.set_bc(g, u);         // fem::set_bc(b, {bc})
+      std::printf("Lifted right-hand side: %d of %d cells hold a Dirichlet dof\n",
+                  pmg_laplacian_lift_cell_count(op.handle(map)), (int)mesh.ncells());
     }
     op(u, y); // creates the handle (geometry, patches) and warms up
     hip_check(hipDeviceSynchronize(), "sync");

@@ -371,6 +371,46 @@ int pmg_laplacian_has_coefficient_field(pmg_laplacian op);
  * reference's manufactured load), also when a coefficient field is set: a caller with a field passes the nodal
  * values of its own f. */
 int pmg_laplacian_assemble_rhs(pmg_laplacian op, const double* f, double* b, pmg_stream stream);
+/* ---- boundary data: Dirichlet lifting, set_bc and the Neumann load (not in the reference's library: its drivers
+ * call dolfinx's fem::apply_lifting and fem::set_bc, examples/cg/main.cpp:231-236, examples/mat_free/main.cpp:253-255)
+ * The right-hand side of a problem with non-zero Dirichlet values and prescribed fluxes, computed on the device from
+ * the operator the caller already has, at O(surface) cost: no second operator with an empty marker, no full-volume
+ * apply.  `g`, `x0` and `b` are device arrays of size_local + num_ghosts entries in the operator's dof numbering.
+ * Unmarked entries of g and x0 are never read (they may hold anything, a NaN included).  Only the owned rows of b are
+ * meaningful afterwards, as with pmg_laplacian_assemble_rhs.  None of the calls touches the stored tensor, the patch
+ * plan or a launch of the apply, and all of them work in every geometry mode, with batched geometry, with the chain
+ * form and with a coefficient field (the lifting recomputes the geometry of its cells from the mesh).
+ *
+ * pmg_laplacian_apply_lifting -- dolfinx fem::apply_lifting(b, {a}, {{bc}}, {x0}, alpha) for this operator:
+ *     b[i] -= alpha * sum_{j marked} A_ij * (g[j] - x0[j])     for every owned, unmarked row i,
+ *   A the UNCONSTRAINED operator (no row / column treatment) with the current coefficient kappa[cell] * kq[dof(cell,q)].
+ *   x0 may be NULL (= 0).  Marked rows of b are not touched.  The ghosts of g are refreshed with the layout's forward
+ *   scatter (a side effect, as pmg_laplacian_apply has on `in`; collective on several ranks); the ghosts of x0 are the
+ *   caller's to have scattered.  The first call of an operator reads the dofmap and the marker back once and keeps the
+ *   list of cells that hold a marked dof (pmg_laplacian_lift_cell_count; -1 before): that call is refused inside a
+ *   stream capture.  One workgroup per listed cell sums through atomics: two calls agree to rounding, not bit for bit.
+ * pmg_laplacian_set_bc -- dolfinx fem::set_bc(b, {bc}, x0, alpha): b[i] = alpha * (g[i] - x0[i]) on every marked
+ *   i < size_local; x0 may be NULL.  Also the way to put g into an initial guess (alpha = 1, x0 = NULL).
+ * pmg_laplacian_assemble_neumann -- the GLL-collocated int_Gamma h v ds over the listed facets:
+ *     b[i] += sum over facets F and face points s of F with dof(F, s) = i:  w1[i1] * w1[i2] * |dS| * h[F][s]
+ *   on unmarked owned rows.  facet_cells / facet_local are HOST arrays; a cell may come from either cell list, ghost
+ *   cells included (each rank lists the exterior facets of all cells it holds, so owned rows are complete without a
+ *   reverse scatter).  Local facet number = 2 * axis + side: axis 0, 1, 2 are the cell's reference axes in the tensor
+ *   order of geom_dofmap (k = i*4 + j*2 + l) and of the ascending node number t = a*nd^2 + b*nd + c; side 0 is the face
+ *   xi_axis = 0, side 1 the face xi_axis = 1 -- also for an operator created in another cell-local node order.  `h` is
+ *   a device array [nfacets][nd*nd], s = i1*nd + i2 over the two remaining axes in increasing axis order, by ascending
+ *   coordinate: one value per facet point, not per dof, because a dof on an edge between two Neumann faces has two
+ *   normals.  |dS| is the Euclidean norm of row `axis` of adj(J) at the point (the outward area vector is +- that row;
+ *   the sign belongs to the caller's h = flux . n).  nfacets == 0 is a no-op.  It uploads the lists and waits for the
+ *   stream: refused inside a stream capture.
+ * Refused with PMG_ERR_INVALID and nothing written: a NULL op, g or b, a NULL h or NULL facet lists with nfacets > 0;
+ * b overlapping g, x0 or h; a facet cell outside [0, ncells) or not in the operator's cell lists; a local facet outside
+ * 0..5. */
+int pmg_laplacian_apply_lifting(pmg_laplacian op, double* g, const double* x0, double alpha, double* b, pmg_stream stream);
+int pmg_laplacian_set_bc(pmg_laplacian op, const double* g, const double* x0, double alpha, double* b, pmg_stream stream);
+int pmg_laplacian_assemble_neumann(pmg_laplacian op, int32_t nfacets, const int32_t* facet_cells,
+                                   const int8_t* facet_local, const double* h, double* b, pmg_stream stream);
+int pmg_laplacian_lift_cell_count(pmg_laplacian op);
 int pmg_laplacian_degree(pmg_laplacian op);
 /* Geometry mode of the apply.  0 (default): the reference's data structure, the
  * stored tensor G[cell][q][6] is streamed (48 bytes per quadrature point).

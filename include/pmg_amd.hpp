@@ -670,6 +670,52 @@ public:
     require_same_map(f, b);
     check(pmg_laplacian_assemble_rhs(handle(f.map()), f.array().data(), b.mutable_array().data(), nullptr));
   }
+  /// fem::apply_lifting(b, {a}, {{bc}}, {x0}, alpha) for this operator (pmg_laplacian_apply_lifting):
+  /// b -= alpha * A (g - x0) restricted to marked columns and owned unmarked rows, A without row / column treatment.
+  /// Unmarked entries of g and x0 are never read; the ghosts of g are refreshed.
+  template <typename Vector>
+  void apply_lifting(Vector& g, Vector& b, T alpha = 1)
+  {
+    require_same_map(g, b);
+    check(pmg_laplacian_apply_lifting(handle(g.map()), g.mutable_array().data(), nullptr, (double)alpha,
+                                      b.mutable_array().data(), nullptr));
+  }
+  template <typename Vector>
+  void apply_lifting(Vector& g, const Vector& x0, Vector& b, T alpha = 1)
+  {
+    require_same_map(g, b);
+    require_same_map(x0, b);
+    check(pmg_laplacian_apply_lifting(handle(g.map()), g.mutable_array().data(), x0.array().data(), (double)alpha,
+                                      b.mutable_array().data(), nullptr));
+  }
+  /// fem::set_bc(b, {bc}, x0, alpha): b = alpha * (g - x0) on the marked owned entries (pmg_laplacian_set_bc).
+  template <typename Vector>
+  void set_bc(const Vector& g, Vector& b, T alpha = 1)
+  {
+    require_same_map(g, b);
+    check(pmg_laplacian_set_bc(handle(g.map()), g.array().data(), nullptr, (double)alpha, b.mutable_array().data(),
+                               nullptr));
+  }
+  template <typename Vector>
+  void set_bc(const Vector& g, const Vector& x0, Vector& b, T alpha = 1)
+  {
+    require_same_map(g, b);
+    require_same_map(x0, b);
+    check(pmg_laplacian_set_bc(handle(g.map()), g.array().data(), x0.array().data(), (double)alpha,
+                               b.mutable_array().data(), nullptr));
+  }
+  /// b += GLL-collocated int h v ds over the listed facets (pmg_laplacian_assemble_neumann): host lists of cells and
+  /// local facets (2 * axis + side), h a device array [nfacets][nd * nd], one value per facet point.
+  template <typename Vector>
+  void assemble_neumann(std::span<const std::int32_t> cells, std::span<const std::int8_t> local_facets,
+                        std::span<const T> h, Vector& b)
+  {
+    const std::size_t nf = (std::size_t)(_degree + 1) * (_degree + 1);
+    if (cells.size() != local_facets.size() || h.size() != cells.size() * nf)
+      throw std::runtime_error("MatFreeLaplacian::assemble_neumann: list sizes do not match");
+    check(pmg_laplacian_assemble_neumann(handle(b.map()), (std::int32_t)cells.size(), cells.data(), local_facets.data(),
+                                         h.data(), b.mutable_array().data(), nullptr));
+  }
   int degree() const { return _degree; }
 
   pmg_laplacian handle(const std::shared_ptr<const IndexMap>& map)

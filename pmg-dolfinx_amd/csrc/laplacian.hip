@@ -2777,6 +2777,7 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->G32);
   (void)hipFree(op->D32);
   (void)hipFree(op->diag32);
+  (void)hipFree(op->lift_cells);
   for (hipEvent_t e : op->prof_events)
     (void)hipEventDestroy(e);
   for (hipEvent_t e : {op->ev_fork, op->ev_order, op->ev_join})

@@ -84,6 +84,12 @@ struct pmg_laplacian_s
   float* diag32 = nullptr;        // [size_local + num_ghosts] float copy of diag_inv
   long long diag_version = 0;     // bumped whenever diag_inv changes; diag32 is current while the two agree
   long long diag32_version = -1;
+  // boundary data (boundary.hip): the listed cells that hold a marked dof, built on the first
+  // pmg_laplacian_apply_lifting (n_lift < 0: not yet) and freed with the handle; which cells are listed at all
+  // (host, built on the first pmg_laplacian_assemble_neumann)
+  int32_t* lift_cells = nullptr;
+  int32_t n_lift = -1;
+  std::vector<char> listed;
 };
 
 namespace pmg

@@ -178,6 +178,55 @@ class MatFreeLaplacian:
     def assemble_rhs(self, f: Vector, b: Vector):
         call("pmg_laplacian_assemble_rhs", self._handle, ptr(f.data), ptr(b.data), current_stream())
 
+    def _boundary_vectors(self, what, g, b, x0):
+        n = self.layout.size_local + self.layout.num_ghosts
+        for name, v in (("g", g), ("b", b)) + ((("x0", x0),) if x0 is not None else ()):
+            if not isinstance(v, Vector):
+                raise TypeError(f"{what}: {name} must be a Vector of the operator's layout")
+            if v.data.numel() != n:
+                raise ValueError(f"{what}: {name} has {v.data.numel()} entries, the operator's layout {n}")
+
+    def apply_lifting(self, g: Vector, b: Vector, x0: Vector = None, alpha: float = 1.0):
+        """dolfinx ``fem.apply_lifting`` for this operator (``pmg_laplacian_apply_lifting``):
+        b[i] -= alpha * sum_{j marked} A_ij (g[j] - x0[j]) on the owned unmarked rows, A without row / column
+        treatment.  Unmarked entries of ``g`` / ``x0`` are never read; the ghosts of ``g`` are refreshed."""
+        self._boundary_vectors("apply_lifting", g, b, x0)
+        call("pmg_laplacian_apply_lifting", self._handle, ptr(g.data), ptr(x0.data) if x0 is not None else None,
+             float(alpha), ptr(b.data), current_stream())
+
+    def set_bc(self, g: Vector, b: Vector, x0: Vector = None, alpha: float = 1.0):
+        """dolfinx ``fem.set_bc``: b[i] = alpha * (g[i] - x0[i]) on the marked owned entries."""
+        self._boundary_vectors("set_bc", g, b, x0)
+        call("pmg_laplacian_set_bc", self._handle, ptr(g.data), ptr(x0.data) if x0 is not None else None,
+             float(alpha), ptr(b.data), current_stream())
+
+    def assemble_neumann(self, cells, local_facets, h, b: Vector):
+        """b += GLL-collocated int h v ds over the listed facets (``pmg_laplacian_assemble_neumann``).  ``cells``
+        (int32) and ``local_facets`` (int8, 2 * axis + side) are host arrays, e.g. ``BoxPartition.exterior_facets()``;
+        ``h`` [nfacets, nd*nd] holds one value per facet point in the order of ``facet_nodes`` (numpy, uploaded here,
+        or a float64 device tensor).  Marked rows are skipped."""
+        import torch
+
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        local_facets = np.ascontiguousarray(local_facets, dtype=np.int8)
+        if cells.ndim != 1 or cells.shape != local_facets.shape:
+            raise ValueError("assemble_neumann: cells and local_facets are two lists of one length")
+        nf = (self.degree + 1) ** 2
+        if isinstance(h, torch.Tensor):
+            if h.dtype != torch.float64 or not h.is_contiguous():
+                raise TypeError("assemble_neumann: h must be a contiguous float64 tensor")
+        else:
+            h = _dev_f64(np.asarray(h, dtype=np.float64).reshape(-1), self.layout.device)
+        if h.numel() != cells.size * nf:
+            raise ValueError(f"assemble_neumann: h has {h.numel()} entries, {cells.size} facets need {cells.size * nf}")
+        self._boundary_vectors("assemble_neumann", b, b, None)
+        call("pmg_laplacian_assemble_neumann", self._handle, int(cells.size), cells.ctypes.data_as(_lib.c_ip),
+             local_facets.ctypes.data_as(_lib.c_bp), ptr(h), ptr(b.data), current_stream())
+
+    def lift_cell_count(self) -> int:
+        """Cells that hold a marked dof (the lifting's work list); -1 before the first ``apply_lifting``."""
+        return int(_lib.lib().pmg_laplacian_lift_cell_count(self._handle))
+
     def is_affine(self) -> bool:
         """Every cell is a parallelepiped (constant Jacobian)."""
         return bool(call("pmg_laplacian_is_affine", self._handle))

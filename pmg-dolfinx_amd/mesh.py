@@ -91,6 +91,20 @@ def dofmap_in_node_order(dofmap: np.ndarray, perm1d) -> np.ndarray:
     return np.ascontiguousarray(dofmap[:, cell_permutation(perm1d)])
 
 
+def facet_nodes(P: int, local_facet: int) -> np.ndarray:
+    """The nd*nd ascending cell-local node numbers t = a*nd^2 + b*nd + c of the face ``local_facet`` = 2 * axis + side
+    (side 0: xi_axis = 0, side 1: xi_axis = 1), in the order of the facet points of ``assemble_neumann``:
+    s = i*nd + j over the two remaining axes in increasing axis order, by ascending coordinate."""
+    if not 0 <= int(local_facet) <= 5:
+        raise ValueError("local facet outside 0..5")
+    nd = P + 1
+    axis, side = divmod(int(local_facet), 2)
+    idx = [np.arange(nd)] * 3
+    idx[axis] = np.array([P if side else 0])
+    a, b, c = np.meshgrid(*idx, indexing="ij")
+    return ((a * nd + b) * nd + c).ravel().astype(np.int32)
+
+
 @dataclass
 class LevelData:
     """Everything one p-level needs on one rank (host arrays)."""
@@ -278,6 +292,20 @@ class BoxPartition:
         )
         self._levels[P] = lv
         return lv
+
+    def exterior_facets(self):
+        """(cells int32, local_facets int8) of every face of a local cell -- ghost cells included -- that lies on the
+        boundary of the whole box; local facet = 2 * axis + side (``facet_nodes``).  Ordered by cell, then facet."""
+        cc = self.cell_coords
+        cells, facets = [], []
+        for axis in range(3):
+            for side, plane in ((0, 0), (1, self.n[axis] - 1)):
+                on = np.nonzero(cc[:, axis] == plane)[0]
+                cells.append(on)
+                facets.append(np.full(on.size, 2 * axis + side))
+        cells, facets = np.concatenate(cells), np.concatenate(facets)
+        order = np.lexsort((facets, cells))
+        return cells[order].astype(np.int32), facets[order].astype(np.int8)
 
     def dof_coordinates(self, P: int) -> np.ndarray:
         """Physical coordinates of the local dofs [ndofs_local, 3]: trilinear image

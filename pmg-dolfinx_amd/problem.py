@@ -25,11 +25,16 @@ def make_layout(lv, group=None, device="cuda", comm=None) -> Layout:
 class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
-                 node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None):
+                 node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
-        load vectors keep the per-cell ``kappa`` only (``pmg_laplacian_assemble_rhs``)."""
+        load vectors keep the per-cell ``kappa`` only (``pmg_laplacian_assemble_rhs``).
+
+        ``dirichlet`` (optional): a callable mapping dof coordinates ``[n, 3]`` to a boolean array; on every level
+        the Dirichlet marker becomes the exterior dofs for which it is true (default: the whole boundary).  The rest
+        of the boundary is natural; non-zero data enter through ``MatFreeLaplacian.apply_lifting`` / ``set_bc`` /
+        ``assemble_neumann`` on the caller's right-hand side."""
         import torch
 
         self.orders = tuple(int(p) for p in orders)
@@ -51,6 +56,9 @@ class PoissonHierarchy:
             lv = part.level(P)
             if level_hook is not None:  # bench.py --corrupt-halo: a deliberately wrong halo plan for the gate's own test
                 level_hook(lv)
+            if dirichlet is not None:
+                keep = np.asarray(dirichlet(part.dof_coordinates(P)), dtype=bool)
+                lv.bc_marker = (lv.bc_marker.astype(bool) & keep).astype(np.int8)
             layout = make_layout(lv, group, device, comm)
             dofmap = lv.dofmap
             if node_order in ("basix", "endpoints_first"):
