@@ -1,0 +1,223 @@
+// Private fragment of laplacian.hip, included there and nowhere else (inside its anonymous namespace): the layout of
+// the stored geometry tensor G, and the geometry, export, diagonal and load-vector kernels that index it.
+
+// Layout of the stored geometry tensor G (double2 pairs (G00,G01)(G02,G11)(G12,G22)).  Two layouts:
+//   default: [slot][layer c][pair][a*nd+b]
+//   flat (P = 2, gflat()): [patch][item][layer c][pair][cell of the item][a*nd+b],
+//     every (item, layer) block padded to whole 128-byte lines -- a wavefront then reads its item's
+//     layer as NJ full-width loads of 64 consecutive double2 (whole lines, none shared between two
+//     load instructions) and hands the values to the lanes that use them through LDS.  Pays where
+//     the per-cell planes are short and misaligned: P = 2 (seven 144-byte pieces per load
+//     instruction otherwise), 765 -> 674 us at 128^3; slower at P = 1, 3, 4 (1485 -> 1524, 513 -> 549,
+//     458 -> 480 us), so only P = 2 uses it.
+__host__ __device__ constexpr bool gflat(int nd) { return nd == 3; } // P = 2 only
+__host__ __device__ constexpr int gcw(int nd) // cells of an item (Shape<P>::CW)
+{
+  return nd == 6 ? 7 : nd == 9 ? 3 : nd * nd <= 64 ? 64 / (nd * nd) : 1;
+}
+__host__ __device__ constexpr int gls(int nd) { return ((3 * gcw(nd) * nd * nd + 7) / 8) * 8; } // layer stride
+__host__ __device__ constexpr long long gpatch(int nd, int K)
+{
+  return gflat(nd) ? (long long)((K + gcw(nd) - 1) / gcw(nd)) * nd * gls(nd) : (long long)K * 3 * nd * nd * nd;
+}
+// absolute position of (patch slot, quadrature point q = (a,b,c), component pair)
+__device__ __forceinline__ size_t gpos(int nd, int K, long long slot, int q, int pair)
+{
+  const int nsq = nd * nd, N = nsq * nd;
+  const int a = q / nsq, b = (q - a * nsq) / nd, c = q - a * nsq - b * nd;
+  if (!gflat(nd))
+    return (size_t)slot * 3 * N + (c * 3 + pair) * nsq + a * nd + b;
+  // flat: [patch][item][layer c][pair][cell of the item][a*nd+b]
+  const long long per_patch = gpatch(nd, K), p = slot / K;
+  const size_t base = (size_t)p * per_patch;
+  const int sl = (int)(slot - p * K), cw = gcw(nd), item = sl / cw;
+  const size_t row = (size_t)(item * nd + c) * gls(nd);
+  return base + row + pair * (cw * nsq) + (sl - item * cw) * nsq + a * nd + b;
+}
+
+// G for the patch slots [slot0, slot0 + nslots) and every q, paired layout (absolute positions:
+// in batch mode G points `slot0` slots before its buffer).  kfield (optional): the nodal coefficient, one value per
+// local dof; G_q is scaled by its value at the point's own dof (GLL collocation: the points are the nodes).  Threads
+// of a wavefront walk q, so the dofmap read is contiguous; the kfield gather follows the dofmap like the apply's x.
+__global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K,
+                                const int32_t* __restrict__ pcell,
+                                const double* __restrict__ xgeom,
+                                const int32_t* __restrict__ geom_dofmap,
+                                const double* __restrict__ dphi, const double* __restrict__ w,
+                                const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
+                                double2* __restrict__ G)
+{
+  const int nq = nd * nd * nd;
+  long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * nq)
+    return;
+  long long slot = gid / nq;
+  int q = (int)(gid - slot * nq);
+  slot += slot0;
+  int c = pcell[slot];
+  double g0 = 0, g1 = 0, g2 = 0, g3 = 0, g4 = 0, g5 = 0;
+  if (c >= 0)
+  {
+    double K[3][3], detJ;
+    jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
+    double s = w[q] / detJ;
+    if (kfield)
+      s *= kfield[dofmap[(size_t)c * nq + q]];
+    g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s; // :99-111
+    g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+    g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+    g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+    g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+    g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+  }
+  G[gpos(nd, K, slot, q, 0)] = make_double2(g0, g1);
+  G[gpos(nd, K, slot, q, 1)] = make_double2(g2, g3);
+  G[gpos(nd, K, slot, q, 2)] = make_double2(g4, g5);
+}
+
+// Constant geometry tensor of an affine cell: K K^T / detJ at the cell centre
+// (q-independent when the cell is a parallelepiped); G_q = w_q * this.
+__global__ void affine_geometry_kernel(long long nslots, const int32_t* __restrict__ pcell,
+                                       const double* __restrict__ xgeom,
+                                       const int32_t* __restrict__ geom_dofmap,
+                                       double* __restrict__ Gaff)
+{
+  long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= nslots)
+    return;
+  int c = pcell[slot];
+  double g[6] = {0, 0, 0, 0, 0, 0};
+  if (c >= 0)
+  {
+    const int32_t* gd = geom_dofmap + (size_t)c * 8;
+    const double* x0 = xgeom + 3 * (size_t)gd[0];
+    const double* xz = xgeom + 3 * (size_t)gd[1]; // (0,0,1)
+    const double* xy = xgeom + 3 * (size_t)gd[2]; // (0,1,0)
+    const double* xx = xgeom + 3 * (size_t)gd[4]; // (1,0,0)
+    double J[3][3];
+    for (int i = 0; i < 3; ++i)
+    {
+      J[i][0] = xx[i] - x0[i];
+      J[i][1] = xy[i] - x0[i];
+      J[i][2] = xz[i] - x0[i];
+    }
+    double K[3][3];
+    K[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+    K[0][1] = -J[0][1] * J[2][2] + J[0][2] * J[2][1];
+    K[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+    K[1][0] = -J[1][0] * J[2][2] + J[1][2] * J[2][0];
+    K[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+    K[1][2] = -J[0][0] * J[1][2] + J[0][2] * J[1][0];
+    K[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+    K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
+    K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+    const double detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
+    const double s = 1.0 / detJ;
+    g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
+    g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+    g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+    g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+    g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+    g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+  }
+  for (int d = 0; d < 6; ++d)
+    Gaff[slot * 6 + d] = g[d];
+}
+
+// paired slot layout -> the reference's [cell][q][6]
+// (qperm: the caller's quadrature-point number -> ascending; nullptr = the caller's order is ascending)
+__global__ void geometry_export_kernel(long long slot0, long long nslots, int nd, int K,
+                                       const int32_t* __restrict__ pcell, const int32_t* __restrict__ qperm,
+                                       const double2* __restrict__ G, double* __restrict__ out)
+{
+  const int nq = nd * nd * nd;
+  long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * nq)
+    return;
+  long long slot = gid / nq;
+  const int qc = (int)(gid - slot * nq); // the caller's number of the point
+  const int q = qperm ? qperm[qc] : qc;
+  slot += slot0;
+  int c = pcell[slot];
+  if (c < 0)
+    return;
+  double2 a = G[gpos(nd, K, slot, q, 0)], b = G[gpos(nd, K, slot, q, 1)],
+          d = G[gpos(nd, K, slot, q, 2)];
+  double* o = out + ((size_t)c * nq + qc) * 6;
+  o[0] = a.x;
+  o[1] = a.y;
+  o[2] = b.x;
+  o[3] = b.y;
+  o[4] = d.x;
+  o[5] = d.y;
+}
+
+// ---- matrix-free diagonal (replaces the CSR detour of examples/pmg/main.cpp:274-279) ----
+__global__ void diagonal_kernel(long long slot0, long long nslots, int nd, int K,
+                                const int32_t* __restrict__ pcell,
+                                const double2* __restrict__ G, const int32_t* __restrict__ dofmap,
+                                const int8_t* __restrict__ bc, const double* __restrict__ kappa,
+                                const double* __restrict__ D, double* __restrict__ diag)
+{
+  const int N = nd * nd * nd, nsq = nd * nd;
+  long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * N)
+    return;
+  long long slot = gid / N;
+  int t = (int)(gid - slot * N);
+  slot += slot0;
+  int cell = pcell[slot];
+  if (cell < 0)
+    return;
+  int a = t / nsq, b = (t - a * nsq) / nd, c = t - a * nsq - b * nd;
+  auto Gq = [&](int q, int pair) { return G[gpos(nd, K, slot, q, pair)]; };
+  double s = 0.0;
+  for (int q = 0; q < nd; ++q)
+  {
+    double da = D[q * nd + a], db = D[q * nd + b], dc = D[q * nd + c];
+    s += da * da * Gq(q * nsq + b * nd + c, 0).x; // G00 at (q,b,c)
+    s += db * db * Gq(a * nsq + q * nd + c, 1).y; // G11 at (a,q,c)
+    s += dc * dc * Gq(a * nsq + b * nd + q, 2).y; // G22 at (a,b,q)
+  }
+  double daa = D[a * nd + a], dbb = D[b * nd + b], dcc = D[c * nd + c];
+  s += 2.0
+       * (Gq(t, 0).y * daa * dbb + Gq(t, 1).x * daa * dcc + Gq(t, 2).x * dbb * dcc);
+  int32_t dof = dofmap[(size_t)cell * N + t];
+  if (!bc[dof])
+    atomicAdd(&diag[dof], kappa[cell] * s);
+}
+
+__global__ void diag_invert_kernel(int n, const int8_t* __restrict__ bc, double* __restrict__ d)
+{
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+  {
+    double v = d[i];
+    d[i] = bc[i] ? 1.0 : (v != 0.0 ? 1.0 / v : 0.0);
+  }
+}
+
+// ---- GLL-collocated load vector ----
+__global__ void rhs_kernel(long long nslots, int nq, const int32_t* __restrict__ pcell,
+                           const double* __restrict__ xgeom,
+                           const int32_t* __restrict__ geom_dofmap,
+                           const double* __restrict__ dphi, const double* __restrict__ w,
+                           const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc,
+                           const double* __restrict__ kappa, const double* __restrict__ f,
+                           double* __restrict__ b)
+{
+  long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * nq)
+    return;
+  long long slot = gid / nq;
+  int q = (int)(gid - slot * nq);
+  int c = pcell[slot];
+  if (c < 0)
+    return;
+  int32_t dof = dofmap[(size_t)c * nq + q];
+  if (bc[dof])
+    return; // set_bc: b[bc] = 0 (b is zeroed first)
+  double K[3][3], detJ;
+  jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
+  atomicAdd(&b[dof], kappa[c] * w[q] * detJ * f[dof]);
+}

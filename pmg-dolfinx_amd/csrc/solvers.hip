@@ -174,11 +174,7 @@ int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n,
     const double c1 = (2.0 * i - 1.0) / (2.0 * i + 3.0);
     const double c2 = (8.0 * i + 4.0) / (2.0 * i + 3.0) / lmax;
     // the last correction enters x here (1); when no residual is wanted either, r and z are dead behind this step (2)
-#ifdef PMG_CHEB_KEEP_RZ // timing comparison: always write r and z
-    const int x_final = (i + 1 == max_iter) ? 1 : 0;
-#else
     const int x_final = (i + 1 == max_iter) ? (need_r == ResidualNone ? 2 : 1) : 0;
-#endif
     if (x_zero && i == 1)
       launch_cheb_first(n, x, w.r, w.z, w.q, dinv, c1, c2, x_final, s, clear_q, n_total);
     else

@@ -1,0 +1,547 @@
+// Private fragment of laplacian.hip, included there and nowhere else (inside its anonymous namespace, after
+// geometry_kernels.hpp): Shape<P> and its policies, the write-back shared with the diagnostic stamps, and the column
+// form of the stiffness kernel.
+
+template <int P>
+struct Shape
+{
+  static constexpr int ND = P + 1;
+  static constexpr int N = ND * ND * ND;
+  static constexpr PatchShape PS = patch_shape(P);
+  static constexpr int K = PS.bx * PS.by * PS.bz; // cells per patch
+  static constexpr int MAXM = PS.max_m;           // patch dofs held in LDS
+  // An item is CW whole cells worked on by WPC waves, a lane one (a, b) column of one of the cells.  Where nd^2 divides
+  // 64 badly a wave per cell group idles many lanes (P = 5: 36 of 64, P = 8: 81 of 128); there four waves share an
+  // item of 7 (P = 5: 252 of 256 lanes) or 3 (P = 8: 243 of 256) cells and exchange their slices through workgroup
+  // barriers instead of wave-private fences -- worth it only with ONE item per workgroup, i.e. patches of exactly CW
+  // cells (round 3, profiles/kernel_tuning_r03.md section 12: P = 5 532 -> 466 us, P = 8 495 -> 421; P = 4 and P = 6,
+  // 78 % of the lanes busy, lose or gain nothing this way).
+  static constexpr int NQ2 = ND * ND;
+  static constexpr bool SHARED_ITEM = P == 5 || P == 8;
+  static constexpr int CW = P == 5 ? 7 : P == 8 ? 3 : (NQ2 <= 64 ? 64 / NQ2 : 1);
+  static constexpr int WPC = SHARED_ITEM ? 4 : (NQ2 + 63) / 64; // waves that share one item
+  static_assert(CW * NQ2 <= 64 * WPC, "an item's columns need a lane each");
+  static constexpr int ITEMS = (K + CW - 1) / CW;  // wave-items per full patch
+  // measured (profiles/kernel_roofline_r01.md, profiles/kernel_tuning_r02.md): 4 waves and more
+  // workgroups per CU for the register-heavy degrees and P = 3, 8 waves otherwise
+  static constexpr int NWMAX = (P == 3 || P == 5 || P == 6 || P == 8) ? 4 : 8;
+  static constexpr int NG = ITEMS < NWMAX / WPC ? ITEMS : NWMAX / WPC; // items in flight per workgroup
+  static constexpr int NW = NG * WPC;                                  // waves per workgroup
+  static constexpr int WTHREADS = NW * 64;
+  static constexpr int WITER = (MAXM + WTHREADS - 1) / WTHREADS;
+  static_assert(MAXM <= 65535, "patch positions are 16-bit");
+};
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains
+// the vector-memory counter (s_waitcnt vmcnt(0)), which would stall every wave on
+// the G loads issued at the top of the kernel; nothing in this kernel passes data
+// between threads through global memory, so LDS ordering is all that is needed
+// (cdna_hip_programming.md, "Pipelining across barriers").
+__device__ __forceinline__ void lds_barrier()
+{
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+
+// ---- write-back of a patch's sums, shared by the kernels below --------------------------------------------
+// Round 4, read at the ISA level: written as one loop "load the list entry, branch on it, store", the write-back was six
+// DEPENDENT round trips per thread -- `global_load_dword; s_waitcnt vmcnt(0); ... global_store` per entry, and since
+// the counter retires in order every one of those waits also covered the acknowledgement of the previous entry's
+// store.  So: the list entries are re-read in ONE pass of unconditional loads (clamped index), issued by every
+// wavefront as it leaves the cell loop, BEFORE the barrier that ends the accumulation; behind the barrier the stores
+// go out back to back; the rare Dirichlet rows (y = x, src/laplacian.hpp:273-274: one more load each) come last, in a
+// pass of their own that interior patches skip.
+template <int ITER, int THREADS>
+__device__ __forceinline__ void patch_list_reload(uint32_t (&mk)[ITER], const uint32_t* __restrict__ pd, int M, int t)
+{
+#pragma unroll
+  for (int k = 0; k < ITER; ++k)
+  {
+    const int i = t + k * THREADS;
+    mk[k] = pd[i < M ? i : M - 1];
+  }
+}
+template <int ITER, int THREADS, bool NT>
+__device__ __forceinline__ void patch_write_back(const uint32_t (&mk)[ITER], int M, int t, const double* sy,
+                                                 const double* __restrict__ x, double* __restrict__ y, int atomic_out)
+{
+  bool bc_row = false;
+#pragma unroll
+  for (int k = 0; k < ITER; ++k)
+  {
+    const int i = t + k * THREADS;
+    const uint32_t dof = mk[k] & PD_MASK;
+    const bool mine = i < M;
+    if (mine && !(mk[k] & PD_BC))
+    {
+      const double v = sy[i];
+      if (atomic_out)
+        atomicAdd(&y[dof], v); // merged launch (global_atomic_add_f64)
+      else if constexpr (NT)
+        __builtin_nontemporal_store(v, &y[dof]);
+      else
+        y[dof] = v;
+    }
+    bc_row |= mine && (mk[k] & (PD_BC | PD_ACC)) == PD_BC;
+  }
+  if (__builtin_amdgcn_ballot_w64(bc_row) != 0) // wave-uniform: interior patches never enter
+  {
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      if (i < M && (mk[k] & (PD_BC | PD_ACC)) == PD_BC)
+        y[mk[k] & PD_MASK] = x[mk[k] & PD_MASK]; // :273-274
+    }
+  }
+}
+
+// ---- diagnostic build only (-DPMG_STAMPS): where a wavefront spends its time -----------------------------------
+// Every wavefront keeps up to eight readings of the constant 100 MHz clock (s_memrealtime: 10 ns ticks) in scalar
+// registers and lane 0 stores them once, at its end, to a buffer of their own: [workgroup][wavefront][8].  No stamp
+// executes in the product build; the timings of a stamped build are read for their SHARES only
+// (cdna_hip_programming.md, In-kernel stamps).
+#ifdef PMG_STAMPS
+__device__ unsigned long long* g_stamp_buffer = nullptr;
+__device__ int g_stamp_capacity = 0; // workgroups the buffer has room for
+#define PMG_STAMP_DECL unsigned long long stamp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define PMG_STAMP(i)                                                                                                  \
+  do                                                                                                                  \
+  {                                                                                                                   \
+    __builtin_amdgcn_sched_barrier(0);                                                                                \
+    stamp_[i] = __builtin_amdgcn_s_memrealtime();                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                                                \
+  } while (0)
+#define PMG_STAMP_FLUSH(nwaves)                                                                                       \
+  do                                                                                                                  \
+  {                                                                                                                   \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* 7: the stores of the write-back are acknowledged */            \
+    PMG_STAMP(7);                                                                                                     \
+    if ((threadIdx.x & 63) == 0 && g_stamp_buffer && (int)blockIdx.x < g_stamp_capacity)                              \
+      for (int i_ = 0; i_ < 8; ++i_)                                                                                  \
+        g_stamp_buffer[((size_t)blockIdx.x * (nwaves) + (threadIdx.x >> 6)) * 8 + i_] = stamp_[i_];                   \
+  } while (0)
+#else
+#define PMG_STAMP_DECL
+#define PMG_STAMP(i)
+#define PMG_STAMP_FLUSH(nwaves)
+#endif
+
+// ---- the hot kernel, column form --------------------------------------
+//
+// One workgroup per patch, NW wavefronts.  Phase 0 / write-back as in the block
+// kernel.  In between every wavefront works on its own: it takes CW whole cells
+// (2 at P = 4), a lane owns the column of nd points above (a, b), keeps the
+// column's dofs and results in registers and marches through the nd layers
+// (the register-blocked 2-D scheme of libParanumal / hipBone).  Per layer the x
+// and y contractions exchange one nd x nd slice through a wave-private LDS
+// region -- LDS executes a wave's instructions in order, so no s_barrier and no
+// waitcnt is needed inside the cell loop, only a compiler fence; the z
+// contraction stays in registers with wave-uniform table entries (scalar loads).
+// A cell costs 4*nd LDS reads per point instead of 12*nd, the 1-D tables for the
+// lane's a and b sit in registers, and the layer-(k+1) slice of G is in flight
+// while layer k is computed.
+__device__ __forceinline__ void wave_fence()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Cache policy.  The G stream is read exactly once per application and is ~6x larger
+// than the MALL: it is loaded non-temporally (nt bit) so that it does not displace x, y,
+// the dof lists and the shared tables from L2 / MALL, and the write-back stores of y are
+// non-temporal as well.  Measured at P = 4, 64^3: 505 -> 475 us with nt stores, -> 430 us
+// with nt G loads on top; the sc0 / sc1 bits make no difference; nt on the x / y gathers
+// or on the dof lists is slower.
+// At P = 1 (8 quadrature points per cell, every dof shared by 8 cells) the default
+// policy is faster (1610 vs 1750 us at 256^3), so the hint starts at P = 2.
+constexpr int NT_FROM = 2;
+typedef double gvec2 __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ double2 gload(const double2* p)
+{
+  if constexpr (NT)
+  {
+    gvec2 v = __builtin_nontemporal_load(reinterpret_cast<const gvec2*>(p));
+    return make_double2(v.x, v.y);
+  }
+  else
+    return *p;
+}
+
+// Slice reads.  The compiler pairs neighbouring LDS reads into ds_read2_b64; issued one by one
+// (volatile LDS loads are not paired) the kernel is 7 % faster at P = 5 and 4 % at P = 8, unchanged at
+// P <= 4 and slower at P = 6, 7 (profiles/kernel_tuning_r02.md).
+typedef __attribute__((address_space(3))) volatile double lds_vdouble;
+template <bool UNPAIRED>
+__device__ __forceinline__ double slice_load(double& v)
+{
+  if constexpr (UNPAIRED)
+    return *(lds_vdouble*)&v;
+  else
+    return v;
+}
+constexpr bool unpaired_slice_reads(int P) { return P == 5 || P == 8; }
+
+// degrees whose kernel keeps the patch's dof list in LDS for the write-back (4 bytes per patch dof).  Round 4, two
+// rounds on one box against the list re-read from global memory: P = 5 454 against 460 - 470 us, P = 7 368 - 372 against
+// 376, P = 8 410 - 411 against 420; P = 4 +0.5 % (within noise, left out); P = 6 474 - 482 against 441 - 445 (the 9.6 KB
+// cost it a workgroup per CU).
+constexpr bool list_in_lds(int P) { return P == 5 || P == 7 || P == 8; }
+// ---- the transposed table without its registers (round 4) ----
+// The transposed table by an identity.  For Lagrange polynomials on ANY distinct nodes D_ij = (l_j / l_i) /
+// (x_i - x_j), i != j, with the barycentric weights l, hence D_ji = -(l_i / l_j)^2 D_ij and
+//     (D^T f)_i = 2 D_ii f_i - rho_i sum_j D_ij (f_j / rho_j),       rho_i = (l_i / l_0)^2 = -D_0i / D_i0,
+// i.e. the backward contraction is the FORWARD one applied to the scaled fluxes: the five registers of D[.][a] (and
+// the nine shift coefficients a DPP direction would need for its transpose) become rho, 1 / rho and 2 D_ii.  Same
+// value to rounding (tests: 1e-12 against the oracle), not bit for bit.  Both directions still go through their LDS
+// slices (the y contractions as DPP row shifts were measured and removed: profiles/dpp_identity_r04.txt).
+// P = 5 is the one degree where the identity pays: 129 registers instead of 164, and asked for four wavefronts per SIMD
+// the allocator finds 128 without a spill -- four workgroups per unit instead of three (33 KB of LDS each): 432 - 444
+// against 452 - 459 us at 51^3, 223 - 225 against 230 - 232 us at 40^3 (profiles/kernel_tuning_r04.md section 12).
+constexpr bool transposes_by_identity(int P) { return P == 5; }
+// minimum waves per SIMD the register allocation has to leave room for: two workgroups per CU up to
+// P = 4; the register-heavy degrees take what they need (profiles/kernel_resources_r02.md)
+template <int P>
+constexpr int min_waves_per_simd()
+{
+  // (P = 5 with the identity: the allocator lands on 129 registers; asked for four wavefronts per SIMD it has to find 128)
+  return P <= 4 ? (2 * Shape<P>::NW + 3) / 4 : transposes_by_identity(P) ? 4 : 1;
+}
+template <int P, bool AFF, bool NT>
+__global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
+    stiffness_column_kernel(const double* __restrict__ x, double* __restrict__ y,
+                            const double2* __restrict__ G, const double* __restrict__ Gaff,
+                            const double* __restrict__ W1, const int32_t* __restrict__ poff,
+                            const uint32_t* __restrict__ pdofs,
+                            const int32_t* __restrict__ lmap_id,
+                            const uint16_t* __restrict__ lmaps, const int32_t* __restrict__ pcell,
+                            const int32_t* __restrict__ pncell, const double* __restrict__ kappa,
+                            const double* __restrict__ Dg, int first, int atomic_out)
+{
+  using Sh = Shape<P>;
+  constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, CW = Sh::CW, NG = Sh::NG, WPC = Sh::WPC;
+  constexpr int MAXM = Sh::MAXM, THREADS = Sh::WTHREADS, ITER = Sh::WITER;
+  constexpr int WL = CW * NQ2; // columns of one item (a wave, or WPC waves sharing a cell)
+  // NT: streaming cache policy for G and the y write-back (chosen per operator, launch_stiffness)
+  constexpr bool UNPAIRED = unpaired_slice_reads(P);
+  __shared__ double sD[ND * ND];
+  __shared__ double skap[K];
+  __shared__ double sx[MAXM];
+  __shared__ double sy[MAXM];
+  // The patch's dof list, kept for the write-back (round 4): under load a dependent global load costs ~2 us even when
+  // it hits in L2 (in-kernel stamps, profiles/kernel_tuning_r04.md), and re-reading the list was one such round trip
+  // per workgroup behind its closing barrier.
+  constexpr bool LIST_IN_LDS = list_in_lds(P);
+  __shared__ uint32_t sm[LIST_IN_LDS ? MAXM : 1];
+  __shared__ double sq[NG * WL];
+  __shared__ double sgr[NG * WL + 1]; // (+ 1: a spare element nothing writes any more; it is part of the LDS size)
+  __shared__ double sgs[NG * WL];
+  // flat G layout: one layer of the item, as loaded (NJ x 64 double2), for the hand-over to the lanes
+  constexpr bool FLAT = !AFF && WPC == 1 && gflat(ND);
+  constexpr int FL = 3 * WL, NJ = (FL + 63) / 64, LS = gls(ND);
+  __shared__ double2 sgb[FLAT ? NG * NJ * 64 : 1];
+
+  PMG_STAMP_DECL;
+  PMG_STAMP(0); // entry
+  const int p = first + blockIdx.x;
+  const int t = threadIdx.x;
+  const int off = poff[p];
+  const int M = poff[p + 1] - off; // 1 <= M <= MAXM
+  const int table = lmap_id[p];
+  const int nc = pncell[p];
+
+  // ---- phase 0: gather (unconditional loads, clamped indices: counted vmcnt waits)
+  {
+    uint32_t m[ITER];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      m[k] = pdofs[off + (i < M ? i : M - 1)];
+    }
+    const int cellk = pcell[(size_t)p * K + (t < K ? t : K - 1)];
+    const double dval = Dg[t < ND * ND ? t : ND * ND - 1];
+    double xv[ITER], yv[ITER];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const uint32_t dof = m[k] & PD_MASK;
+      const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
+      xv[k] = x[dof];
+      const double* ya = acc ? (const double*)(y + dof) : (x + dof);
+      yv[k] = *ya;
+    }
+    const double kapk = kappa[cellk >= 0 ? cellk : 0];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      if (i < M)
+      {
+        const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
+        sx[i] = (m[k] & PD_BC) ? 0.0 : xv[k]; // src/laplacian.hpp:186-189
+        sy[i] = acc ? yv[k] : 0.0;
+        if constexpr (LIST_IN_LDS)
+          sm[i] = m[k];
+      }
+    }
+    if (t < ND * ND)
+      sD[t] = dval;
+    for (int i = t; i < K; i += THREADS)
+      skap[i] = (i == t) ? kapk : kappa[pcell[(size_t)p * K + i] >= 0 ? pcell[(size_t)p * K + i] : 0];
+  }
+  PMG_STAMP(1); // gathered values written to LDS
+  lds_barrier();
+  PMG_STAMP(2); // behind the gather's barrier
+
+  // ---- cell loop: each wave on its own
+  // (nd^2 > 64, i.e. P = 8: WPC waves share a cell, the slices are exchanged between
+  // them, so the fences inside the layer loop become workgroup barriers and every
+  // wave runs the same number of items)
+  const int wave = (t >> 6) / WPC, lane = (t & 63) + 64 * ((t >> 6) % WPC);
+  constexpr bool IDT = transposes_by_identity(P);
+  // the lanes past the item's columns idle on a copy of the last column
+  const bool lane_ok = lane < WL;
+  const int lw = lane_ok ? lane : WL - 1;
+  const int cw = lw / NQ2;          // cell of this lane inside the wave item
+  const int ab = lw - cw * NQ2;     // column: a = x index, b = y index
+  const int a = ab / ND, b = ab - a * ND;
+  // The lane's rows / columns of the 1-D table, in registers (4 nd doubles; re-reading them from LDS
+  // in every layer frees the registers for one more wave per SIMD but is 15 % slower at every degree,
+  // profiles/kernel_tuning_r02.md)
+  double Da[ND], Db[ND], DTa[ND], DTb[ND]; // D[a][.], D[b][.], D[.][a], D[.][b]
+#pragma unroll
+  for (int mm = 0; mm < ND; ++mm)
+  {
+    Da[mm] = sD[a * ND + mm];
+    Db[mm] = sD[b * ND + mm];
+    DTa[mm] = sD[mm * ND + a];
+    DTb[mm] = sD[mm * ND + b];
+  }
+  // the identity's constants (see transposes_by_identity): rho, 1 / rho, 2 D_ii for the lane's a and b
+  double rho_a = 1.0, irho_a = 1.0, d2a = 0.0, rho_b = 1.0, irho_b = 1.0, d2b = 0.0;
+  if constexpr (IDT)
+  {
+    rho_a = a == 0 ? 1.0 : -sD[a] / sD[a * ND];
+    rho_b = b == 0 ? 1.0 : -sD[b] / sD[b * ND];
+    irho_a = 1.0 / rho_a;
+    irho_b = 1.0 / rho_b;
+    d2a = 2.0 * sD[a * ND + a];
+    d2b = 2.0 * sD[b * ND + b];
+  }
+  const double wab = AFF ? W1[a] * W1[b] : 0.0; // 1-D GLL weights of the lane's column
+  double* q_s = sq + wave * WL + cw * NQ2;  // this cell's slices
+  double* gr_s = sgr + wave * WL + cw * NQ2;
+  double* gs_s = sgs + wave * WL + cw * NQ2;
+  double* gr_w = gr_s + ab; // where the lane writes its x flux
+  const int items = WPC > 1 ? (((nc + CW - 1) / CW + NG - 1) / NG) * NG : (nc + CW - 1) / CW;
+  auto slice_sync = [] {
+    if constexpr (WPC > 1)
+      lds_barrier();
+    else
+      wave_fence();
+  };
+
+  for (int it = wave; it < items; it += NG)
+  {
+#ifdef PMG_STAMPS
+    if (it >= wave + NG)
+      PMG_STAMP(3); // first item done (overwritten by later items: the start of the LAST item)
+#endif
+    const int slot = it * CW + cw;
+    const int slotc = slot < K ? slot : K - 1;
+    // (scalar bases + 32-bit lane offsets: a 64-bit per-lane pointer costs two registers, and a spilled one is reloaded
+    // behind a wait that drains the memory counter)
+    const uint16_t* lmb = lmaps + (size_t)table * (K * N);
+    const unsigned lmo = (unsigned)(slotc * N + ab);
+    constexpr int GPS = NQ2; // stride between the three pairs of a layer
+    const double2* Gb = G + (size_t)p * ((long long)K * 3 * N);
+    const unsigned Gs = (unsigned)(slotc * 3 * N + ab);
+    int l[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+      l[k] = lmb[lmo + (unsigned)(k * NQ2)];
+    // storedG: G layers 0 .. GD-1 in flight (empty slots hold zeros).
+    // affine cells (AFF): G_q = w_a w_b w_c * Gc with one constant tensor Gc per cell.
+    constexpr int GD = 1; // G layers in flight per wave (deeper costs registers, i.e. resident waves: no gain)
+    double2 gq[AFF ? 1 : GD][3];
+    double2 gfl[FLAT ? NJ : 1]; // flat layout: the next layer as loaded
+    // (only used when FLAT; the item index is wave-uniform: a scalar base plus 32-bit lane offsets)
+    const double2* Gi = G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS;
+    int eo[FLAT ? NJ : 1]; // the lane's elements of a layer (clamped: the tail lanes re-read the last one)
+    if constexpr (FLAT)
+    {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+        eo[jj] = lane + 64 * jj < FL ? lane + 64 * jj : FL - 1;
+    }
+    double gc[6] = {0, 0, 0, 0, 0, 0};
+    if constexpr (AFF)
+    {
+      const double* ga = Gaff + ((size_t)p * K + slotc) * 6;
+#pragma unroll
+      for (int d = 0; d < 6; ++d)
+        gc[d] = ga[d];
+    }
+    else if constexpr (FLAT)
+    {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+        gfl[jj] = gload<NT>(Gi + eo[jj]);
+    }
+    else
+    {
+#pragma unroll
+      for (int d = 0; d < GD; ++d)
+      {
+        gq[d][0] = gload<NT>(Gb + (Gs + (unsigned)(d * 3 * GPS)));
+        gq[d][1] = gload<NT>(Gb + (Gs + (unsigned)(d * 3 * GPS + GPS)));
+        gq[d][2] = gload<NT>(Gb + (Gs + (unsigned)(d * 3 * GPS + 2 * GPS)));
+      }
+    }
+    // (identity modes: kappa multiplies the cell's INPUT once -- the operator is linear in it, same value to rounding --
+    // and the positions are held two to a register through the layer loop)
+    const double kap = IDT ? 1.0 : skap[slotc];
+    double u[ND], Aq[ND];
+    {
+      const double kin = IDT ? skap[slotc] : 1.0;
+#pragma unroll
+      for (int k = 0; k < ND; ++k)
+      {
+        u[k] = IDT ? kin * sx[l[k]] : sx[l[k]];
+        Aq[k] = 0.0;
+      }
+    }
+    unsigned lp[IDT ? (ND + 1) / 2 : 1];
+    if constexpr (IDT)
+    {
+#pragma unroll
+      for (int k = 0; k < ND; k += 2)
+        lp[k / 2] = (unsigned)l[k] | (k + 1 < ND ? (unsigned)l[k + 1] << 16 : 0u);
+#pragma unroll
+      for (int j = 0; j < (ND + 1) / 2; ++j)
+        asm volatile("" : "+v"(lp[j])); // (opaque: the unpacked values are not kept alongside)
+    }
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      double2 g01, g23, g45;
+      if constexpr (AFF)
+      {
+        const double sc = wab * W1[k]; // w_a w_b w_c; W1[k] is wave-uniform (scalar load)
+        g01 = make_double2(sc * gc[0], sc * gc[1]);
+        g23 = make_double2(sc * gc[2], sc * gc[3]);
+        g45 = make_double2(sc * gc[4], sc * gc[5]);
+      }
+      else if constexpr (FLAT)
+      {
+        double2* gb = sgb + wave * (NJ * 64);
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj)
+          gb[lane + 64 * jj] = gfl[jj]; // as loaded ...
+        wave_fence();
+        g01 = gb[lw]; // ... and as used: [pair][cell of the item][column]
+        g23 = gb[WL + lw];
+        g45 = gb[2 * WL + lw];
+        if (k + 1 < ND)
+        {
+#pragma unroll
+          for (int jj = 0; jj < NJ; ++jj)
+            gfl[jj] = gload<NT>(Gi + (k + 1) * LS + eo[jj]);
+        }
+      }
+      else
+      {
+        g01 = gq[k % GD][0];
+        g23 = gq[k % GD][1];
+        g45 = gq[k % GD][2];
+        if (k + GD < ND) // refill the slot with layer k + GD
+        {
+          gq[k % GD][0] = gload<NT>(Gb + (Gs + (unsigned)((k + GD) * 3 * GPS)));
+          gq[k % GD][1] = gload<NT>(Gb + (Gs + (unsigned)((k + GD) * 3 * GPS + GPS)));
+          gq[k % GD][2] = gload<NT>(Gb + (Gs + (unsigned)((k + GD) * 3 * GPS + 2 * GPS)));
+        }
+      }
+      q_s[ab] = u[k];
+      slice_sync();
+      double qr = 0.0, qs = 0.0, qt = 0.0;
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+      {
+        qr += Da[mm] * slice_load<UNPAIRED>(q_s[mm * ND + b]);  // d/dx: sum over a, :195-199
+        qs += Db[mm] * slice_load<UNPAIRED>(q_s[a * ND + mm]);  // d/dy: sum over b, :206-210
+        qt += Dg[k * ND + mm] * u[mm];    // d/dz: registers, uniform table, :214-218
+      }
+      const double fr = kap * (g01.x * qr + g01.y * qs + g23.x * qt); // :233
+      const double fs = kap * (g01.y * qr + g23.y * qs + g45.x * qt); // :234
+      const double ft = kap * (g23.x * qr + g45.x * qs + g45.y * qt); // :235
+      double acc = 0.0;
+      if constexpr (IDT)
+      {
+        // the transposes as forward contractions of the scaled fluxes (see transposes_by_identity)
+        *gr_w = fr * irho_a;
+        gs_s[ab] = fs * irho_b;
+        slice_sync();
+        double sx_ = 0.0, sy_ = 0.0;
+#pragma unroll
+        for (int mm = 0; mm < ND; ++mm)
+        {
+          sx_ += Da[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
+          sy_ += Db[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
+          Aq[mm] += Dg[k * ND + mm] * ft;     // :263-267
+        }
+        acc = (d2a * fr + d2b * fs) - (rho_a * sx_ + rho_b * sy_);
+      }
+      else
+      {
+        gr_s[ab] = fr;
+        gs_s[ab] = fs;
+        slice_sync();
+#pragma unroll
+        for (int mm = 0; mm < ND; ++mm)
+        {
+          acc += DTa[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
+          acc += DTb[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
+          Aq[mm] += Dg[k * ND + mm] * ft;     // :263-267
+        }
+      }
+      Aq[k] += acc;
+      slice_sync();
+    }
+    // Every lane adds (no branch: a conditional here lets the compiler sink the
+    // whole accumulation into it and keep every layer's operands live); lanes
+    // without a cell (idle lanes, slots past the patch's cells -- their indices
+    // were clamped onto a real slot) add an exact zero.
+    const bool contributes = lane_ok && slot < nc;
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      const int lk = IDT ? (int)((lp[k / 2] >> (16 * (k & 1))) & 0xffffu) : l[k];
+      atomicAdd(&sy[lk], contributes ? Aq[k] : 0.0); // :270,277 -- in LDS (ds_add_f64)
+    }
+  }
+  // ---- write back (plain stores; the accumulator started from the earlier colours' y)
+  {
+    // (the thread index made opaque here: otherwise the list addresses are computed ahead of the cell loop and
+    // held -- or spilled -- through it)
+    PMG_STAMP(4); // cell loop done
+    int tw = t;
+    asm volatile("" : "+v"(tw));
+    uint32_t mk[ITER];
+    if constexpr (!LIST_IN_LDS)
+      patch_list_reload<ITER, THREADS>(mk, pdofs + off, M, tw);
+    lds_barrier();
+    if constexpr (LIST_IN_LDS)
+    {
+#pragma unroll
+      for (int k = 0; k < ITER; ++k)
+        mk[k] = sm[tw + k * THREADS < M ? tw + k * THREADS : M - 1];
+    }
+    PMG_STAMP(5); // behind the barrier that ends the accumulation
+    patch_write_back<ITER, THREADS, NT>(mk, M, tw, sy, x, y, atomic_out);
+    PMG_STAMP(6); // stores issued
+    PMG_STAMP_FLUSH(Sh::NW);
+  }
+}

@@ -9,7 +9,7 @@ reps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 part = pm.BoxPartition(n); lv = part.level(P); layout = pm.make_layout(lv)
 op = pm.MatFreeLaplacian(P, 2.0, lv.dofmap, part.xgeom, part.geom_dofmap, lv.lcells, lv.bcells, lv.bc_marker, layout)
 class V: pass
-big = part.ncells * (P + 1) ** 3 * 2 + 4096  # room for the linear gather / write-back ablations
+big = part.ncells * (P + 1) ** 3 * 2 + 4096  # (longer than the layout needs: any length from the layout's total up will do)
 x = V(); x.data = torch.randn(big, dtype=torch.float64, device="cuda")
 v = V(); v.data = torch.zeros(big, dtype=torch.float64, device="cuda")
 op.time_kernel(x, v, 3)

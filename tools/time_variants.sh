@@ -1,7 +1,7 @@
 #!/bin/bash
 # Time the operator apply of variant libraries in tools/abl (tools/build_variant.sh) for the P:n pairs given, on the GPU
 # box:   tools/time_variants.sh 4:64 6:43 8:32        (all libraries)
-#        LIBS="wb stream4" tools/time_variants.sh 4:64   (only these)
+#        LIBS="base p4long" tools/time_variants.sh 4:64   (only these)
 cd "$(dirname "$0")/.."
 libs=${LIBS:-$(ls tools/abl/lib_*.so | sed 's|tools/abl/lib_||; s|\.so||')}
 for Pn in "$@"; do
