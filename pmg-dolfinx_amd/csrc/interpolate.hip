@@ -859,63 +859,14 @@ extern "C" int pmg_interpolator_create_with_operator(
                          hipMemcpyDeviceToHost, s));
   PMG_HIP(hipStreamSynchronize(s));
 
-  // launch index of every patch
-  std::vector<int32_t> launch_of(np, 0);
-  for (size_t l = 0; l < v.launch_first->size(); ++l)
-    for (int q = 0; q < (*v.launch_count)[l]; ++q)
-      launch_of[(*v.launch_first)[l] + q] = (int32_t)l;
-
-  std::vector<int32_t> cpoff(np + 1, 0), clmap_id(np, 0), first(nc_total, INT32_MAX);
-  std::vector<uint32_t> cpdofs;
-  std::vector<uint16_t> clmaps;
-  std::map<std::vector<uint16_t>, int32_t> uniq;
-  std::vector<std::vector<int32_t>> lists(np);
-  int cmax = 1;
-  for (int p = 0; p < np; ++p)
-  {
-    std::vector<int32_t>& d = lists[p];
-    const int nc = (*v.pncell_h)[p];
-    for (int sl = 0; sl < nc; ++sl)
-    {
-      const int32_t cell = (*v.pcell_h)[(size_t)p * K + sl];
-      PMG_REQUIRE(cell >= 0 && cell < ncells, "pmg_interpolator_create_with_operator: cell out of range");
-      for (int k = 0; k < Nc; ++k)
-      {
-        const int32_t dof = h_dmc[(size_t)cell * Nc + k];
-        PMG_REQUIRE(dof >= 0 && dof < nc_total, "coarse dofmap entry %d out of range", dof);
-        d.push_back(dof);
-      }
-    }
-    std::sort(d.begin(), d.end());
-    d.erase(std::unique(d.begin(), d.end()), d.end());
-    PMG_REQUIRE(d.size() <= 65535, "coarse patch too large");
-    cmax = std::max(cmax, (int)d.size());
-    for (int32_t dof : d)
-      first[dof] = std::min(first[dof], launch_of[p]);
-  }
-  for (int p = 0; p < np; ++p)
-  {
-    const std::vector<int32_t>& d = lists[p];
-    for (int32_t dof : d)
-      cpdofs.push_back((uint32_t)dof | (first[dof] != launch_of[p] ? PD_ACC : 0u));
-    cpoff[p + 1] = (int32_t)cpdofs.size();
-    std::vector<uint16_t> lm((size_t)K * Nc, 0);
-    const int nc = (*v.pncell_h)[p];
-    for (int sl = 0; sl < nc; ++sl)
-    {
-      const int32_t cell = (*v.pcell_h)[(size_t)p * K + sl];
-      for (int k = 0; k < Nc; ++k)
-        lm[(size_t)sl * Nc + k] = (uint16_t)(
-            std::lower_bound(d.begin(), d.end(), h_dmc[(size_t)cell * Nc + k]) - d.begin());
-    }
-    auto it = uniq.find(lm);
-    if (it == uniq.end())
-    {
-      it = uniq.emplace(lm, (int32_t)uniq.size()).first;
-      clmaps.insert(clmaps.end(), lm.begin(), lm.end());
-    }
-    clmap_id[p] = it->second;
-  }
+  // the coarse dof lists of the fine operator's patches (patches.hip)
+  CoarsePlan cplan;
+  PMG_TRY(build_coarse_plan(cplan, K, Nc, np, v.pcell_h->data(), v.pncell_h->data(), *v.launch_first, *v.launch_count,
+                            v.merged ? 0 : v.n_launch_l, ncells, h_dmc.data(), nc_total));
+  const std::vector<int32_t>&cpoff = cplan.cpoff, &clmap_id = cplan.clmap_id;
+  const std::vector<uint32_t>& cpdofs = cplan.cpdofs;
+  const std::vector<uint16_t>& clmaps = cplan.clmaps;
+  const int cmax = cplan.cmax;
   ip->cmax_m = cmax;
   PMG_TRY(upload(&ip->cpoff, cpoff.data(), cpoff.size(), s));
   PMG_TRY(upload(&ip->cpdofs, cpdofs.data(), cpdofs.size(), s));

@@ -698,6 +698,88 @@ int build_chain_plan(ChainPlan& cp, const PatchPlan& plan, int32_t ndofs, const 
   cp.ok = true;
   return PMG_OK;
 }
+
+// ---- coarse dof lists of the patch-form transfers (patches.hpp, CoarsePlan) ----
+int build_coarse_plan(CoarsePlan& cp, int K, int Nc, int npatch, const int32_t* pcell, const int32_t* pncell,
+                      const std::vector<int32_t>& launch_first, const std::vector<int32_t>& launch_count, int n_plain,
+                      int32_t ncells, const int32_t* dofmap_coarse, int32_t nc_total)
+{
+  cp = CoarsePlan();
+  const int np = npatch;
+  // launch index of every patch
+  std::vector<int32_t> launch_of(np, 0);
+  for (size_t l = 0; l < launch_first.size(); ++l)
+    for (int q = 0; q < launch_count[l]; ++q)
+      launch_of[launch_first[l] + q] = (int32_t)l;
+
+  std::vector<int32_t> first(nc_total, INT32_MAX);
+  // (launch, patch) that last listed each coarse dof: two patches of one plain launch must not share one
+  std::vector<int32_t> stamp_launch(nc_total, -1), stamp_patch(nc_total, -1);
+  cp.cpoff.assign(np + 1, 0);
+  cp.clmap_id.assign(np, 0);
+  std::map<std::vector<uint16_t>, int32_t> uniq;
+  std::vector<std::vector<int32_t>> lists(np);
+  int cmax = 1;
+  for (int p = 0; p < np; ++p)
+  {
+    std::vector<int32_t>& d = lists[p];
+    const int nc = pncell[p];
+    for (int sl = 0; sl < nc; ++sl)
+    {
+      const int32_t cell = pcell[(size_t)p * K + sl];
+      if (cell < 0 || cell >= ncells)
+        return fail(PMG_ERR_INVALID, "pmg_interpolator_create_with_operator: cell out of range");
+      for (int k = 0; k < Nc; ++k)
+      {
+        const int32_t dof = dofmap_coarse[(size_t)cell * Nc + k];
+        if (dof < 0 || dof >= nc_total)
+          return fail(PMG_ERR_INVALID, "coarse dofmap entry %d out of range", dof);
+        d.push_back(dof);
+      }
+    }
+    std::sort(d.begin(), d.end());
+    d.erase(std::unique(d.begin(), d.end()), d.end());
+    if (d.size() > 65535)
+      return fail(PMG_ERR_INVALID, "coarse patch too large");
+    cmax = std::max(cmax, (int)d.size());
+    for (int32_t dof : d)
+    {
+      first[dof] = std::min(first[dof], launch_of[p]);
+      if (launch_of[p] < n_plain && stamp_launch[dof] == launch_of[p])
+        return fail(PMG_ERR_INVALID,
+                    "pmg_interpolator_create_with_operator: patches %d and %d of launch %d share coarse dof %d but no "
+                    "fine dof (the coarse and fine spaces do not conform)",
+                    stamp_patch[dof], p, launch_of[p], dof);
+      stamp_launch[dof] = launch_of[p];
+      stamp_patch[dof] = p;
+    }
+  }
+  for (int p = 0; p < np; ++p)
+  {
+    const std::vector<int32_t>& d = lists[p];
+    for (int32_t dof : d)
+      cp.cpdofs.push_back((uint32_t)dof | (first[dof] != launch_of[p] ? PD_ACC : 0u));
+    cp.cpoff[p + 1] = (int32_t)cp.cpdofs.size();
+    std::vector<uint16_t> lm((size_t)K * Nc, 0);
+    const int nc = pncell[p];
+    for (int sl = 0; sl < nc; ++sl)
+    {
+      const int32_t cell = pcell[(size_t)p * K + sl];
+      for (int k = 0; k < Nc; ++k)
+        lm[(size_t)sl * Nc + k]
+            = (uint16_t)(std::lower_bound(d.begin(), d.end(), dofmap_coarse[(size_t)cell * Nc + k]) - d.begin());
+    }
+    auto it = uniq.find(lm);
+    if (it == uniq.end())
+    {
+      it = uniq.emplace(lm, (int32_t)uniq.size()).first;
+      cp.clmaps.insert(cp.clmaps.end(), lm.begin(), lm.end());
+    }
+    cp.clmap_id[p] = it->second;
+  }
+  cp.cmax = cmax;
+  return PMG_OK;
+}
 } // namespace pmg
 
 extern "C" int pmg_set_merge_threshold(long long patch_dofs)

@@ -203,4 +203,25 @@ int build_chain_plan(ChainPlan& cp, const PatchPlan& plan, int32_t ndofs, const 
 int build_patch_plan(PatchPlan& plan, int P, int32_t ncells, const int32_t* dofmap,
                      const int8_t* bc, int32_t ndofs, const float* centroid,
                      const int32_t* lcells, int32_t n_l, const int32_t* bcells, int32_t n_b);
+
+// The coarse side of the patch-form p-transfers: per patch of the fine operator, the sorted list of the coarse dofs of
+// its cells (PD_ACC = a patch of an earlier launch holds the dof), the position of every (slot, coarse t) in that list
+// (clmaps, de-duplicated like PatchPlan::lmaps; plain t order, no table_index) and the longest list (cmax, >= 1).
+struct CoarsePlan
+{
+  std::vector<int32_t> cpoff;    // [npatch+1] offsets into cpdofs
+  std::vector<uint32_t> cpdofs;  // sorted coarse dofs of each patch, PD_ACC in the top bits
+  std::vector<int32_t> clmap_id; // [npatch]
+  std::vector<uint16_t> clmaps;  // [nuniq][K*Nc]
+  int cmax = 1;
+};
+// Host arrays only.  pcell / pncell / launch_first / launch_count / n_plain are the fine operator's PatchPlan.  Two
+// patches of one plain launch (index < n_plain) that share a coarse dof would race in the coloured write-back of the
+// restriction kernel (atomic_out = 0: start from coarse[d] if PD_ACC, else 0, then store).  That form is built into the
+// kernel but not launched today -- restrict_patched and the FP32 transfer zero-fill and add with atomics -- so the
+// PD_ACC bits of cpdofs and this refusal guard a path that is available, not one in use.  Conforming spaces never
+// trip it; anything else is refused (PMG_ERR_INVALID), although the atomic form would handle it.
+int build_coarse_plan(CoarsePlan& cp, int K, int Nc, int npatch, const int32_t* pcell, const int32_t* pncell,
+                      const std::vector<int32_t>& launch_first, const std::vector<int32_t>& launch_count, int n_plain,
+                      int32_t ncells, const int32_t* dofmap_coarse, int32_t nc_total);
 } // namespace pmg

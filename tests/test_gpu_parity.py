@@ -243,6 +243,42 @@ def test_transfer_parity(pm, pc, pf, n, warped, patched):
             ip.interpolate_add(vc, pm.Vector(Lf))
 
 
+def test_patch_transfer_refuses_nonconforming_spaces(pm):
+    """A discontinuous fine space under a continuous coarse one: the fine operator's patches share no fine dof, so
+    they all sit in one plain launch, yet neighbours share coarse dofs.  The coloured write-back of the restriction
+    kernel would race on them; the library launches only the atomic form today, so the refusal (build_coarse_plan)
+    guards a path that is available in the kernel, not one in use.  The half-built handle is not handed out."""
+    import ctypes as C
+
+    from pmg_dolfinx_amd import _lib
+    from pmg_dolfinx_amd._lib import call, current_stream, ptr, vp
+    from pmg_dolfinx_amd.laplacian import _dev_i32
+
+    pc, pf, n = 1, 2, (4, 4, 16)
+    part = pm.BoxPartition(n)
+    lc = part.level(pc)
+    ncells, Nf = lc.dofmap.shape[0], (pf + 1) ** 3
+    dmf = np.arange(ncells * Nf, dtype=np.int32).reshape(ncells, Nf)
+    Lc, Lf = pm.make_layout(lc), pm.Layout(ncells * Nf)
+    cells, none = np.arange(ncells, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    try:
+        pm.set_merge_threshold(0)
+        fop = pm.MatFreeLaplacian(pf, 2.0, dmf, part.xgeom, part.geom_dofmap, cells, none,
+                                  np.zeros(ncells * Nf, dtype=np.int8), Lf)
+        with pytest.raises(RuntimeError, match="conform"):
+            pm.Interpolator(pc, pf, lc.dofmap, dmf, cells, none, Lc, Lf, fine_operator=fop)
+        # the same call on the C ABI: the handle stays NULL (what was built is destroyed, nothing is handed out)
+        h = vp()
+        dc, df = _dev_i32(lc.dofmap, Lf.device), _dev_i32(dmf, Lf.device)
+        with pytest.raises(RuntimeError, match="conform"):
+            call("pmg_interpolator_create_ordered", C.byref(h), Lc.handle, Lf.handle, pc, pf, ncells, ptr(dc), ptr(df),
+                 cells.ctypes.data_as(_lib.c_ip), cells.size, none.ctypes.data_as(_lib.c_ip), 0, fop.handle, 0, None,
+                 None, current_stream())
+        assert not h.value
+    finally:
+        pm.set_merge_threshold(-1)  # (the default; the library has no getter for the value in force)
+
+
 @pytest.mark.parametrize("orders,n", [((1, 2, 4), 4), ((1, 3), 5), ((2, 4), (3, 4, 2)), ((3,), 3),
                                       ((1, 3, 6), 3), ((1, 2, 4, 8), 3),  # (1, 3, 6): BASELINE config 5's levels
                                       ((1, 5), (2, 2, 7)), ((3, 7), (2, 2, 3))])
