@@ -591,6 +591,22 @@ int pmg_interpolator_interpolate_add(pmg_interpolator ip, double* coarse, double
  * weighted transpose), updates the ghosts of `fine`, zeroes `coarse` first. */
 int pmg_interpolator_reverse_interpolate(pmg_interpolator ip, double* fine, double* coarse,
                                          pmg_stream stream);
+/* coarse = R (r - A z) in ONE kernel (not in the reference): the application of the fine-level operator `op` to z
+ * and the restriction of the residual it would feed, fused -- A z is never written, `coarse` is overwritten (it is
+ * zero-filled first and does not depend on its old contents), no fine vector is written.  The restriction is additive
+ * over cells for conforming spaces, so every patch workgroup of the apply restricts its cells' own contributions
+ * (r / multiplicity - A_cell z; on Dirichlet rows, where the apply sets (A z)_i = z_i, (r - z) / multiplicity) and all
+ * patches run in one launch without colours.  Same value as pmg_laplacian_apply followed by the restriction of the
+ * difference, to rounding.  It counts as one application of `op` (pmg_multigrid_apply_counts) and is not part of the
+ * stiffness profile (pmg_laplacian_read_profile keeps describing the plain kernel).
+ * Available -- otherwise PMG_ERR_INVALID with a message -- only where ALL of these hold:
+ *   - `ip` was created with `op` as its fine operator (patch form: pmg_interpolator_create_with_operator);
+ *   - the fine layout has no ghosts;
+ *   - the geometry of `op` is resident (pmg_laplacian_set_geometry_batch(op, 0));
+ *   - the degree pair (coarse, fine) is one of 1-2, 2-4, 1-3, 3-6 (the shared-item degrees 5 and 8 are not covered).
+ * Kappa, the coefficient field, the affine mode and the cache policy work as in pmg_laplacian_apply. */
+int pmg_interpolator_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z, const double* r,
+                                       double* coarse, pmg_stream stream);
 /* The two transfers of the FP32 V-cycle (pmg_multigrid_set_precision) on float device arrays of the layouts' sizes:
  * fine += P coarse, and coarse = R (fine - fine_sub) (`coarse` is overwritten; fine_sub may be NULL: coarse = R fine).
  * The float copy of the 1-D table is built on the first FP32 use and freed with the interpolator.  Refused with
@@ -711,6 +727,16 @@ long long pmg_multigrid_graph_replays(pmg_multigrid mg);
 /* Number of stiffness-kernel launches issued by the last pmg_multigrid_apply,
  * per level (coarse -> fine); for the byte accounting in bench.py. */
 int pmg_multigrid_apply_counts(pmg_multigrid mg, int* counts, int capacity);
+/* Restriction fused into the pre-smooth's last application (pmg_interpolator_restrict_residual).  mode -1, the
+ * default: automatic -- on every level below whose transfer the fused form is available (see there) and which has no
+ * level matrix (pmg_multigrid_set_level_matrix), the FP64 cycle does not issue the pre-smooth's last A z nor the
+ * restriction of r - A z but the one fused kernel; a smoother of one iteration keeps its own path.  Everywhere else --
+ * layouts with ghosts, batched geometry, other degree pairs, interpolators without patches, the FP32 cycle -- the cycle
+ * runs exactly as without this switch.  mode 0: never.  The mode is part of the graph key and setting it drops the
+ * cached graphs.  Results agree with the unfused cycle to rounding; pmg_multigrid_apply_counts is the same in both.
+ * pmg_multigrid_fused_restrictions: how many fused kernels the last pmg_multigrid_apply issued (levels - 1 at most). */
+int pmg_multigrid_set_fused_restriction(pmg_multigrid mg, int mode);
+int pmg_multigrid_fused_restrictions(pmg_multigrid mg);
 /* Precision of the cycle (not in the reference).  PMG_PRECISION_FP64 (default): everything in FP64, as above.
  * PMG_PRECISION_FP32: every later pmg_multigrid_apply, and the V-cycle preconditioner inside pmg_cg_solve, runs the
  * smoothers, operators (pmg_laplacian_apply_f32) and transfers of every level in FP32; rhs and y stay double.

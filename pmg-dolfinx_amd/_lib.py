@@ -152,6 +152,7 @@ _SIGS = {
     "pmg_interpolator_destroy": (C.c_int, [vp]),
     "pmg_interpolator_interpolate": (C.c_int, [vp, vp, vp, vp]),
     "pmg_interpolator_reverse_interpolate": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_interpolator_restrict_residual": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "pmg_interpolator_interpolate_add_f32": (C.c_int, [vp, vp, vp, vp]),
     "pmg_interpolator_reverse_interpolate_f32": (C.c_int, [vp, vp, vp, vp, vp]),
     "pmg_multigrid_create": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), vp]),
@@ -184,6 +185,8 @@ _SIGS = {
     "pmg_multigrid_apply_counts": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int]),
     "pmg_multigrid_set_graph": (C.c_int, [vp, C.c_int]),
     "pmg_multigrid_graph_replays": (C.c_longlong, [vp]),
+    "pmg_multigrid_set_fused_restriction": (C.c_int, [vp, C.c_int]),
+    "pmg_multigrid_fused_restrictions": (C.c_int, [vp]),
     "pmg_matrix_create_from_laplacian": (C.c_int, [C.POINTER(vp), vp, vp]),
     "pmg_matrix_destroy": (C.c_int, [vp]),
     "pmg_matrix_update_values": (C.c_int, [vp, vp]),
@@ -205,7 +208,7 @@ _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplac
                 "pmg_laplacian_has_coefficient_field", "pmg_laplacian_lift_cell_count",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_layout_forward_scatters",
-                "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes"}
+                "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions"}
 
 _lib = None
 

@@ -205,7 +205,10 @@ enum : int
 {
   ResidualNone = 0,    // only x is wanted
   ResidualUpdated = 1, // w.r = b - A x on return
-  ResidualSplit = 2    // b - A x = w.r - w.q is left to the consumer when *split comes back true
+  ResidualSplit = 2,   // b - A x = w.r - w.q is left to the consumer when *split comes back true
+  ResidualFused = 3    // the last application is left to the consumer as well when *split comes back true:
+                       // b - A x = w.r - A w.z (a restriction fused into that application); a one-step smoother
+                       // keeps its own path and returns false with w.r = b - A x
 };
 // A_zeroed (optional): the same operator for an output vector that is already zero over [0, n_total) -- given for
 // an operator whose launch accumulates with atomics; the smoother's vector kernels then clear w.q behind themselves

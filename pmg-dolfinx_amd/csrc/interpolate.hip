@@ -18,6 +18,9 @@ namespace pmg
 {
 PatchView laplacian_patches(pmg_laplacian op);
 pmg_layout laplacian_layout(pmg_laplacian op);
+bool laplacian_fuses_restriction(pmg_laplacian op, int coarse_degree);
+int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const double* z, const double* r,
+                             double* coarse, hipStream_t s);
 }
 
 struct pmg_interpolator_s
@@ -719,6 +722,26 @@ int interp_restrict_difference(pmg_interpolator ip, double* fine, const double* 
   return restrict_patched(ip, fine, fine_sub, coarse, s);
 }
 
+// Can coarse = R (r - A z) be formed inside the application of `op` (stiffness_restrict_kernel, laplacian.hip)?  The
+// transfer is patched on the patches of this very operator, the fine vectors have no ghosts, the geometry is resident
+// and the degree pair is instantiated (pmg_amd.h, pmg_interpolator_restrict_residual).
+bool interp_fuses_residual(pmg_interpolator ip, pmg_laplacian op)
+{
+  return ip->patched && op && ip->lf->num_ghosts == 0 && laplacian_layout(op) == ip->lf
+         && laplacian_patches(op).pdofs == ip->fv.pdofs && laplacian_fuses_restriction(op, ip->pc);
+}
+
+// coarse = R (r - A z), A z never written
+int interp_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z, const double* r, double* coarse,
+                             hipStream_t s)
+{
+  PMG_REQUIRE(interp_fuses_residual(ip, op),
+              "the fused residual restriction is not available here: it needs a patch-form interpolator on the patches "
+              "of this operator, fine vectors without ghosts, resident geometry and one of the degree pairs 1-2, 2-4, "
+              "1-3, 3-6");
+  return laplacian_apply_restrict(op, interp_transfer_view(ip), z, r, coarse, s);
+}
+
 int interp_prolong(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s)
 {
   if (ip->patched)
@@ -968,6 +991,13 @@ extern "C" int pmg_interpolator_interpolate_add(pmg_interpolator ip, double* coa
     return interp_prolong_add(ip, coarse, fine, S(stream));
   return fail(PMG_ERR_INVALID, "pmg_interpolator_interpolate_add needs an interpolator created "
                                "with pmg_interpolator_create_with_operator");
+}
+
+extern "C" int pmg_interpolator_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z,
+                                                  const double* r, double* coarse, pmg_stream stream)
+{
+  PMG_REQUIRE(ip && op && z && r && coarse, "pmg_interpolator_restrict_residual: NULL argument");
+  return interp_restrict_residual(ip, op, z, r, coarse, S(stream));
 }
 
 extern "C" int pmg_interpolator_destroy(pmg_interpolator ip)

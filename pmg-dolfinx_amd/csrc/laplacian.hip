@@ -33,10 +33,11 @@
 // Roofline: HBM-bound, AI 0.85 (P=1) .. 2.05 (P=8) flop/B; algorithmic bytes per
 // cell 48N + 4N + 8 + 17U (model "storedG").
 //
-// One translation unit, four files (the fragments are included below, inside the anonymous namespace, in this order):
+// One translation unit, five files (the fragments are included below, inside the anonymous namespace, in this order):
 //   geometry_kernels.hpp  layout of G (gflat, gpatch, gpos); geometry, export, diagonal and load-vector kernels
 //   stiffness_column.hpp  Shape<P> and its policies, write-back, diagnostic stamps, stiffness_column_kernel
 //   stiffness_chain.hpp   ChainShape<P>, stiffness_chain_kernel (P = 4)
+//   stiffness_restrict.hpp  stiffness_restrict_kernel: the apply fused with the restriction of r - A z
 //   laplacian.hip         the host side: launch plan, run_launches, the C ABI
 #include "laplacian.hpp"
 
@@ -53,6 +54,7 @@ namespace
 #include "geometry_kernels.hpp"
 #include "stiffness_column.hpp"
 #include "stiffness_chain.hpp"
+#include "stiffness_restrict.hpp"
 
 __global__ void zero_list_kernel(int n, const int32_t* __restrict__ idx, double* __restrict__ y)
 {
@@ -282,10 +284,75 @@ int upload(T** dst, const T* src, size_t n, hipStream_t s)
   return PMG_OK;
 }
 
+// (fine degree, coarse degree) pairs stiffness_restrict_kernel is instantiated for
+#define PMG_FOR_FUSED_PAIRS(X) X(2, 1) X(4, 2) X(3, 1) X(6, 3)
+
+// all patches of the operator in one launch of the fused kernel (cache policy and affine mode as launch_stiffness)
+template <int P, int PC>
+int launch_stiffness_restrict(pmg_laplacian op, const TransferView& tv, const double* z, const double* r,
+                              double* coarse, hipStream_t s)
+{
+  constexpr int cm = RestrictShape<P, PC>::CM;
+  PMG_REQUIRE(tv.cmax_m <= cm, "internal: a patch holds %d coarse dofs, the fused kernel %d", tv.cmax_m, cm);
+  const RestrictLists R{tv.cpoff, tv.clmap_id, tv.cpdofs, tv.clmaps, tv.pmult, tv.M1};
+  const bool nt = P >= NT_FROM && op->geometry_mode != 1 && op->stream_policy;
+#define PMG_LAUNCH_FUSED(AFF_, NT_)                                                                                  \
+  stiffness_restrict_kernel<P, PC, AFF_, NT_><<<op->npatch, Shape<P>::WTHREADS, 0, s>>>(                             \
+      z, r, coarse, op->G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell,     \
+      op->kappa, op->D, R)
+  if (op->geometry_mode == 1)
+    PMG_LAUNCH_FUSED(true, false);
+  else if (nt)
+    PMG_LAUNCH_FUSED(false, true);
+  else
+    PMG_LAUNCH_FUSED(false, false);
+#undef PMG_LAUNCH_FUSED
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
 } // namespace
 
 namespace pmg
 {
+// Is the fused apply-and-restrict available on this operator towards degree `coarse_degree`?  (pmg_amd.h,
+// pmg_interpolator_restrict_residual: no ghosts, resident geometry, an instantiated pair -- which leaves out the
+// shared-item degrees 5 and 8)
+bool laplacian_fuses_restriction(pmg_laplacian op, int coarse_degree)
+{
+  if (op->layout->num_ghosts != 0 || op->batch_patches != 0)
+    return false;
+#define X(F, C)                                                                                                      \
+  if (op->P == F && coarse_degree == C)                                                                              \
+    return true;
+  PMG_FOR_FUSED_PAIRS(X)
+#undef X
+  return false;
+}
+
+// coarse = P^T (r - A z) without A z ever reaching memory: the coarse vector is zero-filled, then ALL patches of the
+// operator run in one launch (no colour order: nothing is written to a fine vector).  Counts as one application
+// (pmg_multigrid_apply_counts); it is not part of the stiffness profile, which keeps describing the plain kernel.
+int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const double* z, const double* r,
+                             double* coarse, hipStream_t s)
+{
+  PMG_REQUIRE(laplacian_fuses_restriction(op, tv.ndc - 1) && tv.ndf == op->nd && tv.fv.pdofs == op->pdofs
+                  && tv.fv.npatch == op->npatch && tv.lf == op->layout,
+              "laplacian_apply_restrict: not available for this operator and transfer");
+  launch_zero(tv.lc->total(), coarse, s);
+  if (op->npatch > 0)
+  {
+#define X(F, C)                                                                                                      \
+  if (op->P == F && tv.ndc - 1 == C)                                                                                 \
+    PMG_TRY((launch_stiffness_restrict<F, C>(op, tv, z, r, coarse, s)));
+    PMG_FOR_FUSED_PAIRS(X)
+#undef X
+    op->launches++;
+  }
+  op->applies++;
+  return PMG_OK;
+}
+
 // used by solvers.hip
 int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);

@@ -34,6 +34,9 @@ bool interp_is_patched(pmg_interpolator ip);
 bool interp_restricts_difference(pmg_interpolator ip);
 int interp_restrict_difference(pmg_interpolator ip, double* fine, const double* fine_sub, double* coarse,
                                hipStream_t s);
+bool interp_fuses_residual(pmg_interpolator ip, pmg_laplacian op);
+int interp_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z, const double* r, double* coarse,
+                             hipStream_t s);
 int amg_solve(pmg_amg amg, double* x, const double* b, hipStream_t s);
 pmg_layout amg_layout(pmg_amg amg);
 long long amg_capture_state(pmg_amg amg);
@@ -98,11 +101,16 @@ struct pmg_multigrid_s
     uint64_t config;
     hipGraphExec_t exec;
     std::vector<int> counts;
+    int fused_count;
   };
   int graph_mode = -1; // pmg_multigrid_set_graph: 1 replay when capturable, 0 never, -1 (default) automatic: use_graph()
   std::vector<GraphEntry> graphs;
   hipStream_t capture_stream = nullptr;
   long long graph_replays = 0;
+  // restriction fused into the pre-smooth's last application (pmg_multigrid_set_fused_restriction): -1 automatic,
+  // 0 never; fused_count = how many the last cycle issued
+  int fused_mode = -1;
+  int fused_count = 0;
   // FP32 cycle (pmg_multigrid_set_precision): float vectors of every level, allocated on the first FP32 cycle; the
   // operators and interpolators hold their own float forms (laplacian_f32.hip, cycle_f32.hip)
   int precision = PMG_PRECISION_FP64;
@@ -121,6 +129,9 @@ namespace pmg
 //            ResidualSplit   -- as ResidualUpdated, but the last "r -= q" is left to the consumer when *split
 //                               comes back true: b - A x = w.r - w.q (a restriction subtracts while it gathers; a
 //                               one-step smoother, whose only kernel updates x and r together, returns false).
+//            ResidualFused   -- the last apply itself is left to the consumer when *split comes back true:
+//                               b - A x = w.r - A w.z, for a restriction that forms A w.z on the fly
+//                               (interp_restrict_residual); a one-step smoother keeps its path and returns false.
 int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n, double lmax, int max_iter,
                  double* x, const double* b, int need_r, bool x_zero, hipStream_t s, bool* split,
                  const ApplyFn* A_zeroed, int n_total, bool track_ghosts, const ApplyFn* A_first)
@@ -156,6 +167,11 @@ int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n,
         else
           launch_add(n, x, w.z, s);
       }
+      break;
+    }
+    if (last && need_r == ResidualFused && split && max_iter > 1)
+    {
+      *split = true; // x is final (x_final below); w.r and w.z are what the consumer reads
       break;
     }
     PMG_TRY(An(w.z, w.q)); // :76
@@ -238,6 +254,25 @@ int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b
   };
   return cheb_iterate(w, apply, matrix_diag_inv(M), l->size_local, sm->eig_max, sm->max_iter, x, b, need_r, x_zero, s,
                       split);
+}
+
+// Does level i's pre-smooth hand its last application to the restriction (stiffness_restrict_kernel)?  The level has
+// no assembled matrix and the transfer below it fuses on the level's operator (interp_fuses_residual: patch form, no
+// ghosts, resident geometry, an instantiated pair); pmg_multigrid_set_fused_restriction(mg, 0) turns it off.
+bool fuses_restriction(pmg_multigrid mg, int i)
+{
+  if (mg->fused_mode == 0 || i <= 0 || mg->mats[i] || !interp_fuses_residual(mg->interps[i - 1], mg->ops[i]))
+    return false;
+  // measurements: PMG_FUSED_DEGREES=4 (or 2,4 ...) fuses below these fine degrees only, 0 nowhere
+  if (const char* e = std::getenv("PMG_FUSED_DEGREES"))
+  {
+    const int P = pmg_laplacian_degree(mg->ops[i]);
+    for (const char* c = e; *c; ++c)
+      if (*c - '0' == P)
+        return true;
+    return false;
+  }
+  return true;
 }
 
 // the smoother of level i on whichever form of the operator the level has (pmg_multigrid_set_level_matrix)
@@ -353,6 +388,7 @@ int mg_prepare_f32(pmg_multigrid mg, hipStream_t s)
 int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStream_t s)
 {
   const int L = mg->L;
+  mg->fused_count = 0; // (the FP32 cycle does not fuse)
   std::vector<long long> before(L);
   for (int i = 0; i < L; ++i)
     before[i] = laplacian_launches(mg->ops[i]);
@@ -448,20 +484,30 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
   // folded into the smoothers' x_zero path.
   Range cycle("pmg:vcycle");
   mg->u[L - 1] = y;
+  mg->fused_count = 0;
   for (int i = L - 1; i > 0; --i)
   {
     const double* bi = (i == L - 1) ? rhs : mg->b[i];
     const bool zero = (i == L - 1) ? y_zero : true;
+    const bool fuse = fuses_restriction(mg, i);
     bool split = false;
     {
       Range rg("pmg:pre_smooth");
       // (several ranks: the iterate leaves the pre-smooth with current ghosts, see `local_correction` below)
       PMG_TRY(level_smooth(mg, i, mg->u[i], bi,
-                           interp_restricts_difference(mg->interps[i - 1]) ? ResidualSplit : ResidualUpdated, zero, s,
-                           &split, local_correction(mg, i))); // :83-87
+                           fuse                                              ? ResidualFused
+                           : interp_restricts_difference(mg->interps[i - 1]) ? ResidualSplit
+                                                                             : ResidualUpdated,
+                           zero, s, &split, local_correction(mg, i))); // :83-87
     }
     Range rg("pmg:restrict");
-    if (split) // the residual r - q is formed by the restriction's gather
+    if (split && fuse) // the smoother's last application and the restriction of r - A z in one kernel
+    {
+      PMG_TRY(interp_restrict_residual(mg->interps[i - 1], mg->ops[i], mg->smoothers[i]->z, mg->smoothers[i]->r,
+                                       mg->b[i - 1], s));
+      mg->fused_count++;
+    }
+    else if (split) // the residual r - q is formed by the restriction's gather
       PMG_TRY(interp_restrict_difference(mg->interps[i - 1], mg->smoothers[i]->r, mg->smoothers[i]->q,
                                          mg->b[i - 1], s));
     else
@@ -1006,6 +1052,7 @@ long long capture_config(pmg_multigrid mg)
   if (mg->coarse || mg->coarse_fn) // Krylov coarse solve / caller's solver: host in the loop
     return -1;
   mix((uint64_t)mg->precision);
+  mix((uint64_t)(mg->fused_mode + 1));
   if (mg->precision == PMG_PRECISION_FP32) // the float diagonals are converted when the cycle is captured
     for (int i = 0; i < mg->L; ++i)
       mix((uint64_t)laplacian_diag_version(mg->ops[i]));
@@ -1035,6 +1082,7 @@ int mg_apply_graph(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, 
     {
       PMG_HIP(hipGraphLaunch(g.exec, s));
       mg->counts = g.counts;
+      mg->fused_count = g.fused_count;
       mg->graph_replays++;
       *done = true;
       return PMG_OK;
@@ -1055,7 +1103,7 @@ int mg_apply_graph(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, 
   }
   if (e != hipSuccess || !graph)
     return fail(PMG_ERR_HIP, "capturing the V-cycle failed: %s", hipGetErrorString(e));
-  pmg_multigrid_s::GraphEntry g{rhs, y, y_zero, (uint64_t)cfg, nullptr, mg->counts};
+  pmg_multigrid_s::GraphEntry g{rhs, y, y_zero, (uint64_t)cfg, nullptr, mg->counts, mg->fused_count};
   const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
   (void)hipGraphDestroy(graph);
   if (ei != hipSuccess)
@@ -1077,6 +1125,17 @@ extern "C" int pmg_multigrid_set_graph(pmg_multigrid mg, int enable)
   mg->graph_mode = enable < 0 ? -1 : (enable != 0 ? 1 : 0);
   return PMG_OK;
 }
+
+extern "C" int pmg_multigrid_set_fused_restriction(pmg_multigrid mg, int mode)
+{
+  PMG_REQUIRE(mg, "pmg_multigrid_set_fused_restriction: NULL argument");
+  PMG_REQUIRE(mode == -1 || mode == 0, "pmg_multigrid_set_fused_restriction: mode %d (-1 automatic, 0 never)", mode);
+  drop_graphs(mg);
+  mg->fused_mode = mode;
+  return PMG_OK;
+}
+
+extern "C" int pmg_multigrid_fused_restrictions(pmg_multigrid mg) { return mg ? mg->fused_count : -1; }
 
 extern "C" int pmg_multigrid_set_precision(pmg_multigrid mg, int precision)
 {

@@ -1,0 +1,383 @@
+// Private fragment of laplacian.hip, included there and nowhere else (inside its anonymous namespace, after
+// stiffness_column.hpp): the operator application fused with the restriction of the residual it would feed.
+//
+// The last application of a pre-smooth, q = A z, is written to memory, read back once by the restriction as r - q and
+// never used again.  The restriction is linear and, for conforming spaces, additive over cells: P[f, c] is the same
+// from every cell that holds the fine dof f and zero for every coarse dof outside those cells, so
+//     P^T (r - A z) = sum over cells  P_cell^T (r|cell / mult - A_cell z)          (mult: cells that hold the dof).
+// The patch workgroup of the apply therefore restricts each cell's own contribution straight from its registers: it
+// never sums into the fine output, never writes q and never waits on a colour -- all patches of the operator go in ONE
+// launch.  On Dirichlet rows the apply's rule is q = z (stiffness_column.hpp, patch_write_back), so their share is
+// (r - z) / mult and the cell's product is dropped there.
+//
+// The gather, the cell loop, the layer march and the G pipeline are those of stiffness_column_kernel (WPC == 1 shapes
+// without the transposition identity); `sy` holds the residual shares instead of the output sums.  Behind the layer
+// loop the lane owns w(a, b, .) = share - A_cell z of its column: z is contracted in registers with the 1-D
+// interpolation table M1 (wave-uniform entries), x and y through the wave's slice arrays, and the (PC + 1)^3 results
+// are added to an LDS accumulator over the patch's coarse dofs, which goes to the coarse vector with one atomic per
+// patch coarse dof, as restrict_patch_kernel does (interpolate.hip).
+template <int P, int PC>
+struct RestrictShape
+{
+  using Sh = Shape<P>;
+  static_assert(Sh::WPC == 1 && !transposes_by_identity(P), "the fused form covers the one-wave-per-item shapes only");
+  static constexpr int NDC = PC + 1, NC = NDC * NDC * NDC;
+  static constexpr int CM = Sh::K * NC < Sh::MAXM ? Sh::K * NC : Sh::MAXM; // coarse dofs of a patch: never more
+  static constexpr int CITER = (CM + Sh::WTHREADS - 1) / Sh::WTHREADS;
+  static constexpr int BCW = Sh::WITER * Sh::WTHREADS / 64; // 64-bit words of the Dirichlet bit map
+};
+
+// the coarse side of a patched transfer, as the kernel reads it (TransferView, patches.hpp)
+struct RestrictLists
+{
+  const int32_t *cpoff, *clmap_id;
+  const uint32_t* cpdofs;
+  const uint16_t* clmaps;
+  const uint8_t* pmult;
+  const double* M1; // [P + 1][PC + 1]
+};
+
+// waves per SIMD the allocation has to leave room for: the column kernel's, with two exceptions.  P = 2: the coarse
+// sums push the workgroup past 80 KB of LDS, so one workgroup per CU is what runs.  P = 3: asked for the four the
+// column kernel reaches, the allocation stays at 128 registers instead of 129.  (P = 6, asked for the column kernel's
+// three: spills.)
+template <int P>
+constexpr int restrict_waves_per_simd()
+{
+  return P == 2 ? 2 : P == 3 ? 4 : min_waves_per_simd<P>();
+}
+
+template <int P, int PC, bool AFF, bool NT>
+__global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>())
+    stiffness_restrict_kernel(const double* __restrict__ z, const double* __restrict__ r, double* __restrict__ coarse,
+                              const double2* __restrict__ G, const double* __restrict__ Gaff,
+                              const double* __restrict__ W1, const int32_t* __restrict__ poff,
+                              const uint32_t* __restrict__ pdofs, const int32_t* __restrict__ lmap_id,
+                              const uint16_t* __restrict__ lmaps, const int32_t* __restrict__ pcell,
+                              const int32_t* __restrict__ pncell, const double* __restrict__ kappa,
+                              const double* __restrict__ Dg, RestrictLists R)
+{
+  using Sh = Shape<P>;
+  using Rs = RestrictShape<P, PC>;
+  constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, CW = Sh::CW, NG = Sh::NG;
+  constexpr int MAXM = Sh::MAXM, THREADS = Sh::WTHREADS, ITER = Sh::WITER;
+  constexpr int NDC = Rs::NDC, NC = Rs::NC, CM = Rs::CM, CITER = Rs::CITER;
+  constexpr int WL = CW * NQ2;
+  constexpr bool UNPAIRED = unpaired_slice_reads(P);
+  __shared__ double sD[ND * ND];
+  __shared__ double sM[ND * NDC];
+  __shared__ double sW[AFF ? ND : 1]; // affine mode: the 1-D weights, read per item instead of held per lane
+  __shared__ double skap[K];
+  __shared__ double sx[MAXM];
+  __shared__ double sy[MAXM]; // the residual shares r / mult ((r - z) / mult on Dirichlet rows)
+  __shared__ double sc[CM];   // the patch's coarse sums
+  __shared__ unsigned long long sbc[Rs::BCW]; // bit i: patch entry i is a Dirichlet row
+  __shared__ double ssl[3 * NG * WL]; // the three slices of every item in flight, in ONE array: one address register
+  constexpr bool FLAT = !AFF && gflat(ND);
+  constexpr int FL = 3 * WL, NJ = (FL + 63) / 64, LS = gls(ND);
+  __shared__ double2 sgb[FLAT ? NG * NJ * 64 : 1];
+
+  const int p = blockIdx.x;
+  const int t = threadIdx.x;
+  const int off = poff[p];
+  const int M = poff[p + 1] - off; // 1 <= M <= MAXM
+  const int table = lmap_id[p];
+  const int nc = pncell[p];
+  const int ctable = __builtin_amdgcn_readfirstlane(R.clmap_id[p]);
+  const int coff = R.cpoff[p];
+  const int Mc = R.cpoff[p + 1] - coff; // 1 <= Mc <= CM
+
+  // ---- phase 0: gather (unconditional loads, clamped indices)
+  {
+    uint32_t m[ITER];
+    uint8_t mu[ITER];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      const int ic = off + (i < M ? i : M - 1);
+      m[k] = pdofs[ic];
+      mu[k] = R.pmult[ic];
+    }
+    const int cellk = pcell[(size_t)p * K + (t < K ? t : K - 1)];
+    const double dval = Dg[t < ND * ND ? t : ND * ND - 1];
+    const double mval = R.M1[t < ND * NDC ? t : ND * NDC - 1];
+    double zv[ITER], rv[ITER];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const uint32_t dof = m[k] & PD_MASK;
+      zv[k] = z[dof];
+      rv[k] = r[dof];
+    }
+    const double kapk = kappa[cellk >= 0 ? cellk : 0];
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+    {
+      const int i = t + k * THREADS;
+      const bool bc = i < M && (m[k] & PD_BC);
+      if (i < M)
+      {
+        sx[i] = bc ? 0.0 : zv[k];                                   // src/laplacian.hpp:186-189
+        sy[i] = (bc ? rv[k] - zv[k] : rv[k]) / (double)mu[k];       // src/interpolate.hpp:81-82
+      }
+      const unsigned long long rows = __builtin_amdgcn_ballot_w64(bc); // the wave's entries are i & ~63 .. + 63
+      if ((t & 63) == 0)
+        sbc[i >> 6] = rows;
+    }
+    if (t < ND * ND)
+      sD[t] = dval;
+    if (t < ND * NDC)
+      sM[t] = mval;
+    if constexpr (AFF)
+    {
+      if (t < ND)
+        sW[t] = W1[t];
+    }
+    for (int i = t; i < K; i += THREADS)
+      skap[i] = (i == t) ? kapk : kappa[pcell[(size_t)p * K + i] >= 0 ? pcell[(size_t)p * K + i] : 0];
+    for (int i = t; i < CM; i += THREADS)
+      sc[i] = 0.0;
+  }
+  lds_barrier();
+
+  // ---- cell loop: each wave on its own (stiffness_column_kernel)
+  const int wave = t >> 6, lane = t & 63;
+  const bool lane_ok = lane < WL;
+  const int lw = lane_ok ? lane : WL - 1;
+  const int cw = lw / NQ2;
+  const int ab = lw - cw * NQ2;
+  const int a = ab / ND, b = ab - a * ND;
+  double Da[ND], Db[ND], DTa[ND], DTb[ND];
+#pragma unroll
+  for (int mm = 0; mm < ND; ++mm)
+  {
+    Da[mm] = sD[a * ND + mm];
+    Db[mm] = sD[b * ND + mm];
+    DTa[mm] = sD[mm * ND + a];
+    DTb[mm] = sD[mm * ND + b];
+  }
+  double* q_s = ssl + wave * WL + cw * NQ2; // this cell's slices
+  double* gr_s = q_s + NG * WL;
+  double* gs_s = q_s + 2 * NG * WL;
+  // the lane's coarse point (i, j) = (a, b) of a layer; lanes past the coarse points idle on a copy of the last one
+  // (worked out again from an opaque copy of the column index wherever they are needed: two integer operations
+  // instead of registers held through the layer loop -- or spilled there)
+  const bool coarse_ok = lane_ok && a < NDC && b < NDC;
+  auto coarse_point = [](int abv, int& i, int& j, int bound) {
+    asm volatile("" : "+v"(abv));
+    const int av = abv / ND, bv = abv - av * ND;
+    i = av < bound ? av : bound - 1;
+    j = bv < bound ? bv : bound - 1;
+  };
+  const int items = (nc + CW - 1) / CW;
+
+  for (int it = wave; it < items; it += NG)
+  {
+    const int slot = it * CW + cw;
+    const int slotc = slot < K ? slot : K - 1;
+    const uint16_t* lmb = lmaps + (size_t)table * (K * N);
+    const unsigned lmo = (unsigned)(slotc * N + ab);
+    constexpr int GPS = NQ2;
+    const double2* Gb = G + (size_t)p * ((long long)K * 3 * N);
+    const unsigned Gs = (unsigned)(slotc * 3 * N + ab);
+    int l[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+      l[k] = lmb[lmo + (unsigned)(k * NQ2)];
+    // where the lane's coarse results go (plain t order: (i * ndc + j) * ndc + k), requested with the fine positions
+    const uint16_t* clb = R.clmaps + (size_t)ctable * (K * NC);
+    int ic, jc;
+    coarse_point(ab, ic, jc, NDC);
+    const unsigned clo = (unsigned)(slotc * NC + (ic * NDC + jc) * NDC);
+    // (held two to a register through the layer loop, and opaque, so that the unpacked values are not kept alongside)
+    unsigned lcp[(NDC + 1) / 2];
+#pragma unroll
+    for (int k = 0; k < NDC; k += 2)
+      lcp[k / 2] = (unsigned)clb[clo + (unsigned)k] | (k + 1 < NDC ? (unsigned)clb[clo + (unsigned)(k + 1)] << 16 : 0u);
+#pragma unroll
+    for (int j = 0; j < (NDC + 1) / 2; ++j)
+      asm volatile("" : "+v"(lcp[j]));
+    double2 gq[3];
+    double2 gfl[FLAT ? NJ : 1];
+    const double2* Gi = G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS;
+    int eo[FLAT ? NJ : 1];
+    if constexpr (FLAT)
+    {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+        eo[jj] = lane + 64 * jj < FL ? lane + 64 * jj : FL - 1;
+    }
+    double gc[6] = {0, 0, 0, 0, 0, 0};
+    if constexpr (AFF)
+    {
+      const double* ga = Gaff + ((size_t)p * K + slotc) * 6;
+      // (kappa and the column's weights w_a w_b folded into the cell's constant tensor: same value to rounding)
+      int av, bv;
+      coarse_point(ab, av, bv, ND);
+      const double wab = skap[slotc] * (sW[av] * sW[bv]);
+#pragma unroll
+      for (int d = 0; d < 6; ++d)
+        gc[d] = wab * ga[d];
+    }
+    else if constexpr (FLAT)
+    {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+        gfl[jj] = gload<NT>(Gi + eo[jj]);
+    }
+    else
+    {
+      gq[0] = gload<NT>(Gb + Gs);
+      gq[1] = gload<NT>(Gb + (Gs + (unsigned)GPS));
+      gq[2] = gload<NT>(Gb + (Gs + (unsigned)(2 * GPS)));
+    }
+    const double kap = AFF ? 1.0 : skap[slotc];
+    double u[ND], Aq[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      u[k] = sx[l[k]];
+      Aq[k] = 0.0;
+    }
+    // (the fine positions as well: the epilogue needs them again)
+    unsigned lp[(ND + 1) / 2];
+#pragma unroll
+    for (int k = 0; k < ND; k += 2)
+      lp[k / 2] = (unsigned)l[k] | (k + 1 < ND ? (unsigned)l[k + 1] << 16 : 0u);
+#pragma unroll
+    for (int j = 0; j < (ND + 1) / 2; ++j)
+      asm volatile("" : "+v"(lp[j]));
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      double2 g01, g23, g45;
+      if constexpr (AFF)
+      {
+        g01 = make_double2(gc[0], gc[1]); // (the layer's weight w_c scales the three fluxes below)
+        g23 = make_double2(gc[2], gc[3]);
+        g45 = make_double2(gc[4], gc[5]);
+      }
+      else if constexpr (FLAT)
+      {
+        double2* gb = sgb + wave * (NJ * 64);
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj)
+          gb[lane + 64 * jj] = gfl[jj];
+        wave_fence();
+        g01 = gb[lw];
+        g23 = gb[WL + lw];
+        g45 = gb[2 * WL + lw];
+        if (k + 1 < ND)
+        {
+#pragma unroll
+          for (int jj = 0; jj < NJ; ++jj)
+            gfl[jj] = gload<NT>(Gi + (k + 1) * LS + eo[jj]);
+        }
+      }
+      else
+      {
+        g01 = gq[0];
+        g23 = gq[1];
+        g45 = gq[2];
+        if (k + 1 < ND)
+        {
+          gq[0] = gload<NT>(Gb + (Gs + (unsigned)((k + 1) * 3 * GPS)));
+          gq[1] = gload<NT>(Gb + (Gs + (unsigned)((k + 1) * 3 * GPS + GPS)));
+          gq[2] = gload<NT>(Gb + (Gs + (unsigned)((k + 1) * 3 * GPS + 2 * GPS)));
+        }
+      }
+      q_s[ab] = u[k];
+      wave_fence();
+      double qr = 0.0, qs = 0.0, qt = 0.0;
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+      {
+        qr += Da[mm] * slice_load<UNPAIRED>(q_s[mm * ND + b]);
+        qs += Db[mm] * slice_load<UNPAIRED>(q_s[a * ND + mm]);
+        qt += Dg[k * ND + mm] * u[mm];
+      }
+      const double sck = AFF ? W1[k] : kap; // W1[k] is wave-uniform (scalar load)
+      const double fr = sck * (g01.x * qr + g01.y * qs + g23.x * qt);
+      const double fs = sck * (g01.y * qr + g23.y * qs + g45.x * qt);
+      const double ft = sck * (g23.x * qr + g45.x * qs + g45.y * qt);
+      double acc = 0.0;
+      gr_s[ab] = fr;
+      gs_s[ab] = fs;
+      wave_fence();
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+      {
+        acc += DTa[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]);
+        acc += DTb[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]);
+        Aq[mm] += Dg[k * ND + mm] * ft;
+      }
+      Aq[k] += acc;
+      wave_fence();
+    }
+    // ---- the cell's share of the restricted residual.  w = share - A_cell z down the lane's column; the product is
+    // dropped on Dirichlet rows (a select, no branch: see the column kernel's epilogue).
+    // (the lane's coarse point opaque here as well: otherwise its columns of M1 are read ahead of the layer loop and
+    // held through it, as the thread index of the column kernel's write-back would be)
+    int ie, je;
+    coarse_point(ab, ie, je, NDC);
+    double w[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k)
+    {
+      const int lk = (int)((lp[k / 2] >> (16 * (k & 1))) & 0xffffu);
+      const bool bc = (sbc[lk >> 6] >> (lk & 63)) & 1ull;
+      w[k] = sy[lk] - (bc ? 0.0 : Aq[k]);
+    }
+    // z in registers: M1[c][k] is wave-uniform (scalar loads)
+    double tz[NDC];
+#pragma unroll
+    for (int k = 0; k < NDC; ++k)
+    {
+      tz[k] = 0.0;
+#pragma unroll
+      for (int c = 0; c < ND; ++c)
+        tz[k] += R.M1[c * NDC + k] * w[c];
+    }
+    const bool contributes = coarse_ok && slot < nc;
+#pragma unroll
+    for (int k = 0; k < NDC; ++k)
+    {
+      q_s[ab] = tz[k];
+      wave_fence();
+      double vx = 0.0; // x: (a', b) -> (i, b)
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+        vx += sM[mm * NDC + ie] * q_s[mm * ND + b];
+      gr_s[ab] = vx; // (lanes with a >= NDC hold a copy of row NDC - 1: written to their own place, never read)
+      wave_fence();
+      double vy = 0.0; // y: (i, b') -> (i, j)
+#pragma unroll
+      for (int mm = 0; mm < ND; ++mm)
+        vy += sM[mm * NDC + je] * gr_s[ie * ND + mm];
+      if (contributes)
+        atomicAdd(&sc[(lcp[k / 2] >> (16 * (k & 1))) & 0xffffu], vy); // in LDS (ds_add_f64)
+      wave_fence();
+    }
+  }
+  // ---- patch end: the coarse sums, one atomic per patch coarse dof (coarse was zero-filled by the host).  The coarse
+  // list is requested by every wavefront as it leaves the cell loop, in front of the barrier that ends the accumulation
+  // (as the column kernel re-reads its fine list: the thread index opaque, so that nothing is held through the loop).
+  int tw = t;
+  asm volatile("" : "+v"(tw));
+  uint32_t cm[CITER];
+#pragma unroll
+  for (int j = 0; j < CITER; ++j)
+  {
+    const int i = tw + j * THREADS;
+    cm[j] = R.cpdofs[coff + (i < Mc ? i : Mc - 1)];
+  }
+  lds_barrier();
+#pragma unroll
+  for (int j = 0; j < CITER; ++j)
+  {
+    const int i = tw + j * THREADS;
+    if (i < Mc)
+      atomicAdd(&coarse[cm[j] & PD_MASK], sc[i]);
+  }
+}

@@ -61,6 +61,13 @@ class Interpolator:
         call("pmg_interpolator_reverse_interpolate", self._handle, ptr(Q2_vector.data), ptr(Q1_vector.data),
              current_stream())
 
+    def restrict_residual(self, operator, z: Vector, r: Vector, Q1_vector: Vector):
+        """``Q1 = R (r - A z)`` in one kernel: the application of the fine operator and the restriction of the residual
+        fused, ``A z`` never written.  Raises :class:`PmgError` where the fused form is not available (ghosts, batched
+        geometry, another degree pair, no ``fine_operator``); see ``pmg_interpolator_restrict_residual``."""
+        call("pmg_interpolator_restrict_residual", self._handle, operator.handle, ptr(z.data), ptr(r.data),
+             ptr(Q1_vector.data), current_stream())
+
     def interpolate_add_fp32(self, coarse, fine):
         """fine += P coarse in FP32 (``pmg_interpolator_interpolate_add_f32``) on float32 device tensors of the two
         layouts' total sizes.  Patch form (``fine_operator``) and single domain only."""

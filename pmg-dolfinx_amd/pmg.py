@@ -109,6 +109,16 @@ class MultigridPreconditioner:
         on several ranks when the capture holds nothing but kernels); see ``pmg_multigrid_set_graph``."""
         call("pmg_multigrid_set_graph", self._handle, -1 if enable is None else (1 if enable else 0))
 
+    def set_fused_restriction(self, mode=None):
+        """Fuse the restriction into the pre-smooth's last operator application wherever that is available: ``None``
+        (or -1), the default, automatic; ``False`` (or 0) never.  See ``pmg_multigrid_set_fused_restriction``."""
+        code = -1 if mode is None or mode is True else int(mode)
+        call("pmg_multigrid_set_fused_restriction", self._handle, code)
+
+    def fused_restrictions(self) -> int:
+        """Fused apply-and-restrict kernels issued by the last :meth:`apply`."""
+        return call("pmg_multigrid_fused_restrictions", self._handle)
+
     PRECISIONS = {"fp64": 0, "fp32": 1}
 
     def set_precision(self, precision: str):
