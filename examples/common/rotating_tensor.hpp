@@ -1,0 +1,38 @@
+// The drivers' diffusion tensor (--kappa-tensor): one symmetric positive-definite tensor per cell with eigenvalues
+// (1, 2 + x, 4), rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z), at the cell centre (x, y, z) = the mean of the cell's
+// eight vertices.  Returns [ncells][6] as (xx, xy, xz, yy, yz, zz), the layout of
+// pmg_laplacian_set_coefficient_tensor.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+namespace examples
+{
+inline std::vector<double> rotating_tensor(const std::vector<double>& xgeom,
+                                           const std::vector<std::int32_t>& geom_dofmap)
+{
+  const std::size_t ncells = geom_dofmap.size() / 8;
+  std::vector<double> kt(6 * ncells);
+  for (std::size_t c = 0; c < ncells; ++c)
+  {
+    double x[3] = {0, 0, 0};
+    for (int k = 0; k < 8; ++k)
+      for (int d = 0; d < 3; ++d)
+        x[d] += 0.125 * xgeom[3 * (std::size_t)geom_dofmap[8 * c + k] + d];
+    const double az = 0.6 + 0.8 * x[1], ax = 0.4 + 0.5 * x[2];
+    const double cz = std::cos(az), sz = std::sin(az), cx = std::cos(ax), sx = std::sin(ax);
+    // R = Rz Rx, columns = the principal directions
+    const double R[3][3] = {{cz, -sz * cx, sz * sx}, {sz, cz * cx, -cz * sx}, {0.0, sx, cx}};
+    const double lam[3] = {1.0, 2.0 + x[0], 4.0};
+    double M[3][3];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j)
+        M[i][j] = R[i][0] * lam[0] * R[j][0] + R[i][1] * lam[1] * R[j][1] + R[i][2] * lam[2] * R[j][2];
+    double* t = kt.data() + 6 * c;
+    t[0] = M[0][0], t[1] = M[0][1], t[2] = M[0][2], t[3] = M[1][1], t[4] = M[1][2], t[5] = M[2][2];
+  }
+  return kt;
+}
+} // namespace examples

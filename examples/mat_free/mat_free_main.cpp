@@ -7,11 +7,15 @@
 // with the 7-point stencil the collocated P=1 operator reduces to, evaluated on the host.
 // --kappa-field sets the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z on the operator (not in the
 // reference); the stencil comparison, which is for a constant coefficient, is then left out.
+// --kappa-tensor sets the per-cell diffusion tensor with eigenvalues (1, 2 + x, 4) rotated by
+// Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z) at the cell centre (not in the reference); it combines with --kappa-field, and the
+// stencil comparison is left out as well.
 // --lift restates the right-hand side the reference's driver has commented out (:252-255): u = the assembled load of
 // f = 0 (:133,143: the interpolation of f is commented out as well), lifted with the boundary value 1.3 (:165) and
 // set_bc -- pmg_laplacian_assemble_rhs, _apply_lifting, _set_bc on the one operator -- instead of u = 1.
 // Single rank.
 #include "../common/box_mesh.hpp"
+#include "../common/rotating_tensor.hpp"
 #include "pmg_amd.hpp"
 
 #include <chrono>
@@ -29,7 +33,7 @@ int main(int argc, char** argv)
 {
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
-  bool mat_comp = false, kappa_field = false, lift = false;
+  bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false;
   std::size_t batch_size = 0; // :38,46-50: cells whose geometry tensor is held at a time (0 = all, resident)
   for (int i = 1; i < argc; ++i)
   {
@@ -46,6 +50,8 @@ int main(int argc, char** argv)
       mat_comp = true;
     else if (!std::strcmp(argv[i], "--kappa-field"))
       kappa_field = true;
+    else if (!std::strcmp(argv[i], "--kappa-tensor"))
+      kappa_tensor = true;
     else if (!std::strcmp(argv[i], "--lift"))
       lift = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
@@ -53,7 +59,7 @@ int main(int argc, char** argv)
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--lift]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--lift]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -84,6 +90,21 @@ int main(int argc, char** argv)
                                 bcells, bc.span(), batch_size);
     DeviceVector u(map, 1), y(map, 1);
     u.set(1.0);
+    if (kappa_tensor)
+    {
+      device_array<double> kt(examples::rotating_tensor(mesh.xgeom, mesh.geom_dofmap));
+      op.handle(map); // the handle is created with the first index map the operator sees
+      op.set_coefficient_tensor(kt.span()); // the library copies it
+    }
+    if (kappa_field || kappa_tensor)
+    {
+      std::vector<double> kh(V.ndofs);
+      // u = 1 lies in the kernel of the operator away from the boundary whatever the coefficient: a vector that
+      // shows the coefficient everywhere
+      for (std::size_t d = 0; d < kh.size(); ++d)
+        kh[d] = std::sin(1.0 + 3 * V.x[3 * d] + 5 * V.x[3 * d + 1] * V.x[3 * d + 2]);
+      u.copy_from_host(kh);
+    }
     if (kappa_field)
     {
       std::vector<double> kh(V.ndofs);
@@ -92,11 +113,6 @@ int main(int argc, char** argv)
       DeviceVector kq(map, 1);
       kq.copy_from_host(kh);
       op.set_coefficient_field(kq);
-      // u = 1 lies in the kernel of the operator away from the boundary whatever the coefficient: a vector that
-      // shows the field everywhere
-      for (std::size_t d = 0; d < kh.size(); ++d)
-        kh[d] = std::sin(1.0 + 3 * V.x[3 * d] + 5 * V.x[3 * d + 1] * V.x[3 * d + 2]);
-      u.copy_from_host(kh);
     }
     if (lift)
     {
@@ -149,7 +165,7 @@ int main(int argc, char** argv)
       std::printf("CSR Matvec: %d reps, %.3f us per apply\n", nreps, ms * 1e3 / nreps);
       std::printf("CSR nnz = %zu\n", mat.nnz());
       acc::axpy(ec, -1.0, y, zc);
-      if (degree != 1 || kappa_field)
+      if (degree != 1 || kappa_field || kappa_tensor)
       {
         std::printf("Norm of z = %.15e\n", acc::norm(zc));
         std::printf("Norm of error = %.3e\n", acc::norm(ec));

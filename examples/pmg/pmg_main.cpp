@@ -23,6 +23,10 @@
 //                    every halo exchange are captured on the compute stream: no host work per exchange)
 //   --fp32-cycle     run the V-cycle's smoothers, operators and transfers in FP32 (pmg_multigrid_set_precision); the
 //                    stationary cycles, PCG and residuals stay FP64.  Single domain only: refused with --ranks
+//   --kappa-field    the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z on every level
+//   --kappa-tensor   a per-cell diffusion tensor on every level: eigenvalues (1, 2 + x, 4), rotated by
+//                    Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z) at the cell centre (pmg_laplacian_set_coefficient_tensor);
+//                    combines with --kappa-field, --amg, --pcg, --fp32-cycle, --csr
 //   --check-partition px,py,pz   host-only consistency check of the brick partition (no GPU)
 //   --node-order basix   the dofmaps handed over in basix's cell-local node order (endpoints first), as dolfinx
 //                    gives them to the reference (examples/pmg/main.cpp:83-87); same numbers as without
@@ -31,6 +35,7 @@
 #include "../common/box_mesh.hpp"
 #include "../common/brick_partition.hpp"
 #include "../common/rank_launch.hpp"
+#include "../common/rotating_tensor.hpp"
 #include "pmg_amd.hpp"
 
 #include <algorithm>
@@ -81,6 +86,7 @@ struct Options : examples::RankOptions
   pmg_amd::NodeOrder node_order = pmg_amd::NodeOrder::ascending; // of the dofmaps handed to the library
   bool amg_gather = false; // --amg-setup gathered
   bool kappa_field = false;    // --kappa-field: the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z
+  bool kappa_tensor = false;   // --kappa-tensor: per-cell tensor, eigenvalues (1, 2 + x, 4) rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z)
   bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
   std::vector<int> csr_levels; // empty with --csr: every level
 };
@@ -158,6 +164,12 @@ void solve(const Options& o)
       DeviceVector kq(maps[i], 1);
       hip_check(hipMemcpy(kq.mutable_array().data(), kh.data(), sizeof(T) * kh.size(), hipMemcpyHostToDevice), "H2D");
       operators[i]->set_coefficient_field(kq);
+    }
+    if (o.kappa_tensor) // -div(kappa K grad u): one tensor per cell, the same cells on every level
+    {
+      device_array<T> kt(examples::rotating_tensor(mesh.xgeom, mesh.geom_dofmap));
+      operators[i]->handle(maps[i]); // the handle is created with the first index map the operator sees
+      operators[i]->set_coefficient_tensor(kt.span());
     }
     operators[i]->compute_diag_inverse(maps[i]);                  // replaces :274-279 (no CSR)
 
@@ -410,6 +422,8 @@ int main(int argc, char** argv)
         o.fp32_cycle = true;
       else if (!std::strcmp(argv[i], "--kappa-field"))
         o.kappa_field = true;
+      else if (!std::strcmp(argv[i], "--kappa-tensor"))
+        o.kappa_tensor = true;
       else if (!std::strcmp(argv[i], "--csr"))
       {
         o.csr = true;
@@ -476,7 +490,7 @@ int main(int argc, char** argv)
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
                      "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
-                     "           [--kappa-field]\n"
+                     "           [--kappa-field] [--kappa-tensor]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"

@@ -364,6 +364,34 @@ int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream strea
  * pmg_laplacian_has_coefficient_field: 1 / 0. */
 int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const double* kq, pmg_stream stream);
 int pmg_laplacian_has_coefficient_field(pmg_laplacian op);
+/* Full-tensor diffusion: -div(K grad u) with K symmetric positive definite and constant per cell (not in the
+ * reference).  The stored tensor G_q = adj(J) adj(J)^T w_q / detJ enters the form linearly, and with a tensor K_c it
+ * becomes G_q = adj(J) K_c adj(J)^T w_q / detJ: still six symmetric entries per point, so every form of the apply
+ * streams the same bytes as without one, and the diagonal, the assembled matrix (pmg_matrix_*) and the AMG set-up read
+ * that one tensor.  The effective coefficient is kappa[cell] * kq[dof(cell, q)] * K[cell]: the per-cell array and the
+ * nodal field keep their meaning and combine with it.
+ *
+ * `kt` is a device array [ncells][6], one tensor per local cell, ghost cells included -- exactly the cells kappa
+ * covers -- with the components in physical coordinates in the order (xx, xy, xz, yy, yz, zz), the order of G.  The
+ * library copies it; the caller may free it on return.  kt = NULL removes the tensor and restores the stored tensor
+ * without one bit for bit.  Every component must be finite and every tensor positive definite (leading minors:
+ * xx > 0, xx yy - xy^2 > 0, det > 0; one small reduction over the cells, summed over the ranks, so all ranks refuse
+ * or none does -- on several ranks the call is collective); otherwise PMG_ERR_INVALID, the message names how many
+ * cells failed, and nothing has changed.  The call rebuilds what depends on the tensor, in place and at the same
+ * addresses: the resident FP64 tensor (in batched-geometry mode every application folds the tensor in as it recomputes
+ * its batch), the float tensor if it has been built, the per-cell tensor of the affine mode (it becomes
+ * adj(J) K adj(J)^T / detJ), and the inverse diagonal if it came from pmg_laplacian_compute_diag_inverse (a diagonal
+ * installed with pmg_laplacian_set_diag_inverse is left alone).  An assembled matrix follows with
+ * pmg_matrix_update_values; a smoother's eigenvalue bound and an AMG hierarchy are the caller's to renew.  A captured
+ * V-cycle graph over the resident tensor stays valid (an FP32 cycle re-captures because the diagonal changed; in
+ * batched-geometry mode the captured geometry launches carry the tensor's address, and setting the first tensor or
+ * removing it re-captures).  Like the other set-up calls it allocates and synchronises the stream: not inside a stream
+ * capture (refused).  A per-cell tensor is constant over an affine cell, so unlike the nodal field it works in the
+ * affine geometry mode, in either order of the two calls.  pmg_laplacian_apply_lifting follows the tensor;
+ * pmg_laplacian_assemble_rhs and pmg_laplacian_assemble_neumann do not read it.
+ * pmg_laplacian_has_coefficient_tensor: 1 / 0, -1 for NULL. */
+int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const double* kt, pmg_stream stream);
+int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op);
 /* GLL-collocated load vector b_i = sum_cells kappa * w_q * detJ_q * f_i at q = i
  * (what dolfinx assemble_vector does for L = inner(f, v)*dx with the GLL rule,
  * examples/pmg/poisson.py:40; examples/pmg/main.cpp:289-295), then set_bc:
@@ -418,7 +446,8 @@ int pmg_laplacian_degree(pmg_laplacian op);
  * constant tensor per cell, so the kernel reads 48 bytes per CELL instead (same
  * result to rounding; not in the reference; SURVEY.md 8d calls this byte model
  * separate from storedG).  Fails if the mesh has a non-affine cell, or while a
- * coefficient field is set (pmg_laplacian_set_coefficient_field). */
+ * coefficient field is set (pmg_laplacian_set_coefficient_field).  A per-cell coefficient tensor
+ * (pmg_laplacian_set_coefficient_tensor) is constant over a cell and is carried by both modes. */
 int pmg_laplacian_is_affine(pmg_laplacian op);
 int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode);
 /* Geometry batching (src/laplacian.hpp:383-396; examples/mat_free/main.cpp:34-50 --batch_size):

@@ -662,6 +662,25 @@ public:
       check(pmg_laplacian_set_coefficient_field(_op, nullptr, nullptr));
   }
   bool has_coefficient_field() const { return _op && pmg_laplacian_has_coefficient_field(_op) == 1; }
+  /// Full-tensor diffusion (pmg_laplacian_set_coefficient_tensor; not in the reference): kt is device memory of
+  /// 6 * ncells values, one symmetric positive-definite tensor (xx, xy, xz, yy, yz, zz) per local cell, ghost cells
+  /// included; the operator becomes -div(kappa[cell] * kq(x) * K[cell] grad u).  The tensor, its float and affine
+  /// forms and a computed inverse diagonal follow; an assembled MatrixOperator follows with update_values().
+  /// The handle must exist: it is created with the first vector or index map the operator sees (handle(map)).
+  void set_coefficient_tensor(std::span<const T> kt)
+  {
+    if (kt.size() != 6 * _kappa.size())
+      throw std::runtime_error("MatFreeLaplacian: the coefficient tensor holds 6 values per cell");
+    if (!_op)
+      throw std::runtime_error("MatFreeLaplacian: set_coefficient_tensor before the operator has seen an index map");
+    check(pmg_laplacian_set_coefficient_tensor(_op, kt.data(), nullptr));
+  }
+  void clear_coefficient_tensor()
+  {
+    if (_op)
+      check(pmg_laplacian_set_coefficient_tensor(_op, nullptr, nullptr));
+  }
+  bool has_coefficient_tensor() const { return _op && pmg_laplacian_has_coefficient_tensor(_op) == 1; }
   /// b = GLL-collocated load vector of the nodal source f, BC rows zeroed
   /// (assemble_vector + set_bc, examples/pmg/main.cpp:289-300).  The scaling is by the per-cell coefficient only.
   template <typename Vector>

@@ -30,15 +30,16 @@ struct LiftShape
 // b[dof] -= alpha * (A_cell u_cell)[t] for the unmarked owned rows of the listed cells, with
 // u_cell[t] = marked(dof) ? g[dof] - x0[dof] : 0 -- the element kernel of src/laplacian.hpp:143-278 without its row and
 // column treatment, G_q computed in place (src/laplacian.hpp:72-111, as geometry_kernel: w_q / detJ, times the nodal
-// coefficient when one is set).  Unmarked entries of g and x0 are never read.
+// coefficient when one is set, and with the per-cell diffusion tensor between the two adjugates when one is set).
+// Unmarked entries of g and x0 are never read.
 template <int ND>
 __global__ void __launch_bounds__(LiftShape<ND>::THREADS)
     lifting_kernel(int nlift, const int32_t* __restrict__ lift_cells, const int32_t* __restrict__ dofmap,
                    const int8_t* __restrict__ bc, int32_t size_local, const double* __restrict__ xgeom,
                    const int32_t* __restrict__ geom_dofmap, const double* __restrict__ dphi,
                    const double* __restrict__ w, const double* __restrict__ D, const double* __restrict__ kfield,
-                   const double* __restrict__ kappa, const double* __restrict__ g, const double* __restrict__ x0,
-                   double alpha, double* __restrict__ b)
+                   const double* __restrict__ ktensor, const double* __restrict__ kappa, const double* __restrict__ g,
+                   const double* __restrict__ x0, double alpha, double* __restrict__ b)
 {
   using Sh = LiftShape<ND>;
   constexpr int N = Sh::N, CPW = Sh::CPW;
@@ -83,16 +84,34 @@ __global__ void __launch_bounds__(LiftShape<ND>::THREADS)
     double s = w[t] / detJ;
     if (kfield)
       s *= kfield[dof];
-    const double g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-    const double g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-    const double g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-    const double g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-    const double g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-    const double g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
     const double kc = kappa[cell];
-    f0[ci * N + t] = kc * (g0 * d0 + g1 * d1 + g2 * d2);
-    f1[ci * N + t] = kc * (g1 * d0 + g3 * d1 + g4 * d2);
-    f2[ci * N + t] = kc * (g2 * d0 + g4 * d1 + g5 * d2);
+    if (ktensor)
+    {
+      // G d = s K (T (K^T d)) without forming G: three 3-vectors instead of the six entries and the nine of K T
+      const double* kt = ktensor + (size_t)cell * 6;
+      const double p0 = K[0][0] * d0 + K[1][0] * d1 + K[2][0] * d2;
+      const double p1 = K[0][1] * d0 + K[1][1] * d1 + K[2][1] * d2;
+      const double p2 = K[0][2] * d0 + K[1][2] * d1 + K[2][2] * d2;
+      const double r0 = kt[0] * p0 + kt[1] * p1 + kt[2] * p2;
+      const double r1 = kt[1] * p0 + kt[3] * p1 + kt[4] * p2;
+      const double r2 = kt[2] * p0 + kt[4] * p1 + kt[5] * p2;
+      const double ks = kc * s;
+      f0[ci * N + t] = ks * (K[0][0] * r0 + K[0][1] * r1 + K[0][2] * r2);
+      f1[ci * N + t] = ks * (K[1][0] * r0 + K[1][1] * r1 + K[1][2] * r2);
+      f2[ci * N + t] = ks * (K[2][0] * r0 + K[2][1] * r1 + K[2][2] * r2);
+    }
+    else
+    {
+      const double g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
+      const double g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+      const double g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+      const double g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+      const double g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+      const double g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+      f0[ci * N + t] = kc * (g0 * d0 + g1 * d1 + g2 * d2);
+      f1[ci * N + t] = kc * (g1 * d0 + g3 * d1 + g4 * d2);
+      f2[ci * N + t] = kc * (g2 * d0 + g4 * d1 + g5 * d2);
+    }
   }
   __syncthreads();
   if (active && !marked && dof < size_local)
@@ -199,7 +218,8 @@ void launch_lifting(pmg_laplacian op, const double* g, const double* x0, double 
   const unsigned blocks = (unsigned)((op->n_lift + Sh::CPW - 1) / Sh::CPW);
   lifting_kernel<ND><<<blocks, Sh::THREADS, 0, s>>>(op->n_lift, op->lift_cells, op->dofmap, op->bc,
                                                    op->layout->size_local, op->xgeom, op->geom_dofmap, op->dphi_geom,
-                                                   op->gweights, op->D, op->kfield, op->kappa, g, x0, alpha, b);
+                                                   op->gweights, op->D, op->kfield, op->ktensor, op->kappa, g, x0, alpha,
+                                                   b);
 }
 } // namespace
 

@@ -39,13 +39,18 @@ __device__ __forceinline__ size_t gpos(int nd, int K, long long slot, int q, int
 // in batch mode G points `slot0` slots before its buffer).  kfield (optional): the nodal coefficient, one value per
 // local dof; G_q is scaled by its value at the point's own dof (GLL collocation: the points are the nodes).  Threads
 // of a wavefront walk q, so the dofmap read is contiguous; the kfield gather follows the dofmap like the apply's x.
+// ktensor (optional): the per-cell diffusion tensor [ncells][6]; G_q = adj(J) K_c adj(J)^T w_q / detJ (tensor_geometry).
+// Its six values are one 48-byte read per cell, the same address for (nearly) every lane of a wavefront; the address
+// depends on the cell alone, not on anything computed per point.  The read is written inside the branch, after the
+// Jacobian: hoisted above it, it holds twelve more registers across the Jacobian's gathers (68 VGPRs and 7 waves per
+// SIMD instead of 60 and 8, with or without a tensor).  Without a tensor the branch is uniform and not taken.
 __global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K,
                                 const int32_t* __restrict__ pcell,
                                 const double* __restrict__ xgeom,
                                 const int32_t* __restrict__ geom_dofmap,
                                 const double* __restrict__ dphi, const double* __restrict__ w,
                                 const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
-                                double2* __restrict__ G)
+                                const double* __restrict__ ktensor, double2* __restrict__ G)
 {
   const int nq = nd * nd * nd;
   long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,12 +68,21 @@ __global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K
     double s = w[q] / detJ;
     if (kfield)
       s *= kfield[dofmap[(size_t)c * nq + q]];
-    g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s; // :99-111
-    g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-    g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-    g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-    g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-    g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+    if (ktensor)
+    {
+      double g[6];
+      tensor_geometry(K, ktensor + (size_t)c * 6, s, g);
+      g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5];
+    }
+    else
+    {
+      g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s; // :99-111
+      g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+      g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+      g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+      g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+      g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+    }
   }
   G[gpos(nd, K, slot, q, 0)] = make_double2(g0, g1);
   G[gpos(nd, K, slot, q, 1)] = make_double2(g2, g3);
@@ -76,11 +90,12 @@ __global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K
 }
 
 // Constant geometry tensor of an affine cell: K K^T / detJ at the cell centre
-// (q-independent when the cell is a parallelepiped); G_q = w_q * this.
+// (q-independent when the cell is a parallelepiped); G_q = w_q * this.  ktensor (optional): the per-cell diffusion
+// tensor, constant over the cell like the rest: K Kc K^T / detJ.
 __global__ void affine_geometry_kernel(long long nslots, const int32_t* __restrict__ pcell,
                                        const double* __restrict__ xgeom,
                                        const int32_t* __restrict__ geom_dofmap,
-                                       double* __restrict__ Gaff)
+                                       const double* __restrict__ ktensor, double* __restrict__ Gaff)
 {
   long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= nslots)
@@ -113,12 +128,22 @@ __global__ void affine_geometry_kernel(long long nslots, const int32_t* __restri
     K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
     const double detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
     const double s = 1.0 / detJ;
-    g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-    g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-    g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-    g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-    g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-    g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+    if (ktensor)
+    {
+      double t[6];
+      for (int d = 0; d < 6; ++d)
+        t[d] = ktensor[(size_t)c * 6 + d];
+      tensor_geometry(K, t, s, g);
+    }
+    else
+    {
+      g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
+      g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+      g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+      g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+      g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+      g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+    }
   }
   for (int d = 0; d < 6; ++d)
     Gaff[slot * 6 + d] = g[d];

@@ -72,7 +72,7 @@ const double2* batch_geometry(pmg_laplacian op, int first, int count, hipStream_
     geometry_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)first * op->K, nslots, op->nd, op->K,
                                                               op->pcell, op->xgeom, op->geom_dofmap,
                                                               op->dphi_geom, op->gweights, op->kfield, op->dofmap,
-                                                              base);
+                                                              op->ktensor, base);
   return base;
 }
 
@@ -375,8 +375,9 @@ long long laplacian_capture_state(pmg_laplacian op)
 {
   if (op->profiling)
     return -1;
-  // (batched geometry: the captured geometry launches carry the field's address; the resident tensor is rebuilt in
-  // place by pmg_laplacian_set_coefficient_field, so a graph over it stays valid)
+  // (batched geometry: the captured geometry launches carry the field's and the coefficient tensor's addresses -- one
+  // epoch counts both; the resident tensor is rebuilt in place by pmg_laplacian_set_coefficient_field / _tensor, so a
+  // graph over it stays valid)
   const long long field = op->batch_patches > 0 ? (op->kfield_epoch & 0x3fff) << 44 : 0;
   return ((long long)op->geometry_mode << 40) ^ ((long long)op->batch_patches << 8) ^ (long long)(op->have_diag ? 1 : 0)
          ^ (long long)(op->chain_on ? 2 : 0) ^ field;
@@ -713,7 +714,7 @@ extern "C" int pmg_laplacian_create_ordered(
   PMG_HIP(hipMalloc(&op->Gaff, sizeof(double) * 6 * (nslots ? nslots : 1)));
   if (nslots > 0)
     affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->pcell, xgeom,
-                                                                           geom_dofmap, op->Gaff);
+                                                                           geom_dofmap, nullptr, op->Gaff);
   {
     const size_t gsize = (size_t)op->npatch * gpatch(nd, op->K);
     PMG_HIP(hipMalloc(&op->G, sizeof(double2) * (gsize ? gsize : 1)));
@@ -768,6 +769,7 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->D);
   (void)hipFree(op->Gaff);
   (void)hipFree(op->kfield);
+  (void)hipFree(op->ktensor);
   (void)hipFree(op->W1);
   (void)hipFree(op->dphi_geom);
   (void)hipFree(op->gweights);
@@ -952,6 +954,88 @@ extern "C" int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const doubl
   if (op->have_diag && op->diag_computed)
     PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
   PMG_HIP(hipStreamSynchronize(s)); // the caller may free kq on return
+  if (released)
+    PMG_HIP(hipFree(released));
+  return PMG_OK;
+}
+
+// number of cells of kt[0, ncells)[6] whose tensor (xx, xy, xz, yy, yz, zz) is not finite and symmetric positive
+// definite (leading minors: xx > 0, xx yy - xy^2 > 0, det > 0), added to *bad (zeroed by the caller)
+__global__ void coefficient_tensor_check_kernel(int ncells, const double* __restrict__ kt, double* __restrict__ bad)
+{
+  int mine = 0;
+  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < ncells;
+       c += (long long)gridDim.x * blockDim.x)
+  {
+    const double* t = kt + c * 6;
+    const double xx = t[0], xy = t[1], xz = t[2], yy = t[3], yz = t[4], zz = t[5];
+    bool ok = true;
+    for (int d = 0; d < 6; ++d)
+      ok = ok && fabs(t[d]) <= 1.79769313486231570e308; // NaN and +-inf fail
+    const double m2 = xx * yy - xy * xy;
+    const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+    mine += !(ok && xx > 0.0 && m2 > 0.0 && det > 0.0);
+  }
+  if (mine)
+    atomicAdd(bad, (double)mine);
+}
+
+extern "C" int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op) { return op ? (op->ktensor ? 1 : 0) : -1; }
+
+extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const double* kt, pmg_stream stream)
+{
+  PMG_REQUIRE(op, "pmg_laplacian_set_coefficient_tensor: NULL argument");
+  hipStream_t s = S(stream);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  PMG_HIP(hipStreamIsCapturing(s, &cap));
+  PMG_REQUIRE(cap == hipStreamCaptureStatusNone,
+              "pmg_laplacian_set_coefficient_tensor: not inside a stream capture (it allocates and synchronises)");
+  pmg_layout l = op->layout;
+  double* released = nullptr;
+  if (!kt)
+  {
+    if (!op->ktensor)
+      return PMG_OK;
+    released = op->ktensor;
+    op->ktensor = nullptr;
+    op->kfield_epoch++;
+  }
+  else
+  {
+    // every cell's tensor finite and positive definite, on every rank (the count is summed over the ranks: all of
+    // them refuse, or none; a cell that is a ghost elsewhere is counted on each rank that holds it)
+    double* bad = red_slot(l, 0);
+    PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
+    if (op->ncells > 0)
+      coefficient_tensor_check_kernel<<<std::min((op->ncells + 255) / 256, 1024), 256, 0, s>>>(op->ncells, kt, bad);
+    PMG_HIP(hipGetLastError());
+    PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
+    double nbad = 0.0;
+    PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
+    if (nbad != 0.0)
+      return fail(PMG_ERR_INVALID,
+                  "pmg_laplacian_set_coefficient_tensor: %lld cells have a tensor that is not finite and positive "
+                  "definite",
+                  (long long)nbad);
+    if (!op->ktensor)
+    {
+      PMG_HIP(hipMalloc(&op->ktensor, sizeof(double) * 6 * (size_t)(op->ncells ? op->ncells : 1)));
+      op->kfield_epoch++;
+    }
+    PMG_HIP(hipMemcpyAsync(op->ktensor, kt, sizeof(double) * 6 * (size_t)op->ncells, hipMemcpyDeviceToDevice, s));
+  }
+  // what depends on G, each in its own buffer (a captured graph of this operator's launches stays valid)
+  if (op->batch_patches == 0 && op->npatch > 0)
+    batch_geometry(op, 0, op->npatch, s);
+  const long long nslots = (long long)op->npatch * op->K;
+  if (nslots > 0)
+    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->pcell, op->xgeom,
+                                                                           op->geom_dofmap, op->ktensor, op->Gaff);
+  PMG_HIP(hipGetLastError());
+  PMG_TRY(laplacian_f32_refresh(op, s));
+  if (op->have_diag && op->diag_computed)
+    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
+  PMG_HIP(hipStreamSynchronize(s)); // the caller may free kt on return
   if (released)
     PMG_HIP(hipFree(released));
   return PMG_OK;

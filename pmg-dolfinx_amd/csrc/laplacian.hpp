@@ -27,8 +27,12 @@ struct pmg_laplacian_s
   // built (geometry_kernel); nullptr = none
   double* kfield = nullptr;    // [size_local + num_ghosts], ghosts filled by the layout's forward scatter
   long long kfield_epoch = 0;  // bumped when kfield is allocated or freed (laplacian_capture_state, batch mode)
+  // per-cell diffusion tensor (pmg_laplacian_set_coefficient_tensor): symmetric positive definite, physical
+  // coordinates, (xx, xy, xz, yy, yz, zz); folded into G, the float tensor and Gaff where they are built
+  // (G_q = adj(J) K_c adj(J)^T w_q / detJ); nullptr = none.  Allocating or freeing it bumps kfield_epoch.
+  double* ktensor = nullptr;   // [ncells][6]
   bool diag_computed = false;  // diag_inv came from pmg_laplacian_compute_diag_inverse (it follows a change of field)
-  double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell
+  double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell (K Kc K^T / detJ with a coefficient tensor)
   double* W1 = nullptr;        // [nd] 1-D GLL weights
   bool all_affine = false;     // every listed cell is a parallelepiped
   int geometry_mode = 0;       // 0 = stored G (reference data structure), 1 = affine cells
@@ -128,5 +132,26 @@ __device__ inline void jacobian(const double* __restrict__ xgeom,
   // full cofactor expansion along the first row (the reference's :97 drops to
   // the diagonal-J special case)
   detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
+}
+
+// ---- the six entries of adj(J) T adj(J)^T * s for a symmetric T = (xx, xy, xz, yy, yz, zz) in physical coordinates:
+// M = adj(J) T (nine dot products from the six values), then the upper triangle of M adj(J)^T.  K = adj(J) as
+// jacobian() returns it (row = reference direction, column = physical direction). ----
+__device__ __forceinline__ void tensor_geometry(const double K[3][3], const double t[6], double s, double g[6])
+{
+  double M[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+  {
+    M[a][0] = K[a][0] * t[0] + K[a][1] * t[1] + K[a][2] * t[2];
+    M[a][1] = K[a][0] * t[1] + K[a][1] * t[3] + K[a][2] * t[4];
+    M[a][2] = K[a][0] * t[2] + K[a][1] * t[4] + K[a][2] * t[5];
+  }
+  g[0] = (M[0][0] * K[0][0] + M[0][1] * K[0][1] + M[0][2] * K[0][2]) * s;
+  g[1] = (M[1][0] * K[0][0] + M[1][1] * K[0][1] + M[1][2] * K[0][2]) * s;
+  g[2] = (M[2][0] * K[0][0] + M[2][1] * K[0][1] + M[2][2] * K[0][2]) * s;
+  g[3] = (M[1][0] * K[1][0] + M[1][1] * K[1][1] + M[1][2] * K[1][2]) * s;
+  g[4] = (M[2][0] * K[1][0] + M[2][1] * K[1][1] + M[2][2] * K[1][2]) * s;
+  g[5] = (M[2][0] * K[2][0] + M[2][1] * K[2][1] + M[2][2] * K[2][2]) * s;
 }
 } // namespace pmg

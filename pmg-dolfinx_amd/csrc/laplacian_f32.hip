@@ -80,12 +80,13 @@ __device__ __forceinline__ float2 gload32(const float2* p)
 }
 
 // G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]; kfield (optional) is
-// the nodal coefficient, folded in as in geometry_kernel, in double, before the one rounding
+// the nodal coefficient and ktensor (optional) the per-cell diffusion tensor, both folded in as in geometry_kernel, in
+// double, before the one rounding
 __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __restrict__ pcell,
                                     const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
                                     const double* __restrict__ dphi, const double* __restrict__ w,
                                     const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
-                                    float2* __restrict__ G)
+                                    const double* __restrict__ ktensor, float2* __restrict__ G)
 {
   const int nsq = nd * nd, nq = nsq * nd;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,12 +103,17 @@ __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __r
     double s = w[q] / detJ;
     if (kfield)
       s *= kfield[dofmap[(size_t)c * nq + q]];
-    g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-    g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-    g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-    g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-    g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-    g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+    if (ktensor)
+      tensor_geometry(K, ktensor + (size_t)c * 6, s, g);
+    else
+    {
+      g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
+      g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+      g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+      g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+      g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+      g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
+    }
   }
   const int a = q / nsq, b = (q - a * nsq) / nd, cc = q - a * nsq - b * nd;
   float2* o = G + (size_t)slot * 3 * nq + (size_t)cc * 3 * nsq + a * nd + b;
@@ -393,7 +399,8 @@ int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s)
   if (n > 0)
     geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
                                                                     op->geom_dofmap, op->dphi_geom, op->gweights,
-                                                                    op->kfield, op->dofmap, op->G32);
+                                                                    op->kfield, op->dofmap, op->ktensor,
+                                                                    op->G32);
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }

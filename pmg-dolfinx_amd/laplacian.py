@@ -165,9 +165,36 @@ class MatFreeLaplacian:
     def has_coefficient_field(self) -> bool:
         return bool(call("pmg_laplacian_has_coefficient_field", self._handle))
 
+    def set_coefficient_tensor(self, t):
+        """Per-cell diffusion tensor K (``pmg_laplacian_set_coefficient_tensor``): the operator becomes
+        -div(kappa[cell] * kq(x) * K[cell] grad u).  ``t`` is a float64 numpy array (uploaded here) or torch tensor
+        of shape ``(ncells, 6)``, one symmetric positive-definite tensor per local cell, ghost cells included, as
+        (xx, xy, xz, yy, yz, zz) in physical coordinates; or ``None`` to remove the tensor.  The library copies it.
+        The stored tensor, its float and affine forms and a computed inverse diagonal are rebuilt; not inside a
+        stream capture."""
+        import torch
+
+        if t is None:
+            call("pmg_laplacian_set_coefficient_tensor", self._handle, None, current_stream())
+            return
+        if not isinstance(t, (np.ndarray, torch.Tensor)):
+            raise TypeError("set_coefficient_tensor takes a float64 numpy array or torch tensor, or None")
+        if t.dtype not in (np.float64, torch.float64):
+            raise TypeError(f"the coefficient tensor must be float64, not {t.dtype}")
+        if tuple(t.shape) != (self.ncells, 6):
+            raise ValueError(f"the coefficient tensor has shape {tuple(t.shape)}, the operator needs "
+                             f"({self.ncells}, 6)")
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(t))
+        t = t.to(self.layout.device).contiguous()
+        call("pmg_laplacian_set_coefficient_tensor", self._handle, ptr(t), current_stream())
+
+    def has_coefficient_tensor(self) -> bool:
+        return bool(call("pmg_laplacian_has_coefficient_tensor", self._handle))
+
     def geometry(self):
         """G in the reference layout [ncells, nq, 6] (device tensor), as the kernels read it (with the
-        coefficient field, if one is set)."""
+        coefficient field and the coefficient tensor, if set)."""
         import torch
 
         N = (self.degree + 1) ** 3

@@ -25,11 +25,18 @@ def make_layout(lv, group=None, device="cuda", comm=None) -> Layout:
 class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
-                 node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None):
+                 node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None,
+                 kappa_tensor=None):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
         load vectors keep the per-cell ``kappa`` only (``pmg_laplacian_assemble_rhs``).
+
+        ``kappa_tensor`` (optional): a callable mapping cell centres ``[ncells, 3]`` (the mean of a cell's eight
+        vertices) to ``[ncells, 6]``, one symmetric positive-definite diffusion tensor per cell as
+        (xx, xy, xz, yy, yz, zz); it is set on every level's operator
+        (``MatFreeLaplacian.set_coefficient_tensor``) beside ``kappa_field``, before the diagonal and the eigenvalue
+        estimate.
 
         ``dirichlet`` (optional): a callable mapping dof coordinates ``[n, 3]`` to a boolean array; on every level
         the Dirichlet marker becomes the exterior dofs for which it is true (default: the whole boundary).  The rest
@@ -52,6 +59,10 @@ class PoissonHierarchy:
         self.kappa = torch.full((part.ncells,), float(kappa), dtype=torch.float64, device=dev)  # :190-193
         # node_order = "basix": the dofmaps are handed over as dolfinx would hold them (endpoints first per direction)
         self.node_order = node_order
+        ktensor = None
+        if kappa_tensor is not None:  # the cells are the same on every level
+            centres = part.xgeom[part.geom_dofmap].mean(axis=1)
+            ktensor = torch.from_numpy(np.ascontiguousarray(kappa_tensor(centres), dtype=np.float64)).to(dev)
         for P in self.orders:
             lv = part.level(P)
             if level_hook is not None:  # bench.py --corrupt-halo: a deliberately wrong halo plan for the gate's own test
@@ -73,6 +84,8 @@ class PoissonHierarchy:
                     kappa_field(part.dof_coordinates(P)), dtype=np.float64)))
                 op.set_coefficient_field(kq)
                 del kq
+            if ktensor is not None:
+                op.set_coefficient_tensor(ktensor)
             op.compute_diag_inverse()  # replaces :274-279
             self.levels.append(lv)
             self.layouts.append(layout)
