@@ -33,13 +33,17 @@
 // Roofline: HBM-bound, AI 0.85 (P=1) .. 2.05 (P=8) flop/B; algorithmic bytes per
 // cell 48N + 4N + 8 + 17U (model "storedG").
 //
-// One translation unit, five files (the fragments are included below, inside the anonymous namespace, in this order):
+// One translation unit, five files and a header.  stiffness_layer.hpp (a real header, shared with laplacian_f32.hip)
+// holds the layer march of the four apply kernels: fences, loads, the lane's table rows, the two halves of a layer, the
+// packed positions and the tensor stream.  The fragments are included below, inside the anonymous namespace, in this
+// order:
 //   geometry_kernels.hpp  layout of G (gflat, gpatch, gpos); geometry, export, diagonal and load-vector kernels
 //   stiffness_column.hpp  Shape<P> and its policies, write-back, diagnostic stamps, stiffness_column_kernel
 //   stiffness_chain.hpp   ChainShape<P>, stiffness_chain_kernel (P = 4)
 //   stiffness_restrict.hpp  stiffness_restrict_kernel: the apply fused with the restriction of r - A z
 //   laplacian.hip         the host side: launch plan, run_launches, the C ABI
 #include "laplacian.hpp"
+#include "stiffness_layer.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -106,6 +110,22 @@ bool streams_past_the_cache(long long tensor_bytes)
   return tensor_bytes > (128LL << 20);
 }
 
+// The (AFF, NT) instantiation of an apply kernel that an operator runs, chosen in one place: launch(AFF, NT) is called
+// with the two as std::bool_constant.  Cache policy: a tensor that is read once per application and is larger than the
+// Infinity Cache is streamed (nt), so that it does not displace x, y and the tables; a tensor that fits stays resident
+// between two applications under the default policy (streams_past_the_cache; profiles/kernel_tuning_r03.md).  The
+// affine mode reads no tensor: AFFINE_NT is the kernel's one instantiation for it.
+template <int P, bool AFFINE_NT, typename F>
+void apply_variant(pmg_laplacian op, F launch)
+{
+  if (op->geometry_mode == 1)
+    launch(std::true_type{}, std::bool_constant<AFFINE_NT>{});
+  else if (P >= NT_FROM && op->stream_policy)
+    launch(std::false_type{}, std::true_type{});
+  else
+    launch(std::false_type{}, std::false_type{});
+}
+
 template <int P>
 int launch_stiffness(pmg_laplacian op, const double* x, double* y, int first, int count,
                      int atomic_out, hipStream_t s)
@@ -121,24 +141,12 @@ int launch_stiffness(pmg_laplacian op, const double* x, double* y, int first, in
   const double2* G = op->G;
   if (op->batch_patches > 0 && op->geometry_mode == 0)
     G = batch_geometry(op, first, count, s); // :391-396
-  {
-    // Cache policy: a tensor that is read once per application and is larger than the Infinity Cache is streamed
-    // (nt), so that it does not displace x, y and the tables; a tensor that fits stays resident between two
-    // applications under the default policy (streams_past_the_cache; profiles/kernel_tuning_r03.md).  The affine mode
-    // reads no tensor.
-    const bool nt = P >= NT_FROM && op->geometry_mode != 1 && op->stream_policy;
-#define PMG_LAUNCH_COLUMN(AFF_, NT_)                                                                                \
-  stiffness_column_kernel<P, AFF_, NT_><<<count, Shape<P>::WTHREADS, 0, s>>>(                                         \
-      x, y, G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,  \
-      first, atomic_out)
-    if (op->geometry_mode == 1)
-      PMG_LAUNCH_COLUMN(true, (P >= NT_FROM)); // (only the y stores: as before)
-    else if (nt)
-      PMG_LAUNCH_COLUMN(false, true);
-    else
-      PMG_LAUNCH_COLUMN(false, false);
-#undef PMG_LAUNCH_COLUMN
-  }
+  apply_variant<P, (P >= NT_FROM)>(op, [&](auto aff, auto nt) { // (affine cells: nt is for the y stores)
+    constexpr bool AFF = decltype(aff)::value, NT = decltype(nt)::value;
+    stiffness_column_kernel<P, AFF, NT><<<count, Shape<P>::WTHREADS, 0, s>>>(
+        x, y, G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
+        first, atomic_out);
+  });
   op->launches++;
   return PMG_OK;
 }
@@ -295,18 +303,12 @@ int launch_stiffness_restrict(pmg_laplacian op, const TransferView& tv, const do
   constexpr int cm = RestrictShape<P, PC>::CM;
   PMG_REQUIRE(tv.cmax_m <= cm, "internal: a patch holds %d coarse dofs, the fused kernel %d", tv.cmax_m, cm);
   const RestrictLists R{tv.cpoff, tv.clmap_id, tv.cpdofs, tv.clmaps, tv.pmult, tv.M1};
-  const bool nt = P >= NT_FROM && op->geometry_mode != 1 && op->stream_policy;
-#define PMG_LAUNCH_FUSED(AFF_, NT_)                                                                                  \
-  stiffness_restrict_kernel<P, PC, AFF_, NT_><<<op->npatch, Shape<P>::WTHREADS, 0, s>>>(                             \
-      z, r, coarse, op->G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell,     \
-      op->kappa, op->D, R)
-  if (op->geometry_mode == 1)
-    PMG_LAUNCH_FUSED(true, false);
-  else if (nt)
-    PMG_LAUNCH_FUSED(false, true);
-  else
-    PMG_LAUNCH_FUSED(false, false);
-#undef PMG_LAUNCH_FUSED
+  apply_variant<P, false>(op, [&](auto aff, auto nt) {
+    constexpr bool AFF = decltype(aff)::value, NT = decltype(nt)::value;
+    stiffness_restrict_kernel<P, PC, AFF, NT><<<op->npatch, Shape<P>::WTHREADS, 0, s>>>(
+        z, r, coarse, op->G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell,
+        op->kappa, op->D, R);
+  });
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }

@@ -12,12 +12,15 @@
 // first FP32 use of the operator; it is never converted from the FP64 tensor (which may not be resident: batched
 // geometry).
 //
-// One kernel form for every degree: the column scheme of laplacian.hip without its build options -- a lane owns the
-// (a, b) column of a cell, keeps the column's values in registers and marches through the nd layers; the x and y
-// contractions pass one nd x nd slice through LDS, the z contraction stays in registers.  Half-width registers let
+// One kernel form for every degree: the column scheme of laplacian.hip -- a lane owns the (a, b) column of a cell,
+// keeps the column's values in registers and marches through the nd layers; the x and y contractions pass one nd x nd
+// slice through LDS, the z contraction stays in registers.  The layer march, the lane's table rows, the tensor stream (GD
+// layers deep here), the fences and the loads are the FP64 kernels' own, instantiated for float
+// (stiffness_layer.hpp).  Half-width registers let
 // every degree run eight wavefronts per workgroup where it has the items (P = 6: 49 of 64 lanes, P = 7: 64 of 64),
 // and P = 5 / P = 8 share one item of 7 / 3 cells between four wavefronts as the FP64 kernel does.
 #include "laplacian.hpp"
+#include "stiffness_layer.hpp"
 
 #include <algorithm>
 
@@ -53,31 +56,6 @@ struct Shape32
   static constexpr int MIN_WAVES = P <= 4 ? 6 : 1;
   static_assert(MAXM <= 65535, "patch positions are 16-bit");
 };
-
-__device__ __forceinline__ void wave_fence32()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// workgroup barrier that orders LDS only (no vmcnt drain: nothing passes through global memory inside the kernel)
-__device__ __forceinline__ void lds_barrier32()
-{
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-typedef float fvec2 __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ float2 gload32(const float2* p)
-{
-  if constexpr (NT)
-  {
-    fvec2 v = __builtin_nontemporal_load(reinterpret_cast<const fvec2*>(p));
-    return make_float2(v.x, v.y);
-  }
-  else
-    return *p;
-}
 
 // G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]; kfield (optional) is
 // the nodal coefficient and ktensor (optional) the per-cell diffusion tensor, both folded in as in geometry_kernel, in
@@ -133,6 +111,7 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
   using Sh = Shape32<P>;
   constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, NG = Sh::NG, WPC = Sh::WPC, WL = Sh::WL;
   constexpr int MAXM = Sh::MAXM, THREADS = Sh::THREADS, CW = Sh::CW, ITER = Sh::ITER, GD = Sh::GD;
+  constexpr bool SHARED = WPC > 1; // the item's wavefronts exchange their slices through workgroup barriers
   __shared__ float sD[ND * ND];
   __shared__ float sx[MAXM];
   __shared__ float sy[MAXM];
@@ -187,33 +166,20 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
     const int c = pcell[(size_t)p * K + i];
     skap[i] = (float)kappa[c >= 0 ? c : 0];
   }
-  lds_barrier32();
+  lds_barrier();
 
   const int wave = (t >> 6) / WPC, lane = (t & 63) + 64 * ((t >> 6) % WPC);
   const bool lane_ok = lane < WL;
   const int lw = lane_ok ? lane : WL - 1; // idle lanes shadow the last column (finite values, no contribution)
   const int cw = lw / NQ2, ab = lw - cw * NQ2;
   const int a = ab / ND, b = ab - a * ND;
-  float Da[ND], Db[ND], DTa[ND], DTb[ND]; // D[a][.], D[b][.], D[.][a], D[.][b]
-#pragma unroll
-  for (int mm = 0; mm < ND; ++mm)
-  {
-    Da[mm] = sD[a * ND + mm];
-    Db[mm] = sD[b * ND + mm];
-    DTa[mm] = sD[mm * ND + a];
-    DTb[mm] = sD[mm * ND + b];
-  }
+  LaneTables<float, ND> T;
+  T.fill((const __attribute__((address_space(3))) float*)sD, a, b);
   float* q_s = sq + wave * WL + cw * NQ2;
   float* gr_s = sgr + wave * WL + cw * NQ2;
   float* gs_s = sgs + wave * WL + cw * NQ2;
   // wavefronts that share an item exchange slices through workgroup barriers: all of them run the same item count
   const int items = WPC > 1 ? (((nc + CW - 1) / CW + NG - 1) / NG) * NG : (nc + CW - 1) / CW;
-  auto slice_sync = [] {
-    if constexpr (WPC > 1)
-      lds_barrier32();
-    else
-      wave_fence32();
-  };
   const uint16_t* lmb = lmaps + (size_t)table * (K * N);
   for (int it = wave; it < items; it += NG)
   {
@@ -224,17 +190,9 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
 #pragma unroll
     for (int k = 0; k < ND; ++k)
       l[k] = lmb[lmo + (unsigned)(k * NQ2)];
-    const float2* Gb = G + (size_t)p * K * 3 * N;
-    const unsigned Gs = (unsigned)(slotc * 3 * N + ab);
-    float2 gq[GD][3]; // layers 0 .. GD-1 in flight, slot k % GD refilled with layer k + GD once layer k is read
-#pragma unroll
-    for (int d = 0; d < GD; ++d)
-    {
-      const unsigned o = Gs + (unsigned)(d * 3 * NQ2);
-      gq[d][0] = gload32<NT>(Gb + o);
-      gq[d][1] = gload32<NT>(Gb + (o + NQ2));
-      gq[d][2] = gload32<NT>(Gb + (o + 2 * NQ2));
-    }
+    // layers 0 .. GD-1 in flight, slot k % GD refilled with layer k + GD once layer k is read
+    TensorStream<float2, ND, WL, false, false, 0, NT, GD> gs;
+    gs.prime(G + (size_t)p * K * 3 * N, (unsigned)(slotc * 3 * N + ab));
     // kappa multiplies the cell's input once (the operator is linear in it), as in the FP64 kernels
     const float kap = skap[slotc];
     float u[ND], Aq[ND];
@@ -247,46 +205,21 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
-      const float2 g01 = gq[k % GD][0], g23 = gq[k % GD][1], g45 = gq[k % GD][2];
-      if (k + GD < ND)
-      {
-        const unsigned o = Gs + (unsigned)((k + GD) * 3 * NQ2);
-        gq[k % GD][0] = gload32<NT>(Gb + o);
-        gq[k % GD][1] = gload32<NT>(Gb + (o + NQ2));
-        gq[k % GD][2] = gload32<NT>(Gb + (o + 2 * NQ2));
-      }
-      q_s[ab] = u[k];
-      slice_sync();
-      float qr = 0.0f, qs = 0.0f, qt = 0.0f;
-#pragma unroll
-      for (int mm = 0; mm < ND; ++mm)
-      {
-        qr += Da[mm] * q_s[mm * ND + b]; // d/dx
-        qs += Db[mm] * q_s[a * ND + mm]; // d/dy
-        qt += Dg[k * ND + mm] * u[mm];   // d/dz: registers, wave-uniform table entries
-      }
-      const float fr = g01.x * qr + g01.y * qs + g23.x * qt;
-      const float fs = g01.y * qr + g23.y * qs + g45.x * qt;
-      const float ft = g23.x * qr + g45.x * qs + g45.y * qt;
-      gr_s[ab] = fr;
-      gs_s[ab] = fs;
-      slice_sync();
-      float acc = 0.0f;
-#pragma unroll
-      for (int mm = 0; mm < ND; ++mm)
-      {
-        acc += DTa[mm] * gr_s[mm * ND + b];
-        acc += DTb[mm] * gs_s[a * ND + mm];
-        Aq[mm] += Dg[k * ND + mm] * ft;
-      }
-      Aq[k] += acc;
-      slice_sync();
+      float2 g01, g23, g45;
+      gs.take(k, 1.0f, g01, g23, g45);
+      float fr, fs, ft;
+      layer_forward<ND, false, SHARED>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, 1.0f, fr, fs, ft);
+      layer_backward<ND, false, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
     }
-    // every lane adds (lanes without a cell add an exact zero: no branch around the accumulation)
+    // every lane adds (lanes without a cell add an exact zero: no branch around the accumulation, and the sum is read
+    // ahead of the select, see the epilogue of stiffness_column_kernel)
     const bool contributes = lane_ok && slot < nc;
 #pragma unroll
     for (int k = 0; k < ND; ++k)
-      atomicAdd(&sy[l[k]], contributes ? Aq[k] : 0.0f); // ds_add_f32
+    {
+      const float Ak = Aq[k];
+      atomicAdd(&sy[l[k]], contributes ? Ak : 0.0f); // ds_add_f32
+    }
   }
   // write-back: sums of the non-Dirichlet dofs (store onto the earlier colours' values, or a float atomic in a merged
   // launch); the Dirichlet rows y = x by the first patch that holds them (src/laplacian.hpp:273-274).  The list is
@@ -300,7 +233,7 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
     const int i = tw + k * THREADS;
     mk[k] = pdofs[off + (i < M ? i : M - 1)];
   }
-  lds_barrier32();
+  lds_barrier();
 #pragma unroll
   for (int k = 0; k < ITER; ++k)
   {

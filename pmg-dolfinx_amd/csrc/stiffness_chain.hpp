@@ -1,5 +1,6 @@
 // Private fragment of laplacian.hip, included there and nowhere else (inside its anonymous namespace, after
-// stiffness_column.hpp): the chain form of the stiffness kernel.
+// stiffness_column.hpp): the chain form of the stiffness kernel.  Its layer march is the shared one of
+// stiffness_layer.hpp, in two parts with the refill of the kernel's own two-slot tensor stream between them.
 
 // ---- the hot kernel, chain form (round 4) ------------------------------------------------------
 //
@@ -211,15 +212,8 @@ __global__ void __launch_bounds__(ChainShape<P>::THREADS)
   }
   lds_barrier();
 
-  double Da[ND], Db[ND], DTa[ND], DTb[ND]; // D[a][.], D[b][.], D[.][a], D[.][b]
-#pragma unroll
-  for (int mm = 0; mm < ND; ++mm)
-  {
-    Da[mm] = sD[a * ND + mm];
-    Db[mm] = sD[b * ND + mm];
-    DTa[mm] = sD[mm * ND + a];
-    DTb[mm] = sD[mm * ND + b];
-  }
+  LaneTables<double, ND> T;
+  T.fill((const __attribute__((address_space(3))) double*)sD, a, b);
   double* q_s = ssl + wave * (3 * WL) + cw * NQ2;
   double* gr_s = q_s + WL;
   double* gs_s = q_s + 2 * WL;
@@ -252,42 +246,21 @@ __global__ void __launch_bounds__(ChainShape<P>::THREADS)
       for (int k = 0; k < ND; ++k)
       {
         const int s = k & 1;
-        q_s[ab] = u[k];
-        wave_fence();
-        double qr = 0.0, qs = 0.0, qt = 0.0;
-#pragma unroll
-        for (int mm = 0; mm < ND; ++mm)
-        {
-          qr += Da[mm] * slice_load<UNPAIRED>(q_s[mm * ND + b]); // d/dx: sum over a, :195-199
-          qs += Db[mm] * slice_load<UNPAIRED>(q_s[a * ND + mm]); // d/dy: sum over b, :206-210
-          qt += Dg[k * ND + mm] * u[mm];                         // d/dz: registers, uniform table, :214-218
-        }
-        const double2 g01 = gq[s][0], g23 = gq[s][1], g45 = gq[s][2];
-        const double fr = g01.x * qr + g01.y * qs + g23.x * qt; // :233 (kappa: in u, above)
-        const double fs = g01.y * qr + g23.y * qs + g45.x * qt; // :234
-        const double ft = g23.x * qr + g45.x * qs + g45.y * qt; // :235
+        double fr, fs, ft; // (kappa: in u, above)
+        layer_forward<ND, UNPAIRED, false>(k, u, T, Dg, q_s, a, b, ab, gq[s][0], gq[s][1], gq[s][2], 1.0, fr, fs, ft);
         if (k + 2 < ND)
           gfetch(s, gthis, k + 2);
         else
           gfetch(s, gnext, s); // the head of the wavefront's item in the next patch, into the slot it belongs in
-        gr_s[ab] = fr;
-        gs_s[ab] = fs;
-        wave_fence();
-        double acc = 0.0;
-#pragma unroll
-        for (int mm = 0; mm < ND; ++mm)
-        {
-          acc += DTa[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
-          acc += DTb[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
-          Aq[mm] += Dg[k * ND + mm] * ft;                           // :263-267
-        }
-        Aq[k] += acc;
-        wave_fence();
+        layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
       }
       const bool contributes = lane_ok && slot < nc; // lanes without a cell add an exact zero
 #pragma unroll
       for (int k = 0; k < ND; ++k)
-        atomicAdd(&sy[l[k]], contributes ? Aq[k] : 0.0); // :270,277 -- in LDS (ds_add_f64)
+      {
+        const double Ak = Aq[k]; // (read ahead of the select: see the column kernel's epilogue)
+        atomicAdd(&sy[l[k]], contributes ? Ak : 0.0); // :270,277 -- in LDS (ds_add_f64)
+      }
     }
     PMG_CSTAMP(2); // cell loop done
     dma_lists(c + 2); // (behind the last wait for the tensor, in front of the gather: see above)

@@ -1,6 +1,8 @@
 // Private fragment of laplacian.hip, included there and nowhere else (inside its anonymous namespace, after
 // geometry_kernels.hpp): Shape<P> and its policies, the write-back shared with the diagnostic stamps, and the column
-// form of the stiffness kernel.
+// form of the stiffness kernel.  The layer march, the lane's table rows, the tensor stream, the fences and the loads
+// are those of stiffness_layer.hpp, shared with the restrict, chain and FP32 kernels; what is written out here is the
+// gather, the cell loop and the transposition by identity (P = 5, its one user).
 
 template <int P>
 struct Shape
@@ -31,17 +33,6 @@ struct Shape
   static constexpr int WITER = (MAXM + WTHREADS - 1) / WTHREADS;
   static_assert(MAXM <= 65535, "patch positions are 16-bit");
 };
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains
-// the vector-memory counter (s_waitcnt vmcnt(0)), which would stall every wave on
-// the G loads issued at the top of the kernel; nothing in this kernel passes data
-// between threads through global memory, so LDS ordering is all that is needed
-// (cdna_hip_programming.md, "Pipelining across barriers").
-__device__ __forceinline__ void lds_barrier()
-{
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 
 // ---- write-back of a patch's sums, shared by the kernels below --------------------------------------------
 // Round 4, read at the ISA level: written as one loop "load the list entry, branch on it, store", the write-back was six
@@ -141,47 +132,7 @@ __device__ int g_stamp_capacity = 0; // workgroups the buffer has room for
 // A cell costs 4*nd LDS reads per point instead of 12*nd, the 1-D tables for the
 // lane's a and b sit in registers, and the layer-(k+1) slice of G is in flight
 // while layer k is computed.
-__device__ __forceinline__ void wave_fence()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Cache policy.  The G stream is read exactly once per application and is ~6x larger
-// than the MALL: it is loaded non-temporally (nt bit) so that it does not displace x, y,
-// the dof lists and the shared tables from L2 / MALL, and the write-back stores of y are
-// non-temporal as well.  Measured at P = 4, 64^3: 505 -> 475 us with nt stores, -> 430 us
-// with nt G loads on top; the sc0 / sc1 bits make no difference; nt on the x / y gathers
-// or on the dof lists is slower.
-// At P = 1 (8 quadrature points per cell, every dof shared by 8 cells) the default
-// policy is faster (1610 vs 1750 us at 256^3), so the hint starts at P = 2.
-constexpr int NT_FROM = 2;
-typedef double gvec2 __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ double2 gload(const double2* p)
-{
-  if constexpr (NT)
-  {
-    gvec2 v = __builtin_nontemporal_load(reinterpret_cast<const gvec2*>(p));
-    return make_double2(v.x, v.y);
-  }
-  else
-    return *p;
-}
-
-// Slice reads.  The compiler pairs neighbouring LDS reads into ds_read2_b64; issued one by one
-// (volatile LDS loads are not paired) the kernel is 7 % faster at P = 5 and 4 % at P = 8, unchanged at
-// P <= 4 and slower at P = 6, 7 (profiles/kernel_tuning_r02.md).
-typedef __attribute__((address_space(3))) volatile double lds_vdouble;
-template <bool UNPAIRED>
-__device__ __forceinline__ double slice_load(double& v)
-{
-  if constexpr (UNPAIRED)
-    return *(lds_vdouble*)&v;
-  else
-    return v;
-}
+// P = 5 and P = 8 read their slices one by one (slice_load, stiffness_layer.hpp)
 constexpr bool unpaired_slice_reads(int P) { return P == 5 || P == 8; }
 
 // degrees whose kernel keeps the patch's dof list in LDS for the write-back (4 bytes per patch dof).  Round 4, two
@@ -226,6 +177,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   constexpr int WL = CW * NQ2; // columns of one item (a wave, or WPC waves sharing a cell)
   // NT: streaming cache policy for G and the y write-back (chosen per operator, launch_stiffness)
   constexpr bool UNPAIRED = unpaired_slice_reads(P);
+  constexpr bool SHARED = WPC > 1; // the item's wavefronts exchange their slices through workgroup barriers
   __shared__ double sD[ND * ND];
   __shared__ double skap[K];
   __shared__ double sx[MAXM];
@@ -236,7 +188,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   constexpr bool LIST_IN_LDS = list_in_lds(P);
   __shared__ uint32_t sm[LIST_IN_LDS ? MAXM : 1];
   __shared__ double sq[NG * WL];
-  __shared__ double sgr[NG * WL + 1]; // (+ 1: a spare element nothing writes any more; it is part of the LDS size)
+  __shared__ double sgr[NG * WL];
   __shared__ double sgs[NG * WL];
   // flat G layout: one layer of the item, as loaded (NJ x 64 double2), for the hand-over to the lanes
   constexpr bool FLAT = !AFF && WPC == 1 && gflat(ND);
@@ -308,18 +260,8 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   const int cw = lw / NQ2;          // cell of this lane inside the wave item
   const int ab = lw - cw * NQ2;     // column: a = x index, b = y index
   const int a = ab / ND, b = ab - a * ND;
-  // The lane's rows / columns of the 1-D table, in registers (4 nd doubles; re-reading them from LDS
-  // in every layer frees the registers for one more wave per SIMD but is 15 % slower at every degree,
-  // profiles/kernel_tuning_r02.md)
-  double Da[ND], Db[ND], DTa[ND], DTb[ND]; // D[a][.], D[b][.], D[.][a], D[.][b]
-#pragma unroll
-  for (int mm = 0; mm < ND; ++mm)
-  {
-    Da[mm] = sD[a * ND + mm];
-    Db[mm] = sD[b * ND + mm];
-    DTa[mm] = sD[mm * ND + a];
-    DTb[mm] = sD[mm * ND + b];
-  }
+  LaneTables<double, ND> T;
+  T.fill((const __attribute__((address_space(3))) double*)sD, a, b);
   // the identity's constants (see transposes_by_identity): rho, 1 / rho, 2 D_ii for the lane's a and b
   double rho_a = 1.0, irho_a = 1.0, d2a = 0.0, rho_b = 1.0, irho_b = 1.0, d2b = 0.0;
   if constexpr (IDT)
@@ -335,14 +277,8 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   double* q_s = sq + wave * WL + cw * NQ2;  // this cell's slices
   double* gr_s = sgr + wave * WL + cw * NQ2;
   double* gs_s = sgs + wave * WL + cw * NQ2;
-  double* gr_w = gr_s + ab; // where the lane writes its x flux
+  double* gr_w = gr_s + ab; // where the lane writes its x flux (the identity path, P = 5)
   const int items = WPC > 1 ? (((nc + CW - 1) / CW + NG - 1) / NG) * NG : (nc + CW - 1) / CW;
-  auto slice_sync = [] {
-    if constexpr (WPC > 1)
-      lds_barrier();
-    else
-      wave_fence();
-  };
 
   for (int it = wave; it < items; it += NG)
   {
@@ -356,51 +292,19 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
     // behind a wait that drains the memory counter)
     const uint16_t* lmb = lmaps + (size_t)table * (K * N);
     const unsigned lmo = (unsigned)(slotc * N + ab);
-    constexpr int GPS = NQ2; // stride between the three pairs of a layer
-    const double2* Gb = G + (size_t)p * ((long long)K * 3 * N);
-    const unsigned Gs = (unsigned)(slotc * 3 * N + ab);
     int l[ND];
 #pragma unroll
     for (int k = 0; k < ND; ++k)
       l[k] = lmb[lmo + (unsigned)(k * NQ2)];
-    // storedG: G layers 0 .. GD-1 in flight (empty slots hold zeros).
-    // affine cells (AFF): G_q = w_a w_b w_c * Gc with one constant tensor Gc per cell.
-    constexpr int GD = 1; // G layers in flight per wave (deeper costs registers, i.e. resident waves: no gain)
-    double2 gq[AFF ? 1 : GD][3];
-    double2 gfl[FLAT ? NJ : 1]; // flat layout: the next layer as loaded
-    // (only used when FLAT; the item index is wave-uniform: a scalar base plus 32-bit lane offsets)
-    const double2* Gi = G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS;
-    int eo[FLAT ? NJ : 1]; // the lane's elements of a layer (clamped: the tail lanes re-read the last one)
-    if constexpr (FLAT)
-    {
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj)
-        eo[jj] = lane + 64 * jj < FL ? lane + 64 * jj : FL - 1;
-    }
-    double gc[6] = {0, 0, 0, 0, 0, 0};
+    // the tensor, one layer ahead of the march (affine cells: G_q = w_a w_b w_c * Gc, one constant tensor Gc per cell)
+    TensorStream<double2, ND, WL, AFF, FLAT, LS, NT, 1> gs;
     if constexpr (AFF)
-    {
-      const double* ga = Gaff + ((size_t)p * K + slotc) * 6;
-#pragma unroll
-      for (int d = 0; d < 6; ++d)
-        gc[d] = ga[d];
-    }
-    else if constexpr (FLAT)
-    {
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj)
-        gfl[jj] = gload<NT>(Gi + eo[jj]);
-    }
+      gs.prime_affine(Gaff + ((size_t)p * K + slotc) * 6, 1.0);
+    else if constexpr (FLAT) // (the item index is wave-uniform: a scalar base plus 32-bit lane offsets)
+      gs.prime_flat(G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS,
+                    sgb + wave * (NJ * 64), lane, lw);
     else
-    {
-#pragma unroll
-      for (int d = 0; d < GD; ++d)
-      {
-        gq[d][0] = gload<NT>(Gb + (Gs + (unsigned)(d * 3 * GPS)));
-        gq[d][1] = gload<NT>(Gb + (Gs + (unsigned)(d * 3 * GPS + GPS)));
-        gq[d][2] = gload<NT>(Gb + (Gs + (unsigned)(d * 3 * GPS + 2 * GPS)));
-      }
-    }
+      gs.prime(G + (size_t)p * ((long long)K * 3 * N), (unsigned)(slotc * 3 * N + ab));
     // (identity modes: kappa multiplies the cell's INPUT once -- the operator is linear in it, same value to rounding --
     // and the positions are held two to a register through the layer loop)
     const double kap = IDT ? 1.0 : skap[slotc];
@@ -416,110 +320,47 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
     }
     unsigned lp[IDT ? (ND + 1) / 2 : 1];
     if constexpr (IDT)
-    {
-#pragma unroll
-      for (int k = 0; k < ND; k += 2)
-        lp[k / 2] = (unsigned)l[k] | (k + 1 < ND ? (unsigned)l[k + 1] << 16 : 0u);
-#pragma unroll
-      for (int j = 0; j < (ND + 1) / 2; ++j)
-        asm volatile("" : "+v"(lp[j])); // (opaque: the unpacked values are not kept alongside)
-    }
+      pack_positions(l, lp);
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
       double2 g01, g23, g45;
-      if constexpr (AFF)
-      {
-        const double sc = wab * W1[k]; // w_a w_b w_c; W1[k] is wave-uniform (scalar load)
-        g01 = make_double2(sc * gc[0], sc * gc[1]);
-        g23 = make_double2(sc * gc[2], sc * gc[3]);
-        g45 = make_double2(sc * gc[4], sc * gc[5]);
-      }
-      else if constexpr (FLAT)
-      {
-        double2* gb = sgb + wave * (NJ * 64);
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj)
-          gb[lane + 64 * jj] = gfl[jj]; // as loaded ...
-        wave_fence();
-        g01 = gb[lw]; // ... and as used: [pair][cell of the item][column]
-        g23 = gb[WL + lw];
-        g45 = gb[2 * WL + lw];
-        if (k + 1 < ND)
-        {
-#pragma unroll
-          for (int jj = 0; jj < NJ; ++jj)
-            gfl[jj] = gload<NT>(Gi + (k + 1) * LS + eo[jj]);
-        }
-      }
-      else
-      {
-        g01 = gq[k % GD][0];
-        g23 = gq[k % GD][1];
-        g45 = gq[k % GD][2];
-        if (k + GD < ND) // refill the slot with layer k + GD
-        {
-          gq[k % GD][0] = gload<NT>(Gb + (Gs + (unsigned)((k + GD) * 3 * GPS)));
-          gq[k % GD][1] = gload<NT>(Gb + (Gs + (unsigned)((k + GD) * 3 * GPS + GPS)));
-          gq[k % GD][2] = gload<NT>(Gb + (Gs + (unsigned)((k + GD) * 3 * GPS + 2 * GPS)));
-        }
-      }
-      q_s[ab] = u[k];
-      slice_sync();
-      double qr = 0.0, qs = 0.0, qt = 0.0;
-#pragma unroll
-      for (int mm = 0; mm < ND; ++mm)
-      {
-        qr += Da[mm] * slice_load<UNPAIRED>(q_s[mm * ND + b]);  // d/dx: sum over a, :195-199
-        qs += Db[mm] * slice_load<UNPAIRED>(q_s[a * ND + mm]);  // d/dy: sum over b, :206-210
-        qt += Dg[k * ND + mm] * u[mm];    // d/dz: registers, uniform table, :214-218
-      }
-      const double fr = kap * (g01.x * qr + g01.y * qs + g23.x * qt); // :233
-      const double fs = kap * (g01.y * qr + g23.y * qs + g45.x * qt); // :234
-      const double ft = kap * (g23.x * qr + g45.x * qs + g45.y * qt); // :235
-      double acc = 0.0;
+      gs.take(k, AFF ? wab * W1[k] : 0.0, g01, g23, g45); // w_a w_b w_c; W1[k] is wave-uniform (scalar load)
+      double fr, fs, ft;
+      layer_forward<ND, UNPAIRED, SHARED>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, kap, fr, fs, ft);
       if constexpr (IDT)
       {
         // the transposes as forward contractions of the scaled fluxes (see transposes_by_identity)
         *gr_w = fr * irho_a;
         gs_s[ab] = fs * irho_b;
-        slice_sync();
+        slice_sync<SHARED>();
         double sx_ = 0.0, sy_ = 0.0;
 #pragma unroll
         for (int mm = 0; mm < ND; ++mm)
         {
-          sx_ += Da[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
-          sy_ += Db[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
-          Aq[mm] += Dg[k * ND + mm] * ft;     // :263-267
+          sx_ += T.Da[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
+          sy_ += T.Db[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
+          Aq[mm] += Dg[k * ND + mm] * ft;                            // :263-267
         }
-        acc = (d2a * fr + d2b * fs) - (rho_a * sx_ + rho_b * sy_);
+        Aq[k] += (d2a * fr + d2b * fs) - (rho_a * sx_ + rho_b * sy_);
+        slice_sync<SHARED>();
       }
       else
-      {
-        gr_s[ab] = fr;
-        gs_s[ab] = fs;
-        slice_sync();
-#pragma unroll
-        for (int mm = 0; mm < ND; ++mm)
-        {
-          acc += DTa[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
-          acc += DTb[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
-          Aq[mm] += Dg[k * ND + mm] * ft;     // :263-267
-        }
-      }
-      Aq[k] += acc;
-      slice_sync();
+        layer_backward<ND, UNPAIRED, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
     }
     // Every lane adds (no branch: a conditional here lets the compiler sink the
     // whole accumulation into it and keep every layer's operands live); lanes
     // without a cell (idle lanes, slots past the patch's cells -- their indices
-    // were clamped onto a real slot) add an exact zero.
+    // were clamped onto a real slot) add an exact zero.  The sum is read AHEAD of the select: written
+    // `contributes ? Aq[k] : 0.0` the read itself is conditional, and since the layer functions take Aq by reference
+    // it stays a branch until they are inlined -- into which the accumulation is then sunk (spills at P = 4, 5 affine).
     const bool contributes = lane_ok && slot < nc;
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
-      const int lk = IDT ? (int)((lp[k / 2] >> (16 * (k & 1))) & 0xffffu) : l[k];
-      atomicAdd(&sy[lk], contributes ? Aq[k] : 0.0); // :270,277 -- in LDS (ds_add_f64)
+      const int lk = IDT ? (int)packed_position(lp, k) : l[k];
+      const double Ak = Aq[k];
+      atomicAdd(&sy[lk], contributes ? Ak : 0.0); // :270,277 -- in LDS (ds_add_f64)
     }
   }
   // ---- write back (plain stores; the accumulator started from the earlier colours' y)

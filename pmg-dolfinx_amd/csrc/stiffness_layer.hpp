@@ -1,0 +1,276 @@
+// The layer march of the stiffness apply, defined once for its four kernels: stiffness_column_kernel
+// (stiffness_column.hpp), stiffness_restrict_kernel (stiffness_restrict.hpp), stiffness_chain_kernel
+// (stiffness_chain.hpp) and stiffness_f32_kernel (laplacian_f32.hip).
+//
+// A lane owns the column of nd points above (a, b) of a cell and keeps it in registers.  One layer k of the march:
+// write the slice u(., ., k), contract x and y through LDS and z in registers, form the three fluxes from the six
+// tensor entries, contract back, accumulate.  The scalar type T is double or float, T2 the matching pair.
+//
+// Everything here is forced inline into the kernel that calls it: the callers' register allocations were tuned
+// against measured spills.  Against the text written out in each kernel, every kernel keeps 0 bytes of scratch and its
+// occupancy; the instruction order differs in all of them and a few register counts move (affine column kernels at
+// P = 4, 6, 7: 6 VGPRs more; P = 8 stored: 2 fewer).  The table and the timings are in profiles/layer_march.md.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+namespace pmg
+{
+// ---- synchronisation of a slice exchange ----------------------------------------------------------------------
+// LDS executes a wavefront's instructions in order: where one wavefront owns the slices a compiler fence is all the
+// exchange needs, no s_barrier and no waitcnt.
+__device__ __forceinline__ void wave_fence()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains
+// the vector-memory counter (s_waitcnt vmcnt(0)), which would stall every wave on
+// the G loads issued at the top of the kernel; nothing in these kernels passes data
+// between threads through global memory, so LDS ordering is all that is needed
+// (cdna_hip_programming.md, "Pipelining across barriers").
+__device__ __forceinline__ void lds_barrier()
+{
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// SHARED: several wavefronts share the item and exchange its slices through workgroup barriers
+template <bool SHARED>
+__device__ __forceinline__ void slice_sync()
+{
+  if constexpr (SHARED)
+    lds_barrier();
+  else
+    wave_fence();
+}
+
+// ---- loads ----------------------------------------------------------------------------------------------------
+// Cache policy.  The G stream is read exactly once per application and is ~6x larger
+// than the MALL: it is loaded non-temporally (nt bit) so that it does not displace x, y,
+// the dof lists and the shared tables from L2 / MALL, and the write-back stores of y are
+// non-temporal as well.  Measured at P = 4, 64^3: 505 -> 475 us with nt stores, -> 430 us
+// with nt G loads on top; the sc0 / sc1 bits make no difference; nt on the x / y gathers
+// or on the dof lists is slower.
+// At P = 1 (8 quadrature points per cell, every dof shared by 8 cells) the default
+// policy is faster (1610 vs 1750 us at 256^3), so the hint starts at P = 2.
+constexpr int NT_FROM = 2;
+template <typename T2>
+struct scalar_of;
+template <>
+struct scalar_of<double2>
+{
+  using type = double;
+};
+template <>
+struct scalar_of<float2>
+{
+  using type = float;
+};
+template <bool NT, typename T2> // T2: double2 or float2
+__device__ __forceinline__ T2 gload(const T2* p)
+{
+  if constexpr (NT)
+  {
+    typedef typename scalar_of<T2>::type vec2 __attribute__((ext_vector_type(2)));
+    vec2 v = __builtin_nontemporal_load(reinterpret_cast<const vec2*>(p));
+    return T2(v.x, v.y);
+  }
+  else
+    return *p;
+}
+
+// Slice reads.  The compiler pairs neighbouring LDS reads into ds_read2_b64; issued one by one
+// (volatile LDS loads are not paired) the FP64 kernel is 7 % faster at P = 5 and 4 % at P = 8, unchanged at
+// P <= 4 and slower at P = 6, 7 (profiles/kernel_tuning_r02.md).
+template <bool UNPAIRED, typename T>
+__device__ __forceinline__ T slice_load(T& v)
+{
+  if constexpr (UNPAIRED)
+    return *(__attribute__((address_space(3))) volatile T*)&v;
+  else
+    return v;
+}
+
+// ---- the lane's rows / columns of the 1-D table, in registers ---------------------------------------------------
+// (4 nd values; re-reading them from LDS in every layer frees the registers for one more wave per SIMD but is 15 %
+// slower at every degree, profiles/kernel_tuning_r02.md)
+template <typename T, int ND>
+struct LaneTables
+{
+  T Da[ND], Db[ND], DTa[ND], DTb[ND]; // D[a][.], D[b][.], D[.][a], D[.][b]
+  // sD: the LDS copy of D (typed as such: the index arithmetic of an LDS address is 32-bit)
+  __device__ __forceinline__ void fill(const __attribute__((address_space(3))) T* sD, int a, int b)
+  {
+#pragma unroll
+    for (int mm = 0; mm < ND; ++mm)
+    {
+      Da[mm] = sD[a * ND + mm];
+      Db[mm] = sD[b * ND + mm];
+      DTa[mm] = sD[mm * ND + a];
+      DTb[mm] = sD[mm * ND + b];
+    }
+  }
+};
+
+// ---- one layer --------------------------------------------------------------------------------------------------
+// Two parts, because the chain kernel issues its tensor refill between them.  q_s / gr_s / gs_s are the cell's three
+// nd x nd slices in LDS, Dg the 1-D table in global memory: its entries in row k are wave-uniform (scalar loads).
+//
+// Forward: u(., ., k) into the slice; qr, qs, qt; the three fluxes times `scale`.
+template <int ND, bool UNPAIRED, bool SHARED, typename T, typename T2>
+__device__ __forceinline__ void layer_forward(int k, const T (&u)[ND], const LaneTables<T, ND>& D,
+                                              const T* Dg, T* q_s, int a, int b, int ab, const T2& g01,
+                                              const T2& g23, const T2& g45, T scale, T& fr, T& fs, T& ft)
+{
+  q_s[ab] = u[k];
+  slice_sync<SHARED>();
+  T qr = 0, qs = 0, qt = 0;
+#pragma unroll
+  for (int mm = 0; mm < ND; ++mm)
+  {
+    qr += D.Da[mm] * slice_load<UNPAIRED>(q_s[mm * ND + b]); // d/dx: sum over a, src/laplacian.hpp:195-199
+    qs += D.Db[mm] * slice_load<UNPAIRED>(q_s[a * ND + mm]); // d/dy: sum over b, :206-210
+    qt += Dg[k * ND + mm] * u[mm];                           // d/dz: registers, uniform table, :214-218
+  }
+  fr = scale * (g01.x * qr + g01.y * qs + g23.x * qt); // :233
+  fs = scale * (g01.y * qr + g23.y * qs + g45.x * qt); // :234
+  ft = scale * (g23.x * qr + g45.x * qs + g45.y * qt); // :235
+}
+
+// Backward: the x and y fluxes into their slices, the two transposed contractions, the z one in registers.
+template <int ND, bool UNPAIRED, bool SHARED, typename T>
+__device__ __forceinline__ void layer_backward(int k, T fr, T fs, T ft, const LaneTables<T, ND>& D,
+                                               const T* Dg, T* gr_s, T* gs_s, int a, int b, int ab,
+                                               T (&Aq)[ND])
+{
+  gr_s[ab] = fr;
+  gs_s[ab] = fs;
+  slice_sync<SHARED>();
+  T acc = 0;
+#pragma unroll
+  for (int mm = 0; mm < ND; ++mm)
+  {
+    acc += D.DTa[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
+    acc += D.DTb[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
+    Aq[mm] += Dg[k * ND + mm] * ft;                             // :263-267
+  }
+  Aq[k] += acc;
+  slice_sync<SHARED>();
+}
+
+// ---- patch positions, two to a register -------------------------------------------------------------------------
+// Positions in a patch list are 16-bit.  Where a kernel needs a column's positions again behind the layer loop it
+// holds them packed through it, and opaque, so that the unpacked values are not kept alongside.
+template <int N>
+__device__ __forceinline__ void pack_positions(const int (&l)[N], unsigned (&lp)[(N + 1) / 2])
+{
+#pragma unroll
+  for (int k = 0; k < N; k += 2)
+    lp[k / 2] = (unsigned)l[k] | (k + 1 < N ? (unsigned)l[k + 1] << 16 : 0u);
+#pragma unroll
+  for (int j = 0; j < (N + 1) / 2; ++j)
+    asm volatile("" : "+v"(lp[j]));
+}
+__device__ __forceinline__ unsigned packed_position(const unsigned* lp, int k)
+{
+  return (lp[k / 2] >> (16 * (k & 1))) & 0xffffu;
+}
+
+// ---- the tensor stream of the column and restrict kernels: one layer ahead of the march ---------------------------
+// Three forms.  Default layout: the lane's three pairs of layers 0 .. GD-1 in flight in registers, slot k % GD
+// refilled with layer k + GD once layer k is taken.  Flat layout (FLAT, P = 2): the item's next layer as loaded,
+// NJ x 64 pairs with a layer stride of LS, handed over to the lanes through `gb` in LDS.  Affine cells (AFF):
+// G_q = w_a w_b w_c Gc with one constant tensor Gc per cell, no stream.
+template <typename T2, int ND, int WL, bool AFF, bool FLAT, int LS, bool NT, int GD>
+struct TensorStream
+{
+  using T = typename scalar_of<T2>::type;
+  static constexpr int GPS = ND * ND; // stride between the three pairs of a layer
+  static constexpr int FL = 3 * WL, NJ = (FL + 63) / 64;
+  T2 gq[AFF || FLAT ? 1 : GD][3];
+  T2 gfl[FLAT ? NJ : 1]; // flat layout: the next layer as loaded
+  int eo[FLAT ? NJ : 1]; // the lane's elements of a layer (clamped: the tail lanes re-read the last one)
+  T gc[AFF ? 6 : 1];
+  const T2* base;    // scalar base: the patch (default layout) or the item (flat layout)
+  unsigned lane_off; // default layout: the lane's (layer 0, pair 0) as a 32-bit offset (a 64-bit per-lane pointer
+                     // costs two registers, and a spilled one is reloaded behind a wait that drains the memory counter)
+  T2* gb;            // flat layout: the wavefront's NJ x 64 pairs in LDS
+  int lane, lw;      // flat layout: the lane, and the column it works on
+
+  // default layout: request layers 0 .. GD-1
+  __device__ __forceinline__ void prime(const T2* patch, unsigned lane_off_)
+  {
+    static_assert(!AFF && !FLAT);
+    base = patch;
+    lane_off = lane_off_;
+#pragma unroll
+    for (int d = 0; d < GD; ++d)
+      fetch(d, d);
+  }
+  // flat layout: request layer 0 of the item
+  __device__ __forceinline__ void prime_flat(const T2* item, T2* gb_, int lane_, int lw_)
+  {
+    static_assert(FLAT);
+    base = item;
+    gb = gb_;
+    lane = lane_;
+    lw = lw_;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj)
+      eo[jj] = lane + 64 * jj < FL ? lane + 64 * jj : FL - 1;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj)
+      gfl[jj] = gload<NT>(base + eo[jj]);
+  }
+  // affine cells: the cell's constant tensor times `fold`
+  __device__ __forceinline__ void prime_affine(const T* ga, T fold)
+  {
+    static_assert(AFF);
+#pragma unroll
+    for (int d = 0; d < 6; ++d)
+      gc[d] = fold * ga[d];
+  }
+  __device__ __forceinline__ void fetch(int slot, int layer)
+  {
+    gq[slot][0] = gload<NT>(base + (lane_off + (unsigned)(layer * 3 * GPS)));
+    gq[slot][1] = gload<NT>(base + (lane_off + (unsigned)(layer * 3 * GPS + GPS)));
+    gq[slot][2] = gload<NT>(base + (lane_off + (unsigned)(layer * 3 * GPS + 2 * GPS)));
+  }
+  // layer k's three pairs (affine cells: times `sc`), and the refill behind them
+  __device__ __forceinline__ void take(int k, T sc, T2& g01, T2& g23, T2& g45)
+  {
+    if constexpr (AFF)
+    {
+      g01.x = sc * gc[0], g01.y = sc * gc[1];
+      g23.x = sc * gc[2], g23.y = sc * gc[3];
+      g45.x = sc * gc[4], g45.y = sc * gc[5];
+    }
+    else if constexpr (FLAT)
+    {
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj)
+        gb[lane + 64 * jj] = gfl[jj]; // as loaded ...
+      wave_fence();
+      g01 = gb[lw]; // ... and as used: [pair][cell of the item][column]
+      g23 = gb[WL + lw];
+      g45 = gb[2 * WL + lw];
+      if (k + 1 < ND)
+      {
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj)
+          gfl[jj] = gload<NT>(base + (k + 1) * LS + eo[jj]);
+      }
+    }
+    else
+    {
+      g01 = gq[k % GD][0];
+      g23 = gq[k % GD][1];
+      g45 = gq[k % GD][2];
+      if (k + GD < ND) // refill the slot with layer k + GD
+        fetch(k % GD, k + GD);
+    }
+  }
+};
+} // namespace pmg

@@ -10,8 +10,9 @@
 // launch.  On Dirichlet rows the apply's rule is q = z (stiffness_column.hpp, patch_write_back), so their share is
 // (r - z) / mult and the cell's product is dropped there.
 //
-// The gather, the cell loop, the layer march and the G pipeline are those of stiffness_column_kernel (WPC == 1 shapes
-// without the transposition identity); `sy` holds the residual shares instead of the output sums.  Behind the layer
+// The gather and the cell loop follow stiffness_column_kernel (WPC == 1 shapes without the transposition identity); the
+// layer march, the lane's table rows, the tensor stream and the packed positions are the shared ones of
+// stiffness_layer.hpp.  `sy` holds the residual shares instead of the output sums.  Behind the layer
 // loop the lane owns w(a, b, .) = share - A_cell z of its column: z is contracted in registers with the 1-D
 // interpolation table M1 (wave-uniform entries), x and y through the wave's slice arrays, and the (PC + 1)^3 results
 // are added to an LDS accumulator over the patch's coarse dofs, which goes to the coarse vector with one atomic per
@@ -148,15 +149,8 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
   const int cw = lw / NQ2;
   const int ab = lw - cw * NQ2;
   const int a = ab / ND, b = ab - a * ND;
-  double Da[ND], Db[ND], DTa[ND], DTb[ND];
-#pragma unroll
-  for (int mm = 0; mm < ND; ++mm)
-  {
-    Da[mm] = sD[a * ND + mm];
-    Db[mm] = sD[b * ND + mm];
-    DTa[mm] = sD[mm * ND + a];
-    DTb[mm] = sD[mm * ND + b];
-  }
+  LaneTables<double, ND> T;
+  T.fill((const __attribute__((address_space(3))) double*)sD, a, b);
   double* q_s = ssl + wave * WL + cw * NQ2; // this cell's slices
   double* gr_s = q_s + NG * WL;
   double* gs_s = q_s + 2 * NG * WL;
@@ -178,9 +172,6 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
     const int slotc = slot < K ? slot : K - 1;
     const uint16_t* lmb = lmaps + (size_t)table * (K * N);
     const unsigned lmo = (unsigned)(slotc * N + ab);
-    constexpr int GPS = NQ2;
-    const double2* Gb = G + (size_t)p * ((long long)K * 3 * N);
-    const unsigned Gs = (unsigned)(slotc * 3 * N + ab);
     int l[ND];
 #pragma unroll
     for (int k = 0; k < ND; ++k)
@@ -191,47 +182,26 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
     coarse_point(ab, ic, jc, NDC);
     const unsigned clo = (unsigned)(slotc * NC + (ic * NDC + jc) * NDC);
     // (held two to a register through the layer loop, and opaque, so that the unpacked values are not kept alongside)
+    int lc[NDC];
+#pragma unroll
+    for (int k = 0; k < NDC; ++k)
+      lc[k] = clb[clo + (unsigned)k];
     unsigned lcp[(NDC + 1) / 2];
-#pragma unroll
-    for (int k = 0; k < NDC; k += 2)
-      lcp[k / 2] = (unsigned)clb[clo + (unsigned)k] | (k + 1 < NDC ? (unsigned)clb[clo + (unsigned)(k + 1)] << 16 : 0u);
-#pragma unroll
-    for (int j = 0; j < (NDC + 1) / 2; ++j)
-      asm volatile("" : "+v"(lcp[j]));
-    double2 gq[3];
-    double2 gfl[FLAT ? NJ : 1];
-    const double2* Gi = G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS;
-    int eo[FLAT ? NJ : 1];
-    if constexpr (FLAT)
-    {
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj)
-        eo[jj] = lane + 64 * jj < FL ? lane + 64 * jj : FL - 1;
-    }
-    double gc[6] = {0, 0, 0, 0, 0, 0};
+    pack_positions(lc, lcp);
+    TensorStream<double2, ND, WL, AFF, FLAT, LS, NT, 1> gs;
     if constexpr (AFF)
     {
-      const double* ga = Gaff + ((size_t)p * K + slotc) * 6;
-      // (kappa and the column's weights w_a w_b folded into the cell's constant tensor: same value to rounding)
+      // (kappa and the column's weights w_a w_b folded into the cell's constant tensor: same value to rounding; the
+      // layer's weight w_c scales the three fluxes)
       int av, bv;
       coarse_point(ab, av, bv, ND);
-      const double wab = skap[slotc] * (sW[av] * sW[bv]);
-#pragma unroll
-      for (int d = 0; d < 6; ++d)
-        gc[d] = wab * ga[d];
+      gs.prime_affine(Gaff + ((size_t)p * K + slotc) * 6, skap[slotc] * (sW[av] * sW[bv]));
     }
     else if constexpr (FLAT)
-    {
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj)
-        gfl[jj] = gload<NT>(Gi + eo[jj]);
-    }
+      gs.prime_flat(G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS,
+                    sgb + wave * (NJ * 64), lane, lw);
     else
-    {
-      gq[0] = gload<NT>(Gb + Gs);
-      gq[1] = gload<NT>(Gb + (Gs + (unsigned)GPS));
-      gq[2] = gload<NT>(Gb + (Gs + (unsigned)(2 * GPS)));
-    }
+      gs.prime(G + (size_t)p * ((long long)K * 3 * N), (unsigned)(slotc * 3 * N + ab));
     const double kap = AFF ? 1.0 : skap[slotc];
     double u[ND], Aq[ND];
 #pragma unroll
@@ -242,78 +212,16 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
     }
     // (the fine positions as well: the epilogue needs them again)
     unsigned lp[(ND + 1) / 2];
-#pragma unroll
-    for (int k = 0; k < ND; k += 2)
-      lp[k / 2] = (unsigned)l[k] | (k + 1 < ND ? (unsigned)l[k + 1] << 16 : 0u);
-#pragma unroll
-    for (int j = 0; j < (ND + 1) / 2; ++j)
-      asm volatile("" : "+v"(lp[j]));
+    pack_positions(l, lp);
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
       double2 g01, g23, g45;
-      if constexpr (AFF)
-      {
-        g01 = make_double2(gc[0], gc[1]); // (the layer's weight w_c scales the three fluxes below)
-        g23 = make_double2(gc[2], gc[3]);
-        g45 = make_double2(gc[4], gc[5]);
-      }
-      else if constexpr (FLAT)
-      {
-        double2* gb = sgb + wave * (NJ * 64);
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj)
-          gb[lane + 64 * jj] = gfl[jj];
-        wave_fence();
-        g01 = gb[lw];
-        g23 = gb[WL + lw];
-        g45 = gb[2 * WL + lw];
-        if (k + 1 < ND)
-        {
-#pragma unroll
-          for (int jj = 0; jj < NJ; ++jj)
-            gfl[jj] = gload<NT>(Gi + (k + 1) * LS + eo[jj]);
-        }
-      }
-      else
-      {
-        g01 = gq[0];
-        g23 = gq[1];
-        g45 = gq[2];
-        if (k + 1 < ND)
-        {
-          gq[0] = gload<NT>(Gb + (Gs + (unsigned)((k + 1) * 3 * GPS)));
-          gq[1] = gload<NT>(Gb + (Gs + (unsigned)((k + 1) * 3 * GPS + GPS)));
-          gq[2] = gload<NT>(Gb + (Gs + (unsigned)((k + 1) * 3 * GPS + 2 * GPS)));
-        }
-      }
-      q_s[ab] = u[k];
-      wave_fence();
-      double qr = 0.0, qs = 0.0, qt = 0.0;
-#pragma unroll
-      for (int mm = 0; mm < ND; ++mm)
-      {
-        qr += Da[mm] * slice_load<UNPAIRED>(q_s[mm * ND + b]);
-        qs += Db[mm] * slice_load<UNPAIRED>(q_s[a * ND + mm]);
-        qt += Dg[k * ND + mm] * u[mm];
-      }
-      const double sck = AFF ? W1[k] : kap; // W1[k] is wave-uniform (scalar load)
-      const double fr = sck * (g01.x * qr + g01.y * qs + g23.x * qt);
-      const double fs = sck * (g01.y * qr + g23.y * qs + g45.x * qt);
-      const double ft = sck * (g23.x * qr + g45.x * qs + g45.y * qt);
-      double acc = 0.0;
-      gr_s[ab] = fr;
-      gs_s[ab] = fs;
-      wave_fence();
-#pragma unroll
-      for (int mm = 0; mm < ND; ++mm)
-      {
-        acc += DTa[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]);
-        acc += DTb[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]);
-        Aq[mm] += Dg[k * ND + mm] * ft;
-      }
-      Aq[k] += acc;
-      wave_fence();
+      gs.take(k, 1.0, g01, g23, g45);
+      double fr, fs, ft;
+      // (affine cells: W1[k] is wave-uniform, a scalar load)
+      layer_forward<ND, UNPAIRED, false>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, AFF ? W1[k] : kap, fr, fs, ft);
+      layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
     }
     // ---- the cell's share of the restricted residual.  w = share - A_cell z down the lane's column; the product is
     // dropped on Dirichlet rows (a select, no branch: see the column kernel's epilogue).
@@ -325,9 +233,10 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
-      const int lk = (int)((lp[k / 2] >> (16 * (k & 1))) & 0xffffu);
+      const int lk = (int)packed_position(lp, k);
       const bool bc = (sbc[lk >> 6] >> (lk & 63)) & 1ull;
-      w[k] = sy[lk] - (bc ? 0.0 : Aq[k]);
+      const double Ak = Aq[k]; // (read ahead of the select: see the column kernel's epilogue)
+      w[k] = sy[lk] - (bc ? 0.0 : Ak);
     }
     // z in registers: M1[c][k] is wave-uniform (scalar loads)
     double tz[NDC];
@@ -356,7 +265,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
       for (int mm = 0; mm < ND; ++mm)
         vy += sM[mm * NDC + je] * gr_s[ie * ND + mm];
       if (contributes)
-        atomicAdd(&sc[(lcp[k / 2] >> (16 * (k & 1))) & 0xffffu], vy); // in LDS (ds_add_f64)
+        atomicAdd(&sc[packed_position(lcp, k)], vy); // in LDS (ds_add_f64)
       wave_fence();
     }
   }
