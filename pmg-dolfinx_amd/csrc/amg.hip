@@ -666,12 +666,12 @@ int amg_cycle(pmg_amg amg, int l, double* x, const double* b, hipStream_t s)
       return PMG_OK;
     }
     // a coarsest level too large to invert: smooth it harder
-    const ChebWork w{lv.r, lv.z, lv.q};
-    return cheb_iterate(
+    const ChebWork<double> w{lv.r, lv.z, lv.q};
+    return cheb_iterate<double>(
         w, [&lv, s](double* in, double* out) { return csr_product<0>(lv.A, in, nullptr, out, s); }, lv.dinv, lv.n,
         lv.lmax, 4 * amg->smoother_its, x, b, ResidualNone, true, s);
   }
-  const ChebWork w{lv.r, lv.z, lv.q};
+  const ChebWork<double> w{lv.r, lv.z, lv.q};
   const ApplyFn A = [&lv, s](double* in, double* out) { return csr_product<0>(lv.A, in, nullptr, out, s); };
   AmgLevel& lc = amg->levels[l + 1];
   PMG_TRY(cheb_iterate(w, A, lv.dinv, lv.n, lv.lmax, amg->smoother_its, x, b, ResidualUpdated, true, s)); // leaves r = b - A x
@@ -805,7 +805,7 @@ int dist_cycle(pmg_amg amg, double* x, const double* b, hipStream_t s)
   const int n = l->size_local;
   AmgLevel& l0 = amg->levels[0];
   AmgLevel& l1 = amg->levels[1];
-  const ChebWork w{amg->d0_r, amg->d0_z, amg->d0_q};
+  const ChebWork<double> w{amg->d0_r, amg->d0_z, amg->d0_q};
   const ApplyFn A = [op, s](double* in, double* out) { return laplacian_apply(op, in, out, s); };
   // The inverse diagonal of the hierarchy's OWN level-0 matrix, restricted to this rank (d0_dinv): the bound l0.lmax
   // was computed for D^-1 A with that diagonal, and the operator's diag_inv may never have been computed or may have

@@ -43,6 +43,16 @@ int fail(int code, const char* fmt, ...);
 
 inline hipStream_t S(pmg_stream s) { return reinterpret_cast<hipStream_t>(s); }
 
+// a device copy of the host array src[0, n) (at least one element is allocated), stream-ordered
+template <typename T>
+int upload(T** dst, const T* src, size_t n, hipStream_t s)
+{
+  PMG_HIP(hipMalloc(dst, sizeof(T) * (n ? n : 1)));
+  if (n)
+    PMG_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, s));
+  return PMG_OK;
+}
+
 constexpr int MAXND = PMG_MAX_DEGREE + 1;
 
 // 1-D tables on the host (tables.cpp)
@@ -193,11 +203,15 @@ struct Range
 // solvers.hip -- the 4th-kind Chebyshev / Jacobi smoother (src/chebyshev.hpp:46-91) and the CG loop
 // (src/cg.hpp:147-222) over ANY operator and preconditioner given as callables (the matrix-free
 // Laplacian, an assembled CSR level of the AMG hierarchy; the diagonal, a V-cycle, an AMG cycle)
+// The smoother and its vector passes exist for T = double and, for the FP32 V-cycle, T = float.
+template <typename T>
 struct ChebWork
 {
-  double *r = nullptr, *z = nullptr, *q = nullptr;
+  T *r = nullptr, *z = nullptr, *q = nullptr;
 };
-using ApplyFn = std::function<int(double* in, double* out)>;
+template <typename T>
+using ApplyFnT = std::function<int(T* in, T* out)>;
+using ApplyFn = ApplyFnT<double>;
 using PrecondFn = std::function<int(double* z, const double* r)>;
 int cg_iterate(pmg_cg cg, const ApplyFn& A, const double* dinv, const PrecondFn* M, bool flexible, double* x,
                const double* b, int* iterations, hipStream_t s);
@@ -219,10 +233,12 @@ enum : int
 // returns its residual, in which every correction has been applied to, x then has current ghosts without an exchange
 // of its own.  A_first (optional): the operator for the FIRST application, A x, when the caller knows that x's ghosts
 // are current already (no exchange).
-int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n, double lmax, int max_iter,
-                 double* x, const double* b, int need_r, bool x_zero, hipStream_t s, bool* split = nullptr,
-                 const ApplyFn* A_zeroed = nullptr, int n_total = 0, bool track_ghosts = false,
-                 const ApplyFn* A_first = nullptr);
+// T = float (the FP32 cycle, single domain): A alone; the scalar coefficients are formed in FP64 and rounded once.
+template <typename T>
+int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int n, double lmax, int max_iter, T* x,
+                 const T* b, int need_r, bool x_zero, hipStream_t s, bool* split = nullptr,
+                 const ApplyFnT<T>* A_zeroed = nullptr, int n_total = 0, bool track_ghosts = false,
+                 const ApplyFnT<T>* A_first = nullptr);
 
 // vector.hip -- stream-ordered building blocks used by the solvers
 // local dot of the owned entries into the result slot `slot` of the layout (device)
@@ -237,17 +253,30 @@ void launch_axpy(int n, double* r, double alpha, const double* x, const double* 
 void launch_pointwise(int n, double* w, const double* x, const double* y, hipStream_t s);
 // Chebyshev fused passes (src/chebyshev.hpp:57-83)
 // clear_q (optional): the operator's output, zeroed over [0, n_total) behind the update (see ThenClearF)
-void launch_cheb_init(int n, double* r, double* z, const double* b, const double* q,
-                      const double* dinv, double c0, hipStream_t s, double* clear_q = nullptr, int n_total = 0);
-void launch_cheb_step(int n, double* x, double* r, double* z, const double* q, const double* dinv,
-                      double c1, double c2, bool both, int x_final, hipStream_t s, double* clear_q = nullptr,
-                      int n_total = 0);
+void launch_cheb_init(int n, double* r, double* z, const double* b, const double* q, const double* dinv, double c0,
+                      hipStream_t s, double* clear_q = nullptr, int n_total = 0);
+void launch_cheb_step(int n, double* x, double* r, double* z, const double* q, const double* dinv, double c1, double c2,
+                      bool both, int x_final, hipStream_t s, double* clear_q = nullptr, int n_total = 0);
+void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, const double* dinv, double c1,
+                       double c2, int x_final, hipStream_t s, double* clear_q = nullptr, int n_total = 0);
 void launch_cheb_residual(int n, double* r, const double* q, hipStream_t s);
 void launch_add(int n, double* x, const double* z, hipStream_t s);
-void launch_cheb_last(int n, double* x, double* r, const double* z, const double* q, bool assign,
-                      hipStream_t s);
+void launch_cheb_last(int n, double* x, double* r, const double* z, const double* q, bool assign, hipStream_t s);
 void launch_zero(int n, double* x, hipStream_t s);
 void launch_mask_bc(int n, double* b, const int8_t* bc, hipStream_t s);
+// The same passes for the FP32 cycle: one element per lane, default cache policy.  They have no zeroed-output form: a
+// non-null clear_q ends the process with a message (cheb_iterate refuses such an operator before it gets here).
+void launch_cheb_init(int n, float* r, float* z, const float* b, const float* q, const float* dinv, float c0,
+                      hipStream_t s, float* clear_q = nullptr, int n_total = 0);
+void launch_cheb_step(int n, float* x, float* r, float* z, const float* q, const float* dinv, float c1, float c2,
+                      bool both, int x_final, hipStream_t s, float* clear_q = nullptr, int n_total = 0);
+void launch_cheb_first(int n, float* x, float* r, float* z, const float* q, const float* dinv, float c1,
+                       float c2, int x_final, hipStream_t s, float* clear_q = nullptr, int n_total = 0);
+void launch_cheb_residual(int n, float* r, const float* q, hipStream_t s);
+void launch_add(int n, float* x, const float* z, hipStream_t s);
+void launch_cheb_last(int n, float* x, float* r, const float* z, const float* q, bool assign, hipStream_t s);
+void launch_zero(int n, float* x, hipStream_t s);
+void launch_mask_bc(int n, float* b, const int8_t* bc, hipStream_t s);
 // CG fused passes (src/cg.hpp:160-211); alpha = rnorm / *d_py and beta = (*d_new - *d_sub) / rnorm are
 // formed on the device from the reduced scalars, so no host round trip sits between the kernels
 void launch_cg_update(int n, double* x, double* r, double* y, const double* p, const double* dinv,
@@ -257,28 +286,20 @@ void launch_cg_update2(int n, double* x, double* r, const double* p, const doubl
 void launch_cg_direction(int n, double* p, const double* y, double rnorm, const double* d_new,
                          const double* d_sub, hipStream_t s);
 
-// ---- the FP32 V-cycle (cycle_f32.hip, laplacian_f32.hip; single domain only) ----
-struct ChebWork32
-{
-  float *r = nullptr, *z = nullptr, *q = nullptr;
-};
-// cheb_iterate in FP32 on the operator's float form (no ghosts: no exchange bookkeeping, no zeroed-output variant)
-int cheb_iterate_f32(const ChebWork32& w, pmg_laplacian A, const float* dinv, int n, double lmax, int max_iter,
-                     float* x, const float* b, int need_r, bool x_zero, hipStream_t s, bool* split);
+// ---- the FP32 V-cycle (pmg_multigrid_set_precision; single domain only) ----
+// It runs the smoother loop, the vector passes and the patch-form transfer kernels of the FP64 cycle instantiated for
+// float (solvers.hip, vector.hip, interpolate.hip); its own are the float stiffness apply (laplacian_f32.hip) and the
+// conversions between the caller's FP64 vectors and the cycle's float ones (vector.hip).
 int laplacian_f32_supported(pmg_laplacian op, const char* who); // PMG_OK, or the refusal (ghosts, batched geometry)
 int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s);      // float tensor and table on first use (allocates)
 int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s);      // recompute the float tensor in place (if it exists)
 int laplacian_f32_diag(pmg_laplacian op, const float** d, hipStream_t s, bool* changed);
 long long laplacian_diag_version(pmg_laplacian op);
 int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s);
-float*& interp_m1_f32(pmg_interpolator ip); // the interpolator's float copy of its 1-D table (nullptr: not built)
-int transfer_f32_supported(pmg_interpolator ip, const char* who); // PMG_OK, or the refusal (no patch form, ghosts)
-int transfer_f32_prepare(pmg_interpolator ip, const float** M1);  // the float table, built on first use (allocates)
+int transfer_f32_prepare(pmg_interpolator ip, const float** M1); // the float table, built on first use (allocates)
 int prolong_add_f32(pmg_interpolator ip, const float* M1, const float* coarse, float* fine, hipStream_t s);
 int restrict_f32(pmg_interpolator ip, const float* M1, const float* fine, const float* fine_sub, float* coarse,
                  hipStream_t s);
 void launch_to_f32(int n, const double* in, const double* sub, float* out, hipStream_t s); // out = in (- sub)
 void launch_from_f32(int n, const float* in, double* out, bool add, hipStream_t s);        // out (+)= in
-void launch_zero_f32(int n, float* x, hipStream_t s);
-void launch_mask_bc_f32(int n, float* b, const int8_t* bc, hipStream_t s);
 } // namespace pmg

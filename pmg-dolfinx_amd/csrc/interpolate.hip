@@ -5,12 +5,18 @@
 // thread per fine dof, the cell's values staged in LDS and the cell matrix
 // applied as the tensor product of the 1-D table M1 (nd_f x nd_c) it is built
 // from (entries with |v| <= 1e-12 dropped, :119-135).
+//
+// The patch form of the two transfers (below) is one pair of kernels for both scalar types: the FP64 V-cycle's and, on
+// a float copy of M1, the FP32 cycle's (pmg_interpolator_*_f32; single domain, always fine += P coarse and a
+// zero-filled coarse vector summed with atomics).
 #include "common.hpp"
 #include "patches.hpp"
+#include "stiffness_layer.hpp"
 
 #include <algorithm>
 #include <cstdlib>
 #include <map>
+#include <type_traits>
 
 using namespace pmg;
 
@@ -33,7 +39,7 @@ struct pmg_interpolator_s
   int32_t* dmc_own = nullptr;   // ascending copies of dofmaps given in another cell-local node order
   int32_t* dmf_own = nullptr;   // (pmg_interpolator_create_ordered)
   double* M1 = nullptr;       // [ndf][ndc]
-  float* M1_32 = nullptr;     // float copy of M1, built on the first FP32 transfer (cycle_f32.hip)
+  float* M1_32 = nullptr;     // float copy of M1, built on the first FP32 transfer (transfer_f32_prepare)
   double* inv_mult = nullptr; // [fine total], 1/multiplicity (src/interpolate.hpp:172-178)
   int32_t* lcells = nullptr;  // nullptr = identity
   int32_t* bcells = nullptr;
@@ -50,7 +56,6 @@ struct pmg_interpolator_s
   uint8_t* pmult = nullptr;    // [fine pdofs entries] multiplicity of the fine dof (:172-178)
   int cmax_m = 0;
   int pwaves = 4;
-  size_t pshm = 0;
 };
 
 namespace
@@ -171,21 +176,12 @@ __global__ void restrict_kernel(int ncells_list, const int32_t* __restrict__ cel
 //     requests per patch; the reference issues one FP64 atomicAdd per (cell, coarse
 //     dof), src/interpolate.hpp:84).  A coloured write-back like the operator's is
 //     available in the kernel (atomic_out = 0).
-__device__ __forceinline__ void tfence()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ void tbarrier()
-{
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 __device__ __forceinline__ int ftab(int ndf, int a, int b, int c) // layer-major tables, patches.hpp
 {
   return c * ndf * ndf + a * ndf + b;
 }
 
+template <typename T>
 struct TransferArgs
 {
   int first, ndc, ndf, K, max_mf, max_mc;
@@ -194,7 +190,7 @@ struct TransferArgs
   const uint32_t *pdofs, *cpdofs;
   const uint16_t *lmaps, *clmaps;
   const uint8_t* pmult;
-  const double* M1;
+  const T* M1;
 };
 
 // Round 4, from the in-kernel stamps of the operator (profiles/kernel_tuning_r04.md): under load every DEPENDENT global
@@ -205,19 +201,20 @@ struct TransferArgs
 constexpr int transfer_cpw(int ndf) { return ndf * ndf * ndf <= 32 ? 2 : 1; } // cells per wavefront pass
 constexpr int TRANSFER_LIST_ITER = 6; // list entries per thread held in registers (6 x 512 threads >= any patch list)
 
-template <int NDC, int NDF>
-__global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ coarse,
-                                     double* __restrict__ fine, int add)
+extern __shared__ __attribute__((aligned(16))) unsigned char transfer_lds[]; // T[] of the two kernels below
+
+template <typename T, int NDC, int NDF>
+__global__ void prolong_patch_kernel(TransferArgs<T> A, const T* __restrict__ coarse, T* __restrict__ fine, int add)
 {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
+  T* const smem = reinterpret_cast<T*>(transfer_lds);
   constexpr int ndc = NDC, ndf = NDF, Nc = ndc * ndc * ndc, Nf = ndf * ndf * ndf;
   constexpr int n1 = ndf * ndc * ndc, n2 = ndf * ndf * ndc;
   constexpr int CPW = transfer_cpw(NDF), HL = 64 / CPW; // cells per wavefront pass, lanes per cell
   constexpr int IT = TRANSFER_LIST_ITER;
-  double* sM = smem;                  // [ndf*ndc]
-  double* sc = sM + ndf * ndc;        // [max_mc] coarse values of the patch
-  double* sf = sc + A.max_mc;         // [max_mf] fine values of the patch
-  double* scratch = sf + A.max_mf;    // per wave and cell of the pass: uc[Nc] t1[n1] t2[n2]
+  T* sM = smem;                  // [ndf*ndc]
+  T* sc = sM + ndf * ndc;        // [max_mc] coarse values of the patch
+  T* sf = sc + A.max_mc;         // [max_mf] fine values of the patch
+  T* scratch = sf + A.max_mf;    // per wave and cell of the pass: uc[Nc] t1[n1] t2[n2]
   const int p = A.first + blockIdx.x, t = threadIdx.x, nthr = blockDim.x;
   const int off = A.poff[p], Mf = A.poff[p + 1] - off;
   const int coff = A.cpoff[p], Mc = A.cpoff[p + 1] - coff;
@@ -235,22 +232,26 @@ __global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ 
   for (int i = t; i < Mc; i += nthr)
     sc[i] = coarse[A.cpdofs[coff + i] & PD_MASK];
   // ... and the values the correction is added to (they arrive under the contraction)
-  double v[IT];
+  T v[IT];
 #pragma unroll
   for (int k = 0; k < IT; ++k)
-    v[k] = !add ? 0.0 : A.nt ? __builtin_nontemporal_load(fine + (m[k] & PD_MASK)) : fine[m[k] & PD_MASK];
-  tbarrier();
+    v[k] = !add ? T(0) : A.nt ? __builtin_nontemporal_load(fine + (m[k] & PD_MASK)) : fine[m[k] & PD_MASK];
+  lds_barrier();
   const int wave = t >> 6, lane = t & 63, nw = nthr >> 6;
   const int half = lane / HL, ll = lane - half * HL; // the lane's cell of the pass, its lane inside the cell
-  double* uc = scratch + (size_t)(wave * CPW + half) * (Nc + n1 + n2);
-  double* t1 = uc + Nc;
-  double* t2 = t1 + n1;
+  T* uc = scratch + (size_t)(wave * CPW + half) * (Nc + n1 + n2);
+  T* t1 = uc + Nc;
+  T* t2 = t1 + n1;
   const uint16_t* cl = A.clmaps + (size_t)A.clmap_id[p] * A.K * Nc;
   const uint16_t* fl = A.lmaps + (size_t)A.lmap_id[p] * A.K * Nf;
   // the (cell, local dof) -> patch position tables of the NEXT cell are fetched while the
-  // current one is computed, so the cell loop itself touches only LDS
+  // current one is computed, so the cell loop itself touches only LDS.  FP64 only: in float the registers of the
+  // second set cost a resident workgroup per CU where a patch has no more cells than the workgroup has wavefronts
+  // (profiles/one_scalar_type.md), so the float kernel reads each cell's tables at the top of its pass.
+  constexpr bool AHEAD = sizeof(T) == 8;
   constexpr int FP = (Nf + HL - 1) / HL, CP = (Nc + HL - 1) / HL;
-  int fcur[FP], ccur[CP], fnxt[FP], cnxt[CP];
+  int fcur[FP], ccur[CP];
+  [[maybe_unused]] int fnxt[FP], cnxt[CP]; // the next cell's (AHEAD only: the float kernel never touches them)
   auto fetch = [&](int slot, int* fi, int* ci) {
     const int sl = slot < nc ? slot : nc - 1; // (a half-wavefront without a cell re-reads the last one's tables)
 #pragma unroll
@@ -267,13 +268,15 @@ __global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ 
       fi[j] = fl[(size_t)sl * Nf + ftab(ndf, a, b, c)];
     }
   };
-  if (wave * CPW < nc)
+  if (AHEAD && wave * CPW < nc)
     fetch(wave * CPW + half, fcur, ccur);
   for (int slot0 = wave * CPW; slot0 < nc; slot0 += nw * CPW)
   {
     const int slot = slot0 + half;
     const bool mine = slot < nc;
-    if (slot0 + nw * CPW < nc)
+    if constexpr (!AHEAD)
+      fetch(slot, fcur, ccur);
+    else if (slot0 + nw * CPW < nc)
       fetch(slot + nw * CPW, fnxt, cnxt);
 #pragma unroll
     for (int j = 0; j < CP; ++j)
@@ -282,27 +285,27 @@ __global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ 
       if (o < Nc)
         uc[o] = sc[ccur[j]];
     }
-    tfence();
+    wave_fence();
     for (int o = ll; o < n1; o += HL) // (a, j, k): sum over i
     {
       const int a = o / (ndc * ndc), jk = o - a * ndc * ndc;
-      double w = 0.0;
+      T w = T(0);
       #pragma unroll
       for (int i = 0; i < ndc; ++i)
         w += sM[a * ndc + i] * uc[i * ndc * ndc + jk];
       t1[o] = w;
     }
-    tfence();
+    wave_fence();
     for (int o = ll; o < n2; o += HL) // (a, b, k): sum over j
     {
       const int a = o / (ndf * ndc), r = o - a * ndf * ndc, b = r / ndc, k = r - b * ndc;
-      double w = 0.0;
+      T w = T(0);
       #pragma unroll
       for (int j = 0; j < ndc; ++j)
         w += sM[b * ndc + j] * t1[(a * ndc + j) * ndc + k];
       t2[o] = w;
     }
-    tfence();
+    wave_fence();
 #pragma unroll
     for (int jj = 0; jj < FP; ++jj) // (a, b, c): sum over k
     {
@@ -310,7 +313,7 @@ __global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ 
       if (o < Nf)
       {
         const int a = o / (ndf * ndf), r = o - a * ndf * ndf, b = r / ndf, c = r - b * ndf;
-        double w = 0.0;
+        T w = T(0);
         #pragma unroll
         for (int k = 0; k < ndc; ++k)
           w += sM[c * ndc + k] * t2[(a * ndf + b) * ndc + k];
@@ -318,15 +321,18 @@ __global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ 
           sf[fcur[jj]] = w; // shared dofs: identical values
       }
     }
-    tfence();
+    wave_fence();
+    if constexpr (AHEAD)
+    {
 #pragma unroll
-    for (int j = 0; j < CP; ++j)
-      ccur[j] = cnxt[j];
+      for (int j = 0; j < CP; ++j)
+        ccur[j] = cnxt[j];
 #pragma unroll
-    for (int j = 0; j < FP; ++j)
-      fcur[j] = fnxt[j];
+      for (int j = 0; j < FP; ++j)
+        fcur[j] = fnxt[j];
+    }
   }
-  tbarrier();
+  lds_barrier();
 #pragma unroll
   for (int k = 0; k < IT; ++k)
   {
@@ -338,23 +344,22 @@ __global__ void prolong_patch_kernel(TransferArgs A, const double* __restrict__ 
   {
     const uint32_t mm = A.pdofs[off + i];
     if (!(mm & PD_ACC))
-      fine[mm & PD_MASK] = (add ? fine[mm & PD_MASK] : 0.0) + sf[i];
+      fine[mm & PD_MASK] = (add ? fine[mm & PD_MASK] : T(0)) + sf[i];
   }
 }
 
-template <int NDC, int NDF>
-__global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__ fine,
-                                      const double* __restrict__ fine_sub, double* __restrict__ coarse,
-                                      int atomic_out)
+template <typename T, int NDC, int NDF>
+__global__ void restrict_patch_kernel(TransferArgs<T> A, const T* __restrict__ fine, const T* __restrict__ fine_sub,
+                                      T* __restrict__ coarse, int atomic_out)
 {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
+  T* const smem = reinterpret_cast<T*>(transfer_lds);
   constexpr int ndc = NDC, ndf = NDF, Nc = ndc * ndc * ndc, Nf = ndf * ndf * ndf;
   constexpr int n1 = ndf * ndc * ndc, n2 = ndf * ndf * ndc;
   constexpr int CPW = transfer_cpw(NDF), HL = 64 / CPW;
-  double* sM = smem;
-  double* sc = sM + ndf * ndc;     // [max_mc] coarse accumulators
-  double* sf = sc + A.max_mc;      // [max_mf] weighted fine values
-  double* scratch = sf + A.max_mf; // per wave and cell of the pass: w[Nf] t2[n2] t1[n1]
+  T* sM = smem;
+  T* sc = sM + ndf * ndc;     // [max_mc] coarse accumulators
+  T* sf = sc + A.max_mc;      // [max_mf] weighted fine values
+  T* scratch = sf + A.max_mf; // per wave and cell of the pass: w[Nf] t2[n2] t1[n1]
   const int p = A.first + blockIdx.x, t = threadIdx.x, nthr = blockDim.x;
   const int off = A.poff[p], Mf = A.poff[p + 1] - off;
   const int coff = A.cpoff[p], Mc = A.cpoff[p + 1] - coff;
@@ -370,7 +375,7 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
   {
     uint32_t m[4];
     uint8_t mu[4];
-    double v[4];
+    T v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
     {
@@ -393,26 +398,26 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
     {
       const int i = i0 + k * nthr;
       if (i < Mf)
-        sf[i] = v[k] / (double)mu[k]; // src/interpolate.hpp:81-82
+        sf[i] = v[k] / (T)mu[k]; // src/interpolate.hpp:81-82
     }
   }
   {
     // onto the earlier colours (coloured write-back only)
-    const double c0 = (!atomic_out && (cm & PD_ACC)) ? coarse[cm & PD_MASK] : 0.0;
+    const T c0 = (!atomic_out && (cm & PD_ACC)) ? coarse[cm & PD_MASK] : T(0);
     if (t < Mc)
       sc[t] = c0;
     for (int i = t + nthr; i < Mc; i += nthr)
     {
       const uint32_t mm = A.cpdofs[coff + i];
-      sc[i] = (!atomic_out && (mm & PD_ACC)) ? coarse[mm & PD_MASK] : 0.0;
+      sc[i] = (!atomic_out && (mm & PD_ACC)) ? coarse[mm & PD_MASK] : T(0);
     }
   }
-  tbarrier();
+  lds_barrier();
   const int wave = t >> 6, lane = t & 63, nw = nthr >> 6;
   const int half = lane / HL, ll = lane - half * HL;
-  double* w = scratch + (size_t)(wave * CPW + half) * (Nf + n1 + n2);
-  double* t2 = w + Nf;
-  double* t1 = t2 + n2;
+  T* w = scratch + (size_t)(wave * CPW + half) * (Nf + n1 + n2);
+  T* t2 = w + Nf;
+  T* t1 = t2 + n2;
   const uint16_t* cl = A.clmaps + (size_t)A.clmap_id[p] * A.K * Nc;
   const uint16_t* fl = A.lmaps + (size_t)A.lmap_id[p] * A.K * Nf;
   constexpr int FP = (Nf + HL - 1) / HL, CP = (Nc + HL - 1) / HL;
@@ -448,27 +453,27 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
       if (o < Nf)
         w[o] = sf[fcur[j]];
     }
-    tfence();
+    wave_fence();
     for (int o = ll; o < n2; o += HL) // (a, b, k): sum over c
     {
       const int ab = o / ndc, k = o - ab * ndc;
-      double v = 0.0;
+      T v = T(0);
       #pragma unroll
       for (int c = 0; c < ndf; ++c)
         v += sM[c * ndc + k] * w[ab * ndf + c];
       t2[o] = v;
     }
-    tfence();
+    wave_fence();
     for (int o = ll; o < n1; o += HL) // (a, j, k): sum over b
     {
       const int a = o / (ndc * ndc), r = o - a * ndc * ndc, j = r / ndc, k = r - j * ndc;
-      double v = 0.0;
+      T v = T(0);
       #pragma unroll
       for (int b = 0; b < ndf; ++b)
         v += sM[b * ndc + j] * t2[(a * ndf + b) * ndc + k];
       t1[o] = v;
     }
-    tfence();
+    wave_fence();
 #pragma unroll
     for (int jj = 0; jj < CP; ++jj) // (i, j, k): sum over a
     {
@@ -476,7 +481,7 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
       if (o < Nc)
       {
         const int i = o / (ndc * ndc), jk = o - i * ndc * ndc;
-        double v = 0.0;
+        T v = T(0);
         #pragma unroll
         for (int a = 0; a < ndf; ++a)
           v += sM[a * ndc + i] * t1[a * ndc * ndc + jk];
@@ -484,7 +489,7 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
           atomicAdd(&sc[ccur[jj]], v); // in LDS
       }
     }
-    tfence();
+    wave_fence();
 #pragma unroll
     for (int j = 0; j < CP; ++j)
       ccur[j] = cnxt[j];
@@ -492,7 +497,7 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
     for (int j = 0; j < FP; ++j)
       fcur[j] = fnxt[j];
   }
-  tbarrier();
+  lds_barrier();
   if (atomic_out) // single launch over all patches, coarse zero-filled beforehand
   {
     if (t < Mc)
@@ -509,55 +514,19 @@ __global__ void restrict_patch_kernel(TransferArgs A, const double* __restrict__
   }
 }
 
-// (coarse nd, fine nd) -> kernel instantiation
-#define PMG_FOR_PAIRS(X)                                                                            \
-  X(2, 3) X(2, 4) X(2, 5) X(2, 6) X(2, 7) X(2, 8) X(2, 9) X(3, 4) X(3, 5) X(3, 6) X(3, 7) X(3, 8)   \
-  X(3, 9) X(4, 5) X(4, 6) X(4, 7) X(4, 8) X(4, 9) X(5, 6) X(5, 7) X(5, 8) X(5, 9) X(6, 7) X(6, 8)   \
-  X(6, 9) X(7, 8) X(7, 9) X(8, 9)
-
-int launch_prolong_patch(int ndc, int ndf, int grid, int threads, size_t shm, hipStream_t s,
-                         const TransferArgs& A, const double* coarse, double* fine, int add)
+// runtime (coarse nd, fine nd) -> the pair as compile-time constants: f(integral_constant C, integral_constant F) for
+// the one pair that matches, over all 1 <= degree_coarse < degree_fine <= PMG_MAX_DEGREE
+template <int C = 2, int F = 3, typename Fn>
+int for_pair(int ndc, int ndf, const Fn& f)
 {
-#define X(C, F)                                                                                    \
-  if (ndc == C && ndf == F)                                                                        \
-  {                                                                                                \
-    prolong_patch_kernel<C, F><<<grid, threads, shm, s>>>(A, coarse, fine, add);                   \
-    return PMG_OK;                                                                                 \
-  }
-  PMG_FOR_PAIRS(X)
-#undef X
-  return fail(PMG_ERR_INVALID, "unsupported degree pair");
-}
-
-int launch_restrict_patch(int ndc, int ndf, int grid, int threads, size_t shm, hipStream_t s,
-                          const TransferArgs& A, const double* fine, const double* fine_sub, double* coarse,
-                          int atomic_out)
-{
-#define X(C, F)                                                                                    \
-  if (ndc == C && ndf == F)                                                                        \
-  {                                                                                                \
-    restrict_patch_kernel<C, F><<<grid, threads, shm, s>>>(A, fine, fine_sub, coarse, atomic_out); \
-    return PMG_OK;                                                                                 \
-  }
-  PMG_FOR_PAIRS(X)
-#undef X
-  return fail(PMG_ERR_INVALID, "unsupported degree pair");
-}
-
-int set_patch_kernel_lds(int ndc, int ndf, int bytes)
-{
-#define X(C, F)                                                                                    \
-  if (ndc == C && ndf == F)                                                                        \
-  {                                                                                                \
-    PMG_HIP(hipFuncSetAttribute((const void*)prolong_patch_kernel<C, F>,                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes));               \
-    PMG_HIP(hipFuncSetAttribute((const void*)restrict_patch_kernel<C, F>,                          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes));               \
-    return PMG_OK;                                                                                 \
-  }
-  PMG_FOR_PAIRS(X)
-#undef X
-  return fail(PMG_ERR_INVALID, "unsupported degree pair");
+  if (ndc == C && ndf == F)
+    return f(std::integral_constant<int, C>{}, std::integral_constant<int, F>{});
+  if constexpr (F < MAXND)
+    return for_pair<C, F + 1>(ndc, ndf, f);
+  else if constexpr (C + 2 <= MAXND)
+    return for_pair<C + 1, C + 2>(ndc, ndf, f);
+  else
+    return fail(PMG_ERR_INVALID, "unsupported degree pair");
 }
 
 // multiplicity of every fine patch dof, as a byte next to pdofs
@@ -572,48 +541,6 @@ __global__ void patch_mult_kernel(long long n, const uint32_t* __restrict__ pdof
   }
 }
 
-template <typename T>
-int upload(T** dst, const T* src, size_t n, hipStream_t s)
-{
-  PMG_HIP(hipMalloc(dst, sizeof(T) * (n ? n : 1)));
-  if (n)
-    PMG_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, s));
-  return PMG_OK;
-}
-} // namespace
-
-namespace
-{
-TransferArgs make_args(pmg_interpolator ip, int first)
-{
-  TransferArgs A;
-  A.first = first;
-  A.ndc = ip->ndc;
-  A.ndf = ip->ndf;
-  A.K = ip->fv.K;
-  A.max_mf = ip->fv.max_m;
-  A.max_mc = ip->cmax_m;
-  A.nt = ip->lf->total() >= (4 << 20) ? 1 : 0; // same rule as the smoother kernels (vector.hip)
-  A.poff = ip->fv.poff;
-  A.lmap_id = ip->fv.lmap_id;
-  A.pncell = ip->fv.pncell;
-  A.cpoff = ip->cpoff;
-  A.clmap_id = ip->clmap_id;
-  A.pdofs = ip->fv.pdofs;
-  A.cpdofs = ip->cpdofs;
-  A.lmaps = ip->fv.lmaps;
-  A.clmaps = ip->clmaps;
-  A.pmult = ip->pmult;
-  A.M1 = ip->M1;
-  return A;
-}
-
-// the fine operator is a small level's (all launches merged) and the layout's exchange is one launch
-bool whole_exchange(pmg_interpolator ip, pmg_layout l)
-{
-  return ip->fv.merged && l->num_ghosts > 0 && layout_exchanges_whole(l);
-}
-
 // patches of the interior cell list come first in launch order
 int interior_patches(pmg_interpolator ip)
 {
@@ -621,70 +548,7 @@ int interior_patches(pmg_interpolator ip)
   return ip->fv.n_launch_l < (int)lf.size() ? lf[ip->fv.n_launch_l] : ip->fv.npatch;
 }
 
-int prolong_patched(pmg_interpolator ip, double* coarse, double* fine, int add, hipStream_t s)
-{
-  const int n_int = interior_patches(ip), n_all = ip->fv.npatch;
-  if (whole_exchange(ip, ip->lc)) // a small level: the exchange whole, then all patches in one launch (laplacian.hip)
-  {
-    PMG_TRY(scatter_fwd_whole(ip->lc, coarse, s));
-    if (n_all > 0)
-      PMG_TRY(launch_prolong_patch(ip->ndc, ip->ndf, n_all, ip->pwaves * 64, ip->pshm, s, make_args(ip, 0), coarse,
-                                   fine, add));
-    PMG_HIP(hipGetLastError());
-    return PMG_OK;
-  }
-  PMG_TRY(pmg_scatter_fwd_begin(ip->lc, coarse, (pmg_stream)s)); // src/interpolate.hpp:202
-  if (n_int > 0)
-    PMG_TRY(launch_prolong_patch(ip->ndc, ip->ndf, n_int, ip->pwaves * 64, ip->pshm, s, make_args(ip, 0),
-                                 coarse, fine, add));
-  PMG_TRY(pmg_scatter_fwd_end(ip->lc, coarse, (pmg_stream)s)); // :217
-  if (n_all > n_int)
-    PMG_TRY(launch_prolong_patch(ip->ndc, ip->ndf, n_all - n_int, ip->pwaves * 64, ip->pshm, s,
-                                 make_args(ip, n_int), coarse, fine, add));
-  PMG_HIP(hipGetLastError());
-  return PMG_OK;
-}
-
-int restrict_patched(pmg_interpolator ip, double* fine, const double* fine_sub, double* coarse, hipStream_t s)
-{
-  // One launch per cell list; the patch sums go to the (small) coarse vector with
-  // FP64 atomics: a patch issues a few dozen 64-byte atomic requests (its coarse
-  // dofs form long runs), three orders of magnitude fewer than one per
-  // (cell, coarse dof) as in src/interpolate.hpp:84, and 8 colour launches of a
-  // ~30 us kernel would cost more than they save.
-  // fine_sub (optional, layouts without ghosts only): restrict fine - fine_sub.
-  const int n_int = interior_patches(ip), n_all = ip->fv.npatch;
-  PMG_REQUIRE(!fine_sub || ip->lf->num_ghosts == 0, "restriction of a difference needs a layout without ghosts");
-  if (whole_exchange(ip, ip->lf))
-  {
-    PMG_TRY(scatter_fwd_whole(ip->lf, fine, s));
-    launch_zero(ip->lc->total(), coarse, s);
-    if (n_all > 0)
-      PMG_TRY(launch_restrict_patch(ip->ndc, ip->ndf, n_all, ip->pwaves * 64, ip->pshm, s, make_args(ip, 0), fine,
-                                    fine_sub, coarse, 1));
-    PMG_HIP(hipGetLastError());
-    return PMG_OK;
-  }
-  PMG_TRY(pmg_scatter_fwd_begin(ip->lf, fine, (pmg_stream)s));             // :264
-  launch_zero(ip->lc->total(), coarse, s); // :270
-  if (n_int > 0)
-    PMG_TRY(launch_restrict_patch(ip->ndc, ip->ndf, n_int, ip->pwaves * 64, ip->pshm, s,
-                                  make_args(ip, 0), fine, fine_sub, coarse, 1));
-  PMG_TRY(pmg_scatter_fwd_end(ip->lf, fine, (pmg_stream)s)); // :281
-  if (n_all > n_int)
-    PMG_TRY(launch_restrict_patch(ip->ndc, ip->ndf, n_all - n_int, ip->pwaves * 64, ip->pshm, s,
-                                  make_args(ip, n_int), fine, fine_sub, coarse, 1));
-  PMG_HIP(hipGetLastError());
-  return PMG_OK;
-}
-} // namespace
-
-namespace pmg
-{
-bool interp_is_patched(pmg_interpolator ip) { return ip->patched; }
-float*& interp_m1_f32(pmg_interpolator ip) { return ip->M1_32; }
-
-TransferView interp_transfer_view(pmg_interpolator ip)
+TransferView transfer_view(pmg_interpolator ip)
 {
   TransferView v;
   v.lc = ip->lc;
@@ -702,6 +566,202 @@ TransferView interp_transfer_view(pmg_interpolator ip)
   v.pmult = ip->pmult;
   v.M1 = ip->M1;
   return v;
+}
+
+// M1: the table in the kernel's scalar type (v.M1, or the float copy of it)
+template <typename T>
+TransferArgs<T> make_args(const TransferView& v, const T* M1, int first)
+{
+  TransferArgs<T> A;
+  A.first = first;
+  A.ndc = v.ndc;
+  A.ndf = v.ndf;
+  A.K = v.fv.K;
+  A.max_mf = v.fv.max_m;
+  A.max_mc = v.cmax_m;
+  // FP64: same rule as the smoother kernels (vector.hip); the float vectors of the FP32 cycle are not streamed
+  A.nt = sizeof(T) == 8 && v.lf->total() >= (4 << 20) ? 1 : 0;
+  A.poff = v.fv.poff;
+  A.lmap_id = v.fv.lmap_id;
+  A.pncell = v.fv.pncell;
+  A.cpoff = v.cpoff;
+  A.clmap_id = v.clmap_id;
+  A.pdofs = v.fv.pdofs;
+  A.cpdofs = v.cpdofs;
+  A.lmaps = v.fv.lmaps;
+  A.clmaps = v.clmaps;
+  A.pmult = v.pmult;
+  A.M1 = M1;
+  return A;
+}
+
+// LDS of one transfer workgroup, in scalars: table + coarse list + fine list + per-wave scratch
+size_t transfer_lds_scalars(int ndc, int ndf, int cmax_m, int max_mf, int waves)
+{
+  const size_t per_wave = (size_t)transfer_cpw(ndf) * ((size_t)ndf * ndf * ndf + ndf * ndc * ndc + ndf * ndf * ndc);
+  return (size_t)ndf * ndc + cmax_m + max_mf + waves * per_wave;
+}
+template <typename T>
+size_t transfer_shm(const TransferView& v)
+{
+  return sizeof(T) * transfer_lds_scalars(v.ndc, v.ndf, v.cmax_m, v.fv.max_m, v.pwaves);
+}
+
+// a workgroup of the two kernels may ask for this much LDS (needed above 48 KB)
+template <typename T>
+int allow_transfer_lds(const TransferView& v)
+{
+  const size_t shm = transfer_shm<T>(v);
+  PMG_REQUIRE(shm <= 160 * 1024, "%stransfer kernels need %zu bytes of LDS", sizeof(T) == 4 ? "FP32 " : "", shm);
+  if (shm <= 48 * 1024)
+    return PMG_OK;
+  return for_pair(v.ndc, v.ndf, [&](auto C, auto F) {
+    PMG_HIP(hipFuncSetAttribute((const void*)prolong_patch_kernel<T, C(), F()>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    PMG_HIP(hipFuncSetAttribute((const void*)restrict_patch_kernel<T, C(), F()>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    return PMG_OK;
+  });
+}
+
+// the patches [first, first + count) of the launch order, one workgroup each
+template <typename T>
+int launch_prolong_patch(const TransferView& v, const T* M1, int first, int count, const T* coarse, T* fine, int add,
+                         hipStream_t s)
+{
+  if (count <= 0)
+    return PMG_OK;
+  const TransferArgs<T> A = make_args(v, M1, first);
+  return for_pair(v.ndc, v.ndf, [&](auto C, auto F) {
+    prolong_patch_kernel<T, C(), F()><<<count, v.pwaves * 64, transfer_shm<T>(v), s>>>(A, coarse, fine, add);
+    return PMG_OK;
+  });
+}
+template <typename T>
+int launch_restrict_patch(const TransferView& v, const T* M1, int first, int count, const T* fine, const T* fine_sub,
+                          T* coarse, hipStream_t s)
+{
+  if (count <= 0)
+    return PMG_OK;
+  const TransferArgs<T> A = make_args(v, M1, first);
+  return for_pair(v.ndc, v.ndf, [&](auto C, auto F) { // (atomic_out = 1: the coarse vector is zero-filled beforehand)
+    restrict_patch_kernel<T, C(), F()><<<count, v.pwaves * 64, transfer_shm<T>(v), s>>>(A, fine, fine_sub, coarse, 1);
+    return PMG_OK;
+  });
+}
+
+// the fine operator is a small level's (all launches merged) and the layout's exchange is one launch
+bool whole_exchange(pmg_interpolator ip, pmg_layout l)
+{
+  return ip->fv.merged && l->num_ghosts > 0 && layout_exchanges_whole(l);
+}
+
+int prolong_patched(pmg_interpolator ip, double* coarse, double* fine, int add, hipStream_t s)
+{
+  const TransferView v = transfer_view(ip);
+  const int n_int = v.n_interior, n_all = v.fv.npatch;
+  if (whole_exchange(ip, ip->lc)) // a small level: the exchange whole, then all patches in one launch (laplacian.hip)
+  {
+    PMG_TRY(scatter_fwd_whole(ip->lc, coarse, s));
+    PMG_TRY(launch_prolong_patch(v, v.M1, 0, n_all, coarse, fine, add, s));
+    PMG_HIP(hipGetLastError());
+    return PMG_OK;
+  }
+  PMG_TRY(pmg_scatter_fwd_begin(ip->lc, coarse, (pmg_stream)s)); // src/interpolate.hpp:202
+  PMG_TRY(launch_prolong_patch(v, v.M1, 0, n_int, coarse, fine, add, s));
+  PMG_TRY(pmg_scatter_fwd_end(ip->lc, coarse, (pmg_stream)s)); // :217
+  PMG_TRY(launch_prolong_patch(v, v.M1, n_int, n_all - n_int, coarse, fine, add, s));
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
+int restrict_patched(pmg_interpolator ip, double* fine, const double* fine_sub, double* coarse, hipStream_t s)
+{
+  // One launch per cell list; the patch sums go to the (small) coarse vector with
+  // FP64 atomics: a patch issues a few dozen 64-byte atomic requests (its coarse
+  // dofs form long runs), three orders of magnitude fewer than one per
+  // (cell, coarse dof) as in src/interpolate.hpp:84, and 8 colour launches of a
+  // ~30 us kernel would cost more than they save.
+  // fine_sub (optional, layouts without ghosts only): restrict fine - fine_sub.
+  const TransferView v = transfer_view(ip);
+  const int n_int = v.n_interior, n_all = v.fv.npatch;
+  PMG_REQUIRE(!fine_sub || ip->lf->num_ghosts == 0, "restriction of a difference needs a layout without ghosts");
+  if (whole_exchange(ip, ip->lf))
+  {
+    PMG_TRY(scatter_fwd_whole(ip->lf, fine, s));
+    launch_zero(ip->lc->total(), coarse, s);
+    PMG_TRY(launch_restrict_patch(v, v.M1, 0, n_all, fine, fine_sub, coarse, s));
+    PMG_HIP(hipGetLastError());
+    return PMG_OK;
+  }
+  PMG_TRY(pmg_scatter_fwd_begin(ip->lf, fine, (pmg_stream)s));             // :264
+  launch_zero(ip->lc->total(), coarse, s); // :270
+  PMG_TRY(launch_restrict_patch(v, v.M1, 0, n_int, fine, fine_sub, coarse, s));
+  PMG_TRY(pmg_scatter_fwd_end(ip->lf, fine, (pmg_stream)s)); // :281
+  PMG_TRY(launch_restrict_patch(v, v.M1, n_int, n_all - n_int, fine, fine_sub, coarse, s));
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
+// Can the FP32 transfers run on this interpolator?  (0 = yes, else the refusal has been recorded)
+int transfer_f32_supported(pmg_interpolator ip, const char* who)
+{
+  PMG_REQUIRE(ip->patched,
+              "%s: the FP32 transfers need a patch-form interpolator (pmg_interpolator_create_with_operator)", who);
+  for (pmg_layout l : {ip->lc, ip->lf})
+    PMG_REQUIRE(l->num_ghosts == 0 && !l->multi_rank() && !l->win,
+                "%s: the FP32 transfers are single-domain only (a layout has ghosts or a communicator)", who);
+  return PMG_OK;
+}
+} // namespace
+
+namespace pmg
+{
+bool interp_is_patched(pmg_interpolator ip) { return ip->patched; }
+
+// The interpolator's float copy of its 1-D table, built (and the LDS limit of the float kernels set) on first use;
+// patch form only
+int transfer_f32_prepare(pmg_interpolator ip, const float** M1)
+{
+  if (!ip->M1_32)
+  {
+    PMG_TRY(allow_transfer_lds<float>(transfer_view(ip)));
+    const int n = ip->ndf * ip->ndc;
+    std::vector<double> h(n);
+    PMG_HIP(hipMemcpy(h.data(), ip->M1, sizeof(double) * n, hipMemcpyDeviceToHost));
+    std::vector<float> f(h.begin(), h.end());
+    float* d = nullptr;
+    PMG_HIP(hipMalloc(&d, sizeof(float) * n));
+    const hipError_t e = hipMemcpy(d, f.data(), sizeof(float) * n, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+      (void)hipFree(d);
+      return fail(PMG_ERR_HIP, "transfer_f32_prepare: %s", hipGetErrorString(e));
+    }
+    ip->M1_32 = d;
+  }
+  *M1 = ip->M1_32;
+  return PMG_OK;
+}
+
+// fine += P coarse in FP32 (all patches of the fine operator in one launch: no halo on a single domain)
+int prolong_add_f32(pmg_interpolator ip, const float* M1, const float* coarse, float* fine, hipStream_t s)
+{
+  const TransferView v = transfer_view(ip);
+  PMG_TRY(launch_prolong_patch(v, M1, 0, v.fv.npatch, coarse, fine, 1, s));
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
+// coarse = R (fine - fine_sub) in FP32; fine_sub may be NULL
+int restrict_f32(pmg_interpolator ip, const float* M1, const float* fine, const float* fine_sub, float* coarse,
+                 hipStream_t s)
+{
+  const TransferView v = transfer_view(ip);
+  launch_zero(v.lc->total(), coarse, s);
+  PMG_TRY(launch_restrict_patch(v, M1, 0, v.fv.npatch, fine, fine_sub, coarse, s));
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
 }
 
 // fine += P coarse in one pass (src/pmg.hpp:123-129 fused); patch path only
@@ -739,7 +799,7 @@ int interp_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double
               "the fused residual restriction is not available here: it needs a patch-form interpolator on the patches "
               "of this operator, fine vectors without ghosts, resident geometry and one of the degree pairs 1-2, 2-4, "
               "1-3, 3-6");
-  return laplacian_apply_restrict(op, interp_transfer_view(ip), z, r, coarse, s);
+  return laplacian_apply_restrict(op, transfer_view(ip), z, r, coarse, s);
 }
 
 int interp_prolong(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s)
@@ -903,20 +963,12 @@ extern "C" int pmg_interpolator_create_with_operator(
                                                                            ip->inv_mult, ip->pmult);
     PMG_HIP(hipGetLastError());
   }
-  // LDS: table + coarse list + fine list + per-wave scratch
-  const int ndc = ip->ndc, ndf = ip->ndf;
-  const size_t per_wave = (size_t)transfer_cpw(ndf) * ((size_t)ip->Nf + ndf * ndc * ndc + ndf * ndf * ndc);
-  const size_t base = (size_t)ndf * ndc + cmax + v.max_m;
-  int waves = 8;
+  ip->pwaves = 8;
   if (const char* e = std::getenv("PMG_TRANSFER_WAVES")) // tuning: waves per patch (1 .. 16)
-    waves = std::max(1, std::min(16, std::atoi(e)));
-  while (waves > 1 && 8 * (base + waves * per_wave) > 64 * 1024)
-    --waves;
-  ip->pwaves = waves;
-  ip->pshm = 8 * (base + waves * per_wave);
-  PMG_REQUIRE(ip->pshm <= 160 * 1024, "transfer kernels need %zu bytes of LDS", ip->pshm);
-  if (ip->pshm > 48 * 1024)
-    PMG_TRY(set_patch_kernel_lds(ndc, ndf, (int)ip->pshm));
+    ip->pwaves = std::max(1, std::min(16, std::atoi(e)));
+  while (ip->pwaves > 1 && 8 * transfer_lds_scalars(ip->ndc, ip->ndf, cmax, v.max_m, ip->pwaves) > 64 * 1024)
+    --ip->pwaves; // (the float kernels run with the same count: their scratch fits a fortiori)
+  PMG_TRY(allow_transfer_lds<double>(transfer_view(ip)));
   PMG_HIP(hipStreamSynchronize(s));
   ip->patched = true;
   *out = guard.release();
@@ -991,6 +1043,26 @@ extern "C" int pmg_interpolator_interpolate_add(pmg_interpolator ip, double* coa
     return interp_prolong_add(ip, coarse, fine, S(stream));
   return fail(PMG_ERR_INVALID, "pmg_interpolator_interpolate_add needs an interpolator created "
                                "with pmg_interpolator_create_with_operator");
+}
+
+extern "C" int pmg_interpolator_interpolate_add_f32(pmg_interpolator ip, const float* coarse, float* fine,
+                                                    pmg_stream stream)
+{
+  PMG_REQUIRE(ip && coarse && fine, "pmg_interpolator_interpolate_add_f32: NULL argument");
+  PMG_TRY(transfer_f32_supported(ip, "pmg_interpolator_interpolate_add_f32"));
+  const float* M1 = nullptr;
+  PMG_TRY(transfer_f32_prepare(ip, &M1));
+  return prolong_add_f32(ip, M1, coarse, fine, S(stream));
+}
+
+extern "C" int pmg_interpolator_reverse_interpolate_f32(pmg_interpolator ip, const float* fine, const float* fine_sub,
+                                                        float* coarse, pmg_stream stream)
+{
+  PMG_REQUIRE(ip && fine && coarse, "pmg_interpolator_reverse_interpolate_f32: NULL argument");
+  PMG_TRY(transfer_f32_supported(ip, "pmg_interpolator_reverse_interpolate_f32"));
+  const float* M1 = nullptr;
+  PMG_TRY(transfer_f32_prepare(ip, &M1));
+  return restrict_f32(ip, M1, fine, fine_sub, coarse, S(stream));
 }
 
 extern "C" int pmg_interpolator_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z,

@@ -283,15 +283,6 @@ int run_launches(pmg_laplacian op, const double* x, double* y, int l0, int l1, h
   return PMG_OK;
 }
 
-template <typename T>
-int upload(T** dst, const T* src, size_t n, hipStream_t s)
-{
-  PMG_HIP(hipMalloc(dst, sizeof(T) * (n ? n : 1)));
-  if (n)
-    PMG_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, s));
-  return PMG_OK;
-}
-
 // (fine degree, coarse degree) pairs stiffness_restrict_kernel is instantiated for
 #define PMG_FOR_FUSED_PAIRS(X) X(2, 1) X(4, 2) X(3, 1) X(6, 3)
 

@@ -1,4 +1,4 @@
-// Single-precision form of the operator: the stiffness apply of the FP32 V-cycle (cycle_f32.hip) and of
+// Single-precision form of the operator: the stiffness apply of the FP32 V-cycle (solvers.hip mg_apply_f32) and of
 // pmg_laplacian_apply_f32.
 //
 // Same patch plan as the FP64 apply (laplacian.hip): one workgroup per patch, the patch's x values and y sums in

@@ -155,7 +155,8 @@ struct PatchView
   long long npdofs = 0; // total entries of pdofs
 };
 
-// What the single-precision transfers (cycle_f32.hip) read of an interpolator that shares its fine operator's patches.
+// An interpolator that shares its fine operator's patches, as its kernels read it: the patch-form transfers of both
+// precisions (interpolate.hip) and the restriction fused into the apply (laplacian.hip, stiffness_restrict.hpp).
 struct TransferView
 {
   pmg_layout lc = nullptr, lf = nullptr;

@@ -41,8 +41,6 @@ int amg_solve(pmg_amg amg, double* x, const double* b, hipStream_t s);
 pmg_layout amg_layout(pmg_amg amg);
 long long amg_capture_state(pmg_amg amg);
 long long laplacian_capture_state(pmg_laplacian op);
-void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, const double* dinv,
-                       double c1, double c2, int x_final, hipStream_t s, double* clear_q = nullptr, int n_total = 0);
 bool laplacian_wants_zeroed_output(pmg_laplacian op);
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
@@ -112,10 +110,10 @@ struct pmg_multigrid_s
   int fused_mode = -1;
   int fused_count = 0;
   // FP32 cycle (pmg_multigrid_set_precision): float vectors of every level, allocated on the first FP32 cycle; the
-  // operators and interpolators hold their own float forms (laplacian_f32.hip, cycle_f32.hip)
+  // operators and interpolators hold their own float forms (laplacian_f32.hip, interpolate.hip)
   int precision = PMG_PRECISION_FP64;
   std::vector<float*> u32, b32;
-  std::vector<ChebWork32> w32;
+  std::vector<ChebWork<float>> w32;
   std::vector<const float*> dinv32;   // per level, the operators' float diagonals (refreshed by mg_prepare_f32)
   std::vector<const float*> M1_32;    // per interpolator, its float 1-D table (owned by the interpolator)
 };
@@ -132,15 +130,18 @@ namespace pmg
 //            ResidualFused   -- the last apply itself is left to the consumer when *split comes back true:
 //                               b - A x = w.r - A w.z, for a restriction that forms A w.z on the fly
 //                               (interp_restrict_residual); a one-step smoother keeps its path and returns false.
-int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n, double lmax, int max_iter,
-                 double* x, const double* b, int need_r, bool x_zero, hipStream_t s, bool* split,
-                 const ApplyFn* A_zeroed, int n_total, bool track_ghosts, const ApplyFn* A_first)
+// T = float: the same loop on the float passes (vector.hip); every coefficient is formed in FP64 and rounded once.
+template <typename T>
+int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int n, double lmax, int max_iter, T* x,
+                 const T* b, int need_r, bool x_zero, hipStream_t s, bool* split, const ApplyFnT<T>* A_zeroed,
+                 int n_total, bool track_ghosts, const ApplyFnT<T>* A_first)
 {
+  PMG_REQUIRE(sizeof(T) == 8 || !A_zeroed, "cheb_iterate: the FP32 passes have no zeroed-output form");
   if (split)
     *split = false;
-  double* const clear_q = A_zeroed ? w.q : nullptr; // the vector kernels leave w.q zero for the next application
-  const ApplyFn& An = A_zeroed ? *A_zeroed : A;    // ... which then needs no zero-fill
-  const double c0 = 4.0 / (3.0 * lmax);
+  T* const clear_q = A_zeroed ? w.q : nullptr;      // the vector kernels leave w.q zero for the next application
+  const ApplyFnT<T>& An = A_zeroed ? *A_zeroed : A; // ... which then needs no zero-fill
+  const T c0 = (T)(4.0 / (3.0 * lmax));
   const int ng = track_ghosts && n_total > n ? n_total - n : 0; // ghost entries of x kept current (see common.hpp)
   if (x_zero)
   {
@@ -163,7 +164,7 @@ int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n,
       if (max_iter == 1) // a one-step smoother: z_1 is all there is (:73)
       {
         if (x_zero)
-          PMG_HIP(hipMemcpyAsync(x, w.z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+          PMG_HIP(hipMemcpyAsync(x, w.z, sizeof(T) * n, hipMemcpyDeviceToDevice, s));
         else
           launch_add(n, x, w.z, s);
       }
@@ -187,8 +188,8 @@ int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n,
         launch_cheb_residual(n, w.r, w.q, s);
       break;
     }
-    const double c1 = (2.0 * i - 1.0) / (2.0 * i + 3.0);
-    const double c2 = (8.0 * i + 4.0) / (2.0 * i + 3.0) / lmax;
+    const T c1 = (T)((2.0 * i - 1.0) / (2.0 * i + 3.0));
+    const T c2 = (T)((8.0 * i + 4.0) / (2.0 * i + 3.0) / lmax);
     // the last correction enters x here (1); when no residual is wanted either, r and z are dead behind this step (2)
     const int x_final = (i + 1 == max_iter) ? (need_r == ResidualNone ? 2 : 1) : 0;
     if (x_zero && i == 1)
@@ -201,6 +202,12 @@ int cheb_iterate(const ChebWork& w, const ApplyFn& A, const double* dinv, int n,
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }
+template int cheb_iterate<double>(const ChebWork<double>&, const ApplyFnT<double>&, const double*, int, double, int,
+                                  double*, const double*, int, bool, hipStream_t, bool*, const ApplyFnT<double>*, int,
+                                  bool, const ApplyFnT<double>*);
+template int cheb_iterate<float>(const ChebWork<float>&, const ApplyFnT<float>&, const float*, int, double, int, float*,
+                                 const float*, int, bool, hipStream_t, bool*, const ApplyFnT<float>*, int, bool,
+                                 const ApplyFnT<float>*);
 } // namespace pmg
 
 namespace
@@ -211,11 +218,12 @@ bool use_graph(pmg_multigrid mg);
 // the multigrid's parts invalidates all of them
 void drop_graphs(pmg_multigrid mg);
 
-int alloc_vec(pmg_layout l, double** p)
+template <typename T>
+int alloc_vec(pmg_layout l, T** p)
 {
   size_t n = l->total() ? l->total() : 1;
-  PMG_HIP(hipMalloc(p, sizeof(double) * n));
-  PMG_HIP(hipMemset(*p, 0, sizeof(double) * n));
+  PMG_HIP(hipMalloc(p, sizeof(T) * n));
+  PMG_HIP(hipMemset(*p, 0, sizeof(T) * n));
   PMG_HIP(hipStreamSynchronize(nullptr)); // the fill runs on the null stream, which non-blocking streams do not order
   return PMG_OK;
 }
@@ -228,7 +236,7 @@ int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, in
 {
   pmg_layout l = sm->layout;
   PMG_REQUIRE(laplacian_layout(A) == l, "Chebyshev: operator and smoother layouts differ");
-  const ChebWork w{sm->r, sm->z, sm->q};
+  const ChebWork<double> w{sm->r, sm->z, sm->q};
   // eig_range[0] is unused (src/chebyshev.hpp:51); no per-call D2D copy of the diagonal (:53)
   const ApplyFn apply = [A, s](double* in, double* out) { return laplacian_apply(A, in, out, s); };
   const ApplyFn apply_zeroed = [A, s](double* in, double* out) { return laplacian_apply_zeroed(A, in, out, s); };
@@ -245,7 +253,7 @@ int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b
 {
   pmg_layout l = sm->layout;
   PMG_REQUIRE(matrix_layout(M) == l, "Chebyshev: matrix and smoother layouts differ");
-  const ChebWork w{sm->r, sm->z, sm->q};
+  const ChebWork<double> w{sm->r, sm->z, sm->q};
   const ApplyFn apply = [M, s, applies](double* in, double* out)
   {
     if (applies)
@@ -325,7 +333,7 @@ void free_f32(pmg_multigrid mg)
     (void)hipFree(p);
   for (float* p : mg->b32)
     (void)hipFree(p);
-  for (const ChebWork32& w : mg->w32)
+  for (const ChebWork<float>& w : mg->w32)
   {
     (void)hipFree(w.r);
     (void)hipFree(w.z);
@@ -334,15 +342,6 @@ void free_f32(pmg_multigrid mg)
   mg->u32.clear();
   mg->b32.clear();
   mg->w32.clear();
-}
-
-int alloc_vec_f32(pmg_layout l, float** p)
-{
-  size_t n = l->total() ? l->total() : 1;
-  PMG_HIP(hipMalloc(p, sizeof(float) * n));
-  PMG_HIP(hipMemset(*p, 0, sizeof(float) * n));
-  PMG_HIP(hipStreamSynchronize(nullptr));
-  return PMG_OK;
 }
 
 // Everything the FP32 cycle reads besides its vectors, current on `s`: float vectors, the operators' float tensors,
@@ -356,14 +355,14 @@ int mg_prepare_f32(pmg_multigrid mg, hipStream_t s)
   {
     mg->u32.assign(L, nullptr);
     mg->b32.assign(L, nullptr);
-    mg->w32.assign(L, ChebWork32{});
+    mg->w32.assign(L, ChebWork<float>{});
     for (int i = 0; i < L; ++i)
     {
-      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->u32[i]));
-      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->b32[i]));
-      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].r));
-      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].z));
-      PMG_TRY(alloc_vec_f32(mg->layouts[i], &mg->w32[i].q));
+      PMG_TRY(alloc_vec(mg->layouts[i], &mg->u32[i]));
+      PMG_TRY(alloc_vec(mg->layouts[i], &mg->b32[i]));
+      PMG_TRY(alloc_vec(mg->layouts[i], &mg->w32[i].r));
+      PMG_TRY(alloc_vec(mg->layouts[i], &mg->w32[i].z));
+      PMG_TRY(alloc_vec(mg->layouts[i], &mg->w32[i].q));
     }
   }
   mg->M1_32.assign(L - 1, nullptr);
@@ -376,6 +375,33 @@ int mg_prepare_f32(pmg_multigrid mg, hipStream_t s)
     PMG_TRY(laplacian_f32_diag(mg->ops[i], &mg->dinv32[i], s, nullptr));
   }
   return PMG_OK;
+}
+
+// the smoother of level i in FP32: cheb_iterate on the operator's float form (no ghosts: no exchange bookkeeping)
+int level_smooth_f32(pmg_multigrid mg, int i, int need_r, bool x_zero, hipStream_t s, bool* split)
+{
+  pmg_laplacian op = mg->ops[i];
+  const ApplyFnT<float> apply = [op, s](float* in, float* out) { return laplacian_apply_f32(op, in, out, s); };
+  return cheb_iterate(mg->w32[i], apply, mg->dinv32[i], mg->layouts[i]->size_local, mg->smoothers[i]->eig_max,
+                      mg->smoothers[i]->max_iter, mg->u32[i], mg->b32[i], need_r, x_zero, s, split);
+}
+
+// u[0] = the coarse solver's answer to b[0], in FP64 (src/pmg.hpp:106-107): the library's own AMG (amg.hip), or,
+// KSP-style from a zero initial guess, the library's CG or the caller's callback
+bool has_coarse_solver(pmg_multigrid mg) { return mg->coarse_amg || mg->coarse || mg->coarse_fn; }
+int coarse_solve(pmg_multigrid mg, hipStream_t s)
+{
+  if (mg->coarse_amg)
+    return amg_solve(mg->coarse_amg, mg->u[0], mg->b[0], s);
+  launch_zero(mg->layouts[0]->total(), mg->u[0], s);
+  if (mg->coarse_fn)
+  {
+    if (mg->coarse_fn(mg->coarse_user, mg->u[0], mg->b[0], (pmg_stream)s) != 0)
+      return fail(PMG_ERR_INVALID, "the coarse-solver callback failed");
+    return PMG_OK;
+  }
+  int its = 0;
+  return pmg_cg_solve(mg->coarse, mg->ops[0], mg->u[0], mg->b[0], nullptr, &its, (pmg_stream)s);
 }
 
 // The V-cycle in FP32 (pmg_multigrid_set_precision): the caller's FP64 rhs / y at the finest level only.
@@ -405,12 +431,10 @@ int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hi
   }
   for (int i = L - 1; i > 0; --i)
   {
-    pmg_chebyshev sm = mg->smoothers[i];
     bool split = false;
     {
       Range rg("pmg:pre_smooth");
-      PMG_TRY(cheb_iterate_f32(mg->w32[i], mg->ops[i], mg->dinv32[i], mg->layouts[i]->size_local, sm->eig_max,
-                               sm->max_iter, mg->u32[i], mg->b32[i], ResidualSplit, true, s, &split));
+      PMG_TRY(level_smooth_f32(mg, i, ResidualSplit, true, s, &split));
     }
     Range rg("pmg:restrict");
     PMG_TRY(restrict_f32(mg->interps[i - 1], mg->M1_32[i - 1], mg->w32[i].r, split ? mg->w32[i].q : nullptr,
@@ -418,36 +442,17 @@ int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hi
   }
   const int n0 = mg->layouts[0]->size_local;
   if (L > 1)
-    launch_mask_bc_f32(n0, mg->b32[0], mg->bc0, s);
+    launch_mask_bc(n0, mg->b32[0], mg->bc0, s);
   {
     Range rg("pmg:coarse_solve");
-    if ((mg->coarse_amg || mg->coarse || mg->coarse_fn) && L > 1) // FP64 on the existing objects
+    if (has_coarse_solver(mg) && L > 1) // FP64 on the existing objects
     {
       launch_from_f32(n0, mg->b32[0], mg->b[0], false, s);
-      if (mg->coarse_amg)
-        PMG_TRY(amg_solve(mg->coarse_amg, mg->u[0], mg->b[0], s));
-      else
-      {
-        launch_zero(mg->layouts[0]->total(), mg->u[0], s);
-        if (mg->coarse_fn)
-        {
-          if (mg->coarse_fn(mg->coarse_user, mg->u[0], mg->b[0], (pmg_stream)s) != 0)
-            return fail(PMG_ERR_INVALID, "the coarse-solver callback failed");
-        }
-        else
-        {
-          int its = 0;
-          PMG_TRY(pmg_cg_solve(mg->coarse, mg->ops[0], mg->u[0], mg->b[0], nullptr, &its, (pmg_stream)s));
-        }
-      }
+      PMG_TRY(coarse_solve(mg, s));
       launch_to_f32(n0, mg->u[0], nullptr, mg->u32[0], s);
     }
     else
-    {
-      pmg_chebyshev sm = mg->smoothers[0];
-      PMG_TRY(cheb_iterate_f32(mg->w32[0], mg->ops[0], mg->dinv32[0], n0, sm->eig_max, sm->max_iter, mg->u32[0],
-                               mg->b32[0], ResidualNone, true, s, nullptr));
-    }
+      PMG_TRY(level_smooth_f32(mg, 0, ResidualNone, true, s, nullptr));
   }
   for (int i = 0; i < L - 1; ++i)
   {
@@ -456,10 +461,7 @@ int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hi
       PMG_TRY(prolong_add_f32(mg->interps[i], mg->M1_32[i], mg->u32[i], mg->u32[i + 1], s));
     }
     Range rg("pmg:post_smooth");
-    pmg_chebyshev sm = mg->smoothers[i + 1];
-    PMG_TRY(cheb_iterate_f32(mg->w32[i + 1], mg->ops[i + 1], mg->dinv32[i + 1], mg->layouts[i + 1]->size_local,
-                             sm->eig_max, sm->max_iter, mg->u32[i + 1], mg->b32[i + 1], ResidualNone, false, s,
-                             nullptr));
+    PMG_TRY(level_smooth_f32(mg, i + 1, ResidualNone, false, s, nullptr));
   }
   launch_from_f32(nf, mg->u32[L - 1], y, !y_zero, s);
   for (int i = 0; i < L; ++i)
@@ -519,22 +521,8 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
     Range rg("pmg:coarse_solve");
     const double* b0 = (L == 1) ? rhs : mg->b[0];
     const bool zero = (L == 1) ? y_zero : true;
-    if (mg->coarse_amg && L > 1) // :106-107 with the library's own AMG (amg.hip)
-      PMG_TRY(amg_solve(mg->coarse_amg, mg->u[0], mg->b[0], s));
-    else if ((mg->coarse || mg->coarse_fn) && L > 1) // :106-107, KSP-style: zero initial guess
-    {
-      launch_zero(mg->layouts[0]->total(), mg->u[0], s);
-      if (mg->coarse_fn)
-      {
-        if (mg->coarse_fn(mg->coarse_user, mg->u[0], mg->b[0], (pmg_stream)s) != 0)
-          return fail(PMG_ERR_INVALID, "the coarse-solver callback failed");
-      }
-      else
-      {
-        int its = 0;
-        PMG_TRY(pmg_cg_solve(mg->coarse, mg->ops[0], mg->u[0], b0, nullptr, &its, (pmg_stream)s));
-      }
-    }
+    if (has_coarse_solver(mg) && L > 1) // :106-107
+      PMG_TRY(coarse_solve(mg, s));
     else
       PMG_TRY(level_smooth(mg, 0, mg->u[0], b0, ResidualNone, zero, s)); // :109
   }

@@ -16,7 +16,7 @@
 
 namespace pmg
 {
-// ---- synchronisation of a slice exchange ----------------------------------------------------------------------
+// ---- synchronisation of a slice exchange (also of the patch transfers' wave-private scratch, interpolate.hip) -----
 // LDS executes a wavefront's instructions in order: where one wavefront owns the slices a compiler fence is all the
 // exchange needs, no s_barrier and no waitcnt.
 __device__ __forceinline__ void wave_fence()

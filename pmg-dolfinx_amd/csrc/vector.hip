@@ -5,7 +5,14 @@
 // Every kernel is a pure HBM stream: 16 B per lane (double2) when the operands
 // are 16-byte aligned, grid capped at 8 blocks per CU and grid-strided.
 // Nothing synchronises the host except the reductions that must return a value.
+//
+// The smoother's passes are defined once for both scalar types of the V-cycle: their functors carry the scalar T, the
+// element body one(i) is the same text for double and float, and the float launchers (the FP32 cycle) run it one
+// element per lane with the default cache policy -- pair(i), its double2 and its nt loads are FP64 only.  The
+// conversions between the two precisions are at the end of the pass launchers.
 #include "common.hpp"
+
+#include <cstdlib>
 
 using namespace pmg;
 
@@ -83,6 +90,13 @@ __global__ void ew_kernel1(int begin, int n, F f)
     f.one(i);
 }
 
+// one element per lane: f.one(i) alone (all a float functor has)
+template <typename F>
+void ew_launch1(int n, F f, hipStream_t s)
+{
+  if (n > 0)
+    ew_kernel1<<<ew_blocks(n), EW_THREADS, 0, s>>>(0, n, f);
+}
 template <typename F>
 void ew_launch(int n, bool vec_ok, F f, hipStream_t s)
 {
@@ -94,7 +108,7 @@ void ew_launch(int n, bool vec_ok, F f, hipStream_t s)
     ew_kernel2<<<ew_blocks(n2), EW_THREADS, 0, s>>>(n2, (n & 1) ? n - 1 : -1, f);
   }
   else
-    ew_kernel1<<<ew_blocks(n), EW_THREADS, 0, s>>>(0, n, f);
+    ew_launch1(n, f, s);
 }
 
 
@@ -136,10 +150,11 @@ void ew_launch_clear(int n_owned, int n_total, bool vec_ok, F f, double* q, hipS
 #define D2(p) reinterpret_cast<double2*>(p)
 #define CD2(p) reinterpret_cast<const double2*>(p)
 
+template <typename T>
 struct SetF
 {
-  double* x;
-  double v;
+  T* x;
+  T v;
   __device__ void pair(int i) const { D2(x)[i] = make_double2(v, v); }
   __device__ void one(int i) const { x[i] = v; }
 };
@@ -220,15 +235,15 @@ __device__ __forceinline__ void st2(double* p, int i, double2 v)
     D2(p)[i] = v;
 }
 
-template <bool NT>
+template <typename T, bool NT>
 struct ChebInitF
 { // r = b - q ; z = c0 * dinv * r   (src/chebyshev.hpp:57,67-68); q == nullptr: r = b
-  double* r;
-  double* z;
-  const double* b;
-  const double* q;
-  const double* dinv;
-  double c0;
+  T* r;
+  T* z;
+  const T* b;
+  const T* q;
+  const T* dinv;
+  T c0;
   __device__ void pair(int i) const
   {
     double2 vb = ld2<NT>(b, i), vd = ld2<NT>(dinv, i);
@@ -244,7 +259,7 @@ struct ChebInitF
   }
   __device__ void one(int i) const
   {
-    double vr = b[i] - (q ? q[i] : 0.0);
+    T vr = b[i] - (q ? q[i] : T(0));
     r[i] = vr;
     z[i] = c0 * dinv[i] * vr;
   }
@@ -253,15 +268,15 @@ struct ChebInitF
 // kernel anyway), so no pass is needed for "x += z" after the last operator application:
 //   step 1:      x = (x + z_1) + z_2   (the sums in the order of src/chebyshev.hpp:73)
 //   step i >= 2: x += z_{i+1}
-template <bool NT, bool BOTH>
+template <typename T, bool NT, bool BOTH>
 struct ChebStepF
 { // r -= q ; z_new = c1 z + c2 dinv r ; x += (z if BOTH) + z_new   (src/chebyshev.hpp:73-83)
-  double* x;
-  double* r;
-  double* z;
-  const double* q;
-  const double* dinv;
-  double c1, c2;
+  T* x;
+  T* r;
+  T* z;
+  const T* q;
+  const T* dinv;
+  T c1, c2;
   int x_final; // 1, 2: the last correction: x is gathered next (apply / prolongation), keep it in cache;
                // 2: nobody reads r and z after this step (no residual wanted): they are not written
   __device__ void pair(int i) const
@@ -291,10 +306,10 @@ struct ChebStepF
   }
   __device__ void one(int i) const
   {
-    double vz = z[i], vx = x[i];
+    T vz = z[i], vx = x[i];
     if constexpr (BOTH)
       vx += vz;
-    double vr = r[i] - q[i];
+    T vr = r[i] - q[i];
     vz = c1 * vz + c2 * dinv[i] * vr;
     if (x_final != 2)
     {
@@ -304,15 +319,15 @@ struct ChebStepF
     x[i] = vx + vz;
   }
 };
-template <bool NT>
+template <typename T, bool NT>
 struct ChebFirstF
 { // first step from x == 0:  r -= q ; z_2 = c1 z_1 + c2 dinv r ; x = z_1 + z_2
-  double* x;
-  double* r;
-  double* z;
-  const double* q;
-  const double* dinv;
-  double c1, c2;
+  T* x;
+  T* r;
+  T* z;
+  const T* q;
+  const T* dinv;
+  T c1, c2;
   int x_final;
   __device__ void pair(int i) const
   {
@@ -335,9 +350,9 @@ struct ChebFirstF
   }
   __device__ void one(int i) const
   {
-    double vz = z[i];
-    const double vx = vz;
-    double vr = r[i] - q[i];
+    T vz = z[i];
+    const T vx = vz;
+    T vr = r[i] - q[i];
     vz = c1 * vz + c2 * dinv[i] * vr;
     if (x_final != 2)
     {
@@ -347,11 +362,11 @@ struct ChebFirstF
     x[i] = vx + vz;
   }
 };
-template <bool NT>
+template <typename T, bool NT>
 struct ChebResidualF
 { // after the last application when the residual is wanted: r -= q   (src/chebyshev.hpp:77)
-  double* r;
-  const double* q;
+  T* r;
+  const T* q;
   __device__ void pair(int i) const
   {
     double2 vr = ld2<NT>(r, i), vq = ld2<NT>(q, i);
@@ -359,13 +374,13 @@ struct ChebResidualF
   }
   __device__ void one(int i) const { r[i] -= q[i]; }
 };
-template <bool NT>
+template <typename T, bool NT>
 struct ChebLastF
 { // the only step of a one-step smoother when x and the residual are wanted:  x (+)= z ; r -= q
-  double* x;
-  double* r;
-  const double* z;
-  const double* q;
+  T* x;
+  T* r;
+  const T* z;
+  const T* q;
   int assign; // x = z (first step from x == 0) instead of x += z
   __device__ void pair(int i) const
   {
@@ -376,15 +391,15 @@ struct ChebLastF
   }
   __device__ void one(int i) const
   {
-    x[i] = (assign ? 0.0 : x[i]) + z[i];
+    x[i] = (assign ? T(0) : x[i]) + z[i];
     r[i] -= q[i];
   }
 };
-template <bool NT>
+template <typename T, bool NT>
 struct AddF
 { // x += z
-  double* x;
-  const double* z;
+  T* x;
+  const T* z;
   __device__ void pair(int i) const
   {
     double2 vx = ld2<NT>(x, i), vz = ld2<NT>(z, i);
@@ -392,22 +407,36 @@ struct AddF
   }
   __device__ void one(int i) const { x[i] += z[i]; }
 };
+template <typename T>
 struct MaskBcF
 { // b *= (1 - bc)   (src/pmg.hpp:100-103)
-  double* b;
+  T* b;
   const int8_t* bc;
   __device__ void pair(int i) const
   {
     if (bc[2 * i])
-      b[2 * i] = 0.0;
+      b[2 * i] = T(0);
     if (bc[2 * i + 1])
-      b[2 * i + 1] = 0.0;
+      b[2 * i + 1] = T(0);
   }
   __device__ void one(int i) const
   {
     if (bc[i])
-      b[i] = 0.0;
+      b[i] = T(0);
   }
+};
+struct ToF32
+{ // out = float(in - sub)   (sub optional: the defect rhs - A y of an FP32 cycle from a non-zero guess)
+  float* out;
+  const double *in, *sub;
+  __device__ void one(int i) const { out[i] = (float)(sub ? in[i] - sub[i] : in[i]); }
+};
+struct FromF32
+{ // out (+)= double(in)
+  double* out;
+  const float* in;
+  int add;
+  __device__ void one(int i) const { out[i] = (add ? out[i] : 0.0) + (double)in[i]; }
 };
 struct CgUpdateF
 { // x += alpha p ; r -= alpha y ; y = dinv r   (src/cg.hpp:186-192), alpha = rnorm / *d_py (:182)
@@ -584,14 +613,14 @@ void launch_cheb_init(int n, double* r, double* z, const double* b, const double
   if (clear_q)
   {
     if (streams(n))
-      ew_launch_clear(n, n_total, v, ChebInitF<true>{r, z, b, q, dinv, c0}, clear_q, s);
+      ew_launch_clear(n, n_total, v, ChebInitF<double, true>{r, z, b, q, dinv, c0}, clear_q, s);
     else
-      ew_launch_clear(n, n_total, v, ChebInitF<false>{r, z, b, q, dinv, c0}, clear_q, s);
+      ew_launch_clear(n, n_total, v, ChebInitF<double, false>{r, z, b, q, dinv, c0}, clear_q, s);
   }
   else if (streams(n))
-    ew_launch(n, v, ChebInitF<true>{r, z, b, q, dinv, c0}, s);
+    ew_launch(n, v, ChebInitF<double, true>{r, z, b, q, dinv, c0}, s);
   else
-    ew_launch(n, v, ChebInitF<false>{r, z, b, q, dinv, c0}, s);
+    ew_launch(n, v, ChebInitF<double, false>{r, z, b, q, dinv, c0}, s);
 }
 void launch_cheb_step(int n, double* x, double* r, double* z, const double* q, const double* dinv,
                       double c1, double c2, bool both, int x_final, hipStream_t s, double* clear_q, int n_total)
@@ -601,29 +630,29 @@ void launch_cheb_step(int n, double* x, double* r, double* z, const double* q, c
   if (clear_q) // small levels only (merged-launch operators): no streaming variants needed
   {
     if (both)
-      ew_launch_clear(n, n_total, v, ChebStepF<false, true>{x, r, z, q, dinv, c1, c2, xf}, clear_q, s);
+      ew_launch_clear(n, n_total, v, ChebStepF<double, false, true>{x, r, z, q, dinv, c1, c2, xf}, clear_q, s);
     else
-      ew_launch_clear(n, n_total, v, ChebStepF<false, false>{x, r, z, q, dinv, c1, c2, xf}, clear_q, s);
+      ew_launch_clear(n, n_total, v, ChebStepF<double, false, false>{x, r, z, q, dinv, c1, c2, xf}, clear_q, s);
     return;
   }
   if (streams(n))
   {
     if (both)
-      ew_launch(n, v, ChebStepF<true, true>{x, r, z, q, dinv, c1, c2, xf}, s);
+      ew_launch(n, v, ChebStepF<double, true, true>{x, r, z, q, dinv, c1, c2, xf}, s);
     else
-      ew_launch(n, v, ChebStepF<true, false>{x, r, z, q, dinv, c1, c2, xf}, s);
+      ew_launch(n, v, ChebStepF<double, true, false>{x, r, z, q, dinv, c1, c2, xf}, s);
   }
   else if (both)
-    ew_launch(n, v, ChebStepF<false, true>{x, r, z, q, dinv, c1, c2, xf}, s);
+    ew_launch(n, v, ChebStepF<double, false, true>{x, r, z, q, dinv, c1, c2, xf}, s);
   else
-    ew_launch(n, v, ChebStepF<false, false>{x, r, z, q, dinv, c1, c2, xf}, s);
+    ew_launch(n, v, ChebStepF<double, false, false>{x, r, z, q, dinv, c1, c2, xf}, s);
 }
 void launch_cheb_residual(int n, double* r, const double* q, hipStream_t s)
 {
   if (streams(n))
-    ew_launch(n, aligned16(r) && aligned16(q), ChebResidualF<true>{r, q}, s);
+    ew_launch(n, aligned16(r) && aligned16(q), ChebResidualF<double, true>{r, q}, s);
   else
-    ew_launch(n, aligned16(r) && aligned16(q), ChebResidualF<false>{r, q}, s);
+    ew_launch(n, aligned16(r) && aligned16(q), ChebResidualF<double, false>{r, q}, s);
 }
 void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, const double* dinv,
                        double c1, double c2, int x_final, hipStream_t s, double* clear_q, int n_total)
@@ -631,34 +660,87 @@ void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, 
   bool v = aligned16(x) && aligned16(r) && aligned16(z) && aligned16(q) && aligned16(dinv);
   const int xf = x_final;
   if (clear_q)
-    ew_launch_clear(n, n_total, v, ChebFirstF<false>{x, r, z, q, dinv, c1, c2, xf}, clear_q, s);
+    ew_launch_clear(n, n_total, v, ChebFirstF<double, false>{x, r, z, q, dinv, c1, c2, xf}, clear_q, s);
   else if (streams(n))
-    ew_launch(n, v, ChebFirstF<true>{x, r, z, q, dinv, c1, c2, xf}, s);
+    ew_launch(n, v, ChebFirstF<double, true>{x, r, z, q, dinv, c1, c2, xf}, s);
   else
-    ew_launch(n, v, ChebFirstF<false>{x, r, z, q, dinv, c1, c2, xf}, s);
+    ew_launch(n, v, ChebFirstF<double, false>{x, r, z, q, dinv, c1, c2, xf}, s);
 }
 void launch_cheb_last(int n, double* x, double* r, const double* z, const double* q, bool assign,
                       hipStream_t s)
 {
   bool v = aligned16(x) && aligned16(r) && aligned16(z) && aligned16(q);
   if (streams(n))
-    ew_launch(n, v, ChebLastF<true>{x, r, z, q, assign ? 1 : 0}, s);
+    ew_launch(n, v, ChebLastF<double, true>{x, r, z, q, assign ? 1 : 0}, s);
   else
-    ew_launch(n, v, ChebLastF<false>{x, r, z, q, assign ? 1 : 0}, s);
+    ew_launch(n, v, ChebLastF<double, false>{x, r, z, q, assign ? 1 : 0}, s);
 }
 void launch_add(int n, double* x, const double* z, hipStream_t s)
 {
   if (streams(n))
-    ew_launch(n, aligned16(x) && aligned16(z), AddF<true>{x, z}, s);
+    ew_launch(n, aligned16(x) && aligned16(z), AddF<double, true>{x, z}, s);
   else
-    ew_launch(n, aligned16(x) && aligned16(z), AddF<false>{x, z}, s);
+    ew_launch(n, aligned16(x) && aligned16(z), AddF<double, false>{x, z}, s);
 }
 // x[0..n) = 0 in ONE kernel (hipMemsetAsync issues two, ~5 us apiece on a small level)
-void launch_zero(int n, double* x, hipStream_t s) { ew_launch(n, aligned16(x), SetF{x, 0.0}, s); }
+void launch_zero(int n, double* x, hipStream_t s) { ew_launch(n, aligned16(x), SetF<double>{x, 0.0}, s); }
 void launch_mask_bc(int n, double* b, const int8_t* bc, hipStream_t s)
 {
-  ew_launch(n, true, MaskBcF{b, bc}, s);
+  ew_launch(n, true, MaskBcF<double>{b, bc}, s);
 }
+// The passes of the FP32 cycle: one element per lane, default cache policy.  both / x_final as above.  There is no
+// zeroed-output form: cheb_iterate refuses such an operator in FP32, and a clear_q that arrives here all the same
+// would lose its zero-fill without notice, so it ends the process.
+static void refuse_clear_q(const float* clear_q)
+{
+  if (clear_q)
+  {
+    std::fprintf(stderr, "pmg_amd: the FP32 smoother passes have no zeroed-output form (clear_q given)\n");
+    std::abort();
+  }
+}
+void launch_cheb_init(int n, float* r, float* z, const float* b, const float* q, const float* dinv, float c0,
+                      hipStream_t s, float* clear_q, int)
+{
+  refuse_clear_q(clear_q);
+  ew_launch1(n, ChebInitF<float, false>{r, z, b, q, dinv, c0}, s);
+}
+void launch_cheb_step(int n, float* x, float* r, float* z, const float* q, const float* dinv, float c1, float c2,
+                      bool both, int x_final, hipStream_t s, float* clear_q, int)
+{
+  refuse_clear_q(clear_q);
+  if (both)
+    ew_launch1(n, ChebStepF<float, false, true>{x, r, z, q, dinv, c1, c2, x_final}, s);
+  else
+    ew_launch1(n, ChebStepF<float, false, false>{x, r, z, q, dinv, c1, c2, x_final}, s);
+}
+void launch_cheb_first(int n, float* x, float* r, float* z, const float* q, const float* dinv, float c1, float c2,
+                       int x_final, hipStream_t s, float* clear_q, int)
+{
+  refuse_clear_q(clear_q);
+  ew_launch1(n, ChebFirstF<float, false>{x, r, z, q, dinv, c1, c2, x_final}, s);
+}
+void launch_cheb_residual(int n, float* r, const float* q, hipStream_t s)
+{
+  ew_launch1(n, ChebResidualF<float, false>{r, q}, s);
+}
+void launch_cheb_last(int n, float* x, float* r, const float* z, const float* q, bool assign, hipStream_t s)
+{
+  ew_launch1(n, ChebLastF<float, false>{x, r, z, q, assign ? 1 : 0}, s);
+}
+void launch_add(int n, float* x, const float* z, hipStream_t s) { ew_launch1(n, AddF<float, false>{x, z}, s); }
+void launch_zero(int n, float* x, hipStream_t s) { ew_launch1(n, SetF<float>{x, 0.0f}, s); }
+void launch_mask_bc(int n, float* b, const int8_t* bc, hipStream_t s) { ew_launch1(n, MaskBcF<float>{b, bc}, s); }
+// ... and the conversions between the caller's FP64 vectors and the cycle's float ones
+void launch_to_f32(int n, const double* in, const double* sub, float* out, hipStream_t s)
+{
+  ew_launch1(n, ToF32{out, in, sub}, s);
+}
+void launch_from_f32(int n, const float* in, double* out, bool add, hipStream_t s)
+{
+  ew_launch1(n, FromF32{out, in, add ? 1 : 0}, s);
+}
+
 void launch_cg_update(int n, double* x, double* r, double* y, const double* p, const double* dinv,
                       double rnorm, const double* d_py, hipStream_t s)
 {
@@ -942,7 +1024,7 @@ extern "C" int pmg_scatter_rev_end(pmg_layout l, double* x, pmg_stream stream)
 extern "C" int pmg_vec_set(pmg_layout l, double* x, double value, pmg_stream stream)
 {
   PMG_REQUIRE(l && x, "pmg_vec_set: NULL argument");
-  ew_launch(l->total(), aligned16(x), SetF{x, value}, S(stream));
+  ew_launch(l->total(), aligned16(x), SetF<double>{x, value}, S(stream));
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }

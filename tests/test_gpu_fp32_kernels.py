@@ -1,7 +1,9 @@
 """The FP32 kernels branch by branch: the stiffness apply (laplacian_f32.hip) at full and cut-short patches, with the
 streamed tensor, per-cell kappa, odd little meshes and operators not in their default state; kappa changed in place;
-the patch-form transfers (cycle_f32.hip) at every degree pair through their own entry points; the FP32 V-cycle at
-every Chebyshev degree count and with the Krylov and callback coarse solvers; PCG with the FP32 cycle at full size.
+the patch-form transfers (the float instantiation of interpolate.hip's two patch kernels) at every degree pair through
+their own entry points, and in both precisions with workgroups too small for their lists; the FP32 V-cycle (the float
+instantiation of the smoother loop and passes, solvers.hip and vector.hip) at every Chebyshev degree count and with the
+Krylov and callback coarse solvers; PCG with the FP32 cycle at full size.
 
 Every FP32 output is filled with NaN before the call, so a value the kernel was meant to overwrite and did not fails
 the comparison.  References: the FP64 oracles (pmg_oracle, and the C oracle at the large sizes) on the float-rounded
@@ -456,6 +458,58 @@ def test_fp32_transfers_every_pair(pm, pc, pf):
 @pytest.mark.parametrize("pc,pf,n,warped", TRANSFER_SHAPES)
 def test_fp32_transfers_full_and_cut_short_patches(pm, pc, pf, n, warped):
     _transfer_case(pm, pc, pf, n, warped)
+
+
+TOL_TRANSFER_FP64 = 1e-12  # the FP64 transfers against the oracle (test_gpu_parity.py::test_transfer_parity)
+
+
+# (coarse degree, fine degree, cells of the box, cells of one patch of the fine operator: patch_shape(), patches.hpp)
+FEW_WAVEFRONT_CASES = [(1, 2, (4, 4, 16), (4, 4, 16)), (2, 4, (4, 4, 8), (2, 2, 8))]
+
+
+@pytest.mark.parametrize("waves", [1, 3])
+@pytest.mark.parametrize("pc,pf,n,block", FEW_WAVEFRONT_CASES)
+def test_transfers_with_few_wavefronts(pm, pc, pf, n, block, waves, monkeypatch):
+    """PMG_TRANSFER_WAVES (read when the interpolator is created) makes the workgroup smaller than its patch's lists:
+    the fine list of a patch is longer than the 6 entries per thread the prolongation holds in registers (its tail
+    loop) and the coarse list longer than the workgroup (the restriction's loops behind the first entry per thread).
+    Both boxes are whole patches of the fine operator on a tensor grid (the structured builder: full blocks, checked
+    on the host by test_patch_plans.py), so every patch has (pf bx + 1)(pf by + 1)(pf bz + 1) = 2 673 fine and
+    (pc bx + 1)(pc by + 1)(pc bz + 1) = 425 coarse dofs: one patch for (1, 2), four for (2, 4).  Both precisions of
+    the same two kernels."""
+    assert all(m % b == 0 for m, b in zip(n, block))  # whole patches only
+    fine_list = int(np.prod([pf * b + 1 for b in block]))
+    coarse_list = int(np.prod([pc * b + 1 for b in block]))
+    assert (fine_list, coarse_list) == (2673, 425)
+    assert fine_list > 6 * 64 * waves and coarse_list > 64 * waves  # TRANSFER_LIST_ITER x threads; threads
+    from oracle import pmg_oracle as po
+
+    monkeypatch.setenv("PMG_TRANSFER_WAVES", str(waves))
+    part = pm.BoxPartition(n)
+    lc, lf = part.level(pc), part.level(pf)
+    Lc, Lf = pm.make_layout(lc), pm.make_layout(lf)
+    fop = pm.MatFreeLaplacian(pf, 2.0, lf.dofmap, part.xgeom, part.geom_dofmap, lf.lcells, lf.bcells, lf.bc_marker,
+                              Lf)
+    ip = pm.Interpolator(pc, pf, lc.dofmap, lf.dofmap, lf.lcells, lf.bcells, Lc, Lf, fine_operator=fop)
+    oi = po.Interpolator(pc, pf, lc.dofmap, lf.dofmap, lc.ndofs, lf.ndofs)
+    rng = np.random.default_rng(waves * 100 + pc * 10 + pf)
+    uc, uf = rng.standard_normal(lc.ndofs), rng.standard_normal(lf.ndofs)
+
+    def vec(layout, values):
+        v = pm.Vector(layout)
+        v.data.copy_(torch.from_numpy(values))
+        return v
+
+    vc, vf = vec(Lc, uc), vec(Lf, np.full(lf.ndofs, np.nan))
+    ip.interpolate(vc, vf)
+    _check("fp64_prolong", _relerr(vf.data_copy(), oi.interpolate(uc)), TOL_TRANSFER_FP64)
+    vf = vec(Lf, uf)
+    ip.interpolate_add(vc, vf)
+    _check("fp64_prolong_add", _relerr(vf.data_copy(), uf + oi.interpolate(uc)), TOL_TRANSFER_FP64)
+    vf, vc = vec(Lf, uf), vec(Lc, np.full(lc.ndofs, np.nan))
+    ip.reverse_interpolate(vf, vc)
+    _check("fp64_restrict", _relerr(vc.data_copy(), oi.reverse_interpolate(uf)), TOL_TRANSFER_FP64)
+    _check_transfers(ip, oi, lc.ndofs, lf.ndofs, rng)
 
 
 def test_fp32_transfer_refusals(pm):

@@ -2,7 +2,7 @@
 solver) and PCG to 1e-8 (iterations and wall time), on the same hierarchy, both precisions timed the same way.
 Prints one JSON line.
 
-usage: python tools/fp32_cycle.py [--n 64] [--orders 1,2,4] [--orders 1,3,6] [--reps 20] [--repeats 5]
+usage: python tools/fp32_cycle.py [--n 64] [--orders 1,2,4] [--orders 1,3,6] [--reps 20] [--repeats 5] [--cheb-its 3]
 
 Timing (measuring-on-mi355x): warm-up first, then `repeats` timed runs of `reps` back-to-back calls bracketed by
 HIP events; the median run is reported.  The FP32 kernel's fraction of 8 TB/s is computed on the byte model
@@ -68,9 +68,9 @@ def pcg(h, rtol):
     return its, wall, pm.norm(r) / pm.norm(h.rhs[-1])
 
 
-def one_config(n, orders, reps, repeats):
-    h = pm.PoissonHierarchy(n, orders, kappa=2.0, cheb_its=3)
-    out = {"n": n, "orders": list(orders), "fine_dofs": h.fine_ndofs_owned, "apply": {}}
+def one_config(n, orders, reps, repeats, cheb_its=3):
+    h = pm.PoissonHierarchy(n, orders, kappa=2.0, cheb_its=cheb_its)
+    out = {"n": n, "orders": list(orders), "cheb_its": cheb_its, "fine_dofs": h.fine_ndofs_owned, "apply": {}}
     for P, op, lay in zip(orders, h.operators, h.layouts):
         ncells = h.part.ncells
         x64, y64 = pm.Vector(lay), pm.Vector(lay)
@@ -111,11 +111,12 @@ def main():
     ap.add_argument("--orders", action="append", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--cheb-its", type=int, default=3)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     configs = [tuple(int(p) for p in o.split(",")) for o in (a.orders or ["1,2,4"])]
     res = {"tool": "fp32_cycle", "device": torch.cuda.get_device_name(0),
-           "configs": [one_config(a.n, o, a.reps, a.repeats) for o in configs]}
+           "configs": [one_config(a.n, o, a.reps, a.repeats, a.cheb_its) for o in configs]}
     print(json.dumps(res))
 
 
