@@ -35,4 +35,21 @@ inline std::vector<double> rotating_tensor(const std::vector<double>& xgeom,
   }
   return kt;
 }
+
+// The drivers' reaction coefficient (--reaction S): sigma_c = S (1 + x_c) at the cell centre.  Returns [ncells], the
+// layout of pmg_laplacian_set_reaction.
+inline std::vector<double> linear_reaction(const std::vector<double>& xgeom,
+                                           const std::vector<std::int32_t>& geom_dofmap, double S)
+{
+  const std::size_t ncells = geom_dofmap.size() / 8;
+  std::vector<double> sigma(ncells);
+  for (std::size_t c = 0; c < ncells; ++c)
+  {
+    double x = 0;
+    for (int k = 0; k < 8; ++k)
+      x += 0.125 * xgeom[3 * (std::size_t)geom_dofmap[8 * c + k]];
+    sigma[c] = S * (1.0 + x);
+  }
+  return sigma;
+}
 } // namespace examples

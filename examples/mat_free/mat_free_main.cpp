@@ -10,6 +10,8 @@
 // --kappa-tensor sets the per-cell diffusion tensor with eigenvalues (1, 2 + x, 4) rotated by
 // Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z) at the cell centre (not in the reference); it combines with --kappa-field, and the
 // stencil comparison is left out as well.
+// --reaction S adds the reaction term sigma u with sigma_c = S (1 + x_c) at the cell centre (not in the reference;
+// pmg_laplacian_set_reaction); it combines with the two above, and the stencil comparison is left out as well.
 // --lift restates the right-hand side the reference's driver has commented out (:252-255): u = the assembled load of
 // f = 0 (:133,143: the interpolation of f is commented out as well), lifted with the boundary value 1.3 (:165) and
 // set_bc -- pmg_laplacian_assemble_rhs, _apply_lifting, _set_bc on the one operator -- instead of u = 1.
@@ -34,6 +36,7 @@ int main(int argc, char** argv)
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
   bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false;
+  double reaction = 0.0; // S of --reaction; 0 = no term
   std::size_t batch_size = 0; // :38,46-50: cells whose geometry tensor is held at a time (0 = all, resident)
   for (int i = 1; i < argc; ++i)
   {
@@ -52,6 +55,8 @@ int main(int argc, char** argv)
       kappa_field = true;
     else if (!std::strcmp(argv[i], "--kappa-tensor"))
       kappa_tensor = true;
+    else if (!std::strcmp(argv[i], "--reaction"))
+      reaction = std::atof(next());
     else if (!std::strcmp(argv[i], "--lift"))
       lift = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
@@ -59,7 +64,7 @@ int main(int argc, char** argv)
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--lift]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--lift]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -96,7 +101,13 @@ int main(int argc, char** argv)
       op.handle(map); // the handle is created with the first index map the operator sees
       op.set_coefficient_tensor(kt.span()); // the library copies it
     }
-    if (kappa_field || kappa_tensor)
+    if (reaction > 0.0)
+    {
+      device_array<double> sigma(examples::linear_reaction(mesh.xgeom, mesh.geom_dofmap, reaction));
+      op.handle(map);
+      op.set_reaction(sigma.span()); // the library keeps the vector it builds from it
+    }
+    if (kappa_field || kappa_tensor || reaction > 0.0)
     {
       std::vector<double> kh(V.ndofs);
       // u = 1 lies in the kernel of the operator away from the boundary whatever the coefficient: a vector that
@@ -165,7 +176,7 @@ int main(int argc, char** argv)
       std::printf("CSR Matvec: %d reps, %.3f us per apply\n", nreps, ms * 1e3 / nreps);
       std::printf("CSR nnz = %zu\n", mat.nnz());
       acc::axpy(ec, -1.0, y, zc);
-      if (degree != 1 || kappa_field || kappa_tensor)
+      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0)
       {
         std::printf("Norm of z = %.15e\n", acc::norm(zc));
         std::printf("Norm of error = %.3e\n", acc::norm(ec));

@@ -27,6 +27,9 @@
 //   --kappa-tensor   a per-cell diffusion tensor on every level: eigenvalues (1, 2 + x, 4), rotated by
 //                    Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z) at the cell centre (pmg_laplacian_set_coefficient_tensor);
 //                    combines with --kappa-field, --amg, --pcg, --fp32-cycle, --csr
+//   --reaction S     the reaction term sigma u on every level, sigma_c = S (1 + x_c) at the cell centre
+//                    (pmg_laplacian_set_reaction); combines with --kappa-field, --kappa-tensor, --amg, --pcg,
+//                    --fp32-cycle, --csr
 //   --check-partition px,py,pz   host-only consistency check of the brick partition (no GPU)
 //   --node-order basix   the dofmaps handed over in basix's cell-local node order (endpoints first), as dolfinx
 //                    gives them to the reference (examples/pmg/main.cpp:83-87); same numbers as without
@@ -87,6 +90,7 @@ struct Options : examples::RankOptions
   bool amg_gather = false; // --amg-setup gathered
   bool kappa_field = false;    // --kappa-field: the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z
   bool kappa_tensor = false;   // --kappa-tensor: per-cell tensor, eigenvalues (1, 2 + x, 4) rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z)
+  double reaction = 0.0;       // --reaction S: sigma_c = S (1 + x_c); 0 = no term
   bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
   std::vector<int> csr_levels; // empty with --csr: every level
 };
@@ -170,6 +174,12 @@ void solve(const Options& o)
       device_array<T> kt(examples::rotating_tensor(mesh.xgeom, mesh.geom_dofmap));
       operators[i]->handle(maps[i]); // the handle is created with the first index map the operator sees
       operators[i]->set_coefficient_tensor(kt.span());
+    }
+    if (o.reaction > 0.0) // -div(kappa grad u) + sigma u: one value per cell, the same cells on every level
+    {
+      device_array<T> sigma(examples::linear_reaction(mesh.xgeom, mesh.geom_dofmap, o.reaction));
+      operators[i]->handle(maps[i]);
+      operators[i]->set_reaction(sigma.span());
     }
     operators[i]->compute_diag_inverse(maps[i]);                  // replaces :274-279 (no CSR)
 
@@ -424,6 +434,8 @@ int main(int argc, char** argv)
         o.kappa_field = true;
       else if (!std::strcmp(argv[i], "--kappa-tensor"))
         o.kappa_tensor = true;
+      else if (!std::strcmp(argv[i], "--reaction") && i + 1 < argc)
+        o.reaction = std::atof(argv[++i]);
       else if (!std::strcmp(argv[i], "--csr"))
       {
         o.csr = true;
@@ -490,7 +502,7 @@ int main(int argc, char** argv)
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
                      "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
-                     "           [--kappa-field] [--kappa-tensor]\n"
+                     "           [--kappa-field] [--kappa-tensor] [--reaction S]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"

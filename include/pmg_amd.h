@@ -392,6 +392,41 @@ int pmg_laplacian_has_coefficient_field(pmg_laplacian op);
  * pmg_laplacian_has_coefficient_tensor: 1 / 0, -1 for NULL. */
 int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const double* kt, pmg_stream stream);
 int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op);
+/* Reaction term: -div(K grad u) + sigma u with sigma >= 0 constant per cell (not in the reference) -- an implicit
+ * step of the heat equation (M / dt + K), a screened Poisson problem, a Robin-type penalty.  With GLL collocation the
+ * quadrature points are the nodes, so the mass matrix is diagonal and the term is one vector over the dofs,
+ *   d[dof] = sum over the listed cells c that hold the dof, at the cell's point q on it, of sigma[c] * w_q * detJ_q
+ * (the weights of pmg_laplacian_assemble_rhs with sigma in place of kappa and f = 1; 0 on marked dofs).  The operator
+ * becomes y = A x + d .* x on unmarked rows; Dirichlet rows stay y = x.  d does not depend on the stored tensor, so
+ * the call combines freely with kappa, the nodal field, the coefficient tensor, both geometry modes and batched
+ * geometry.  No apply form takes a further pass over the vectors: in the FP64 and FP32 patch kernels the first patch
+ * of a dof starts its sum at d * x where it started at 0, and the fused restriction (pmg_interpolator_restrict_residual)
+ * spreads r - d z over the cells where it spread r.  The chain form
+ * (pmg_laplacian_set_chain_form) does not carry the term: while one is set, the operator's interior runs as the
+ * column launches, and pmg_laplacian_launches_per_apply counts those.
+ *
+ * `sigma` is a device array [ncells], one value per local cell, ghost cells included -- exactly the cells kappa
+ * covers.  The library keeps d, not sigma; the caller may free sigma on return.  sigma = NULL removes the term and
+ * restores every apply form (FP64, FP32, fused restriction) bit for bit; a computed inverse diagonal is recomputed by
+ * the code of an operator without a term, whose atomic sums meet in no fixed order, so it agrees with that operator's
+ * to rounding as two computations of it always do.  Every value must be finite and >= 0 (all zeros is
+ * legal; one small reduction over the cells, summed over the ranks, so all ranks refuse or none does -- on several
+ * ranks the call is collective); otherwise PMG_ERR_INVALID, the message names how many cells failed, and nothing has
+ * changed.  The call builds, and a later call rebuilds in place at the same addresses: d over size_local +
+ * num_ghosts (ghost entries hold this rank's cells only, as those of the computed diagonal), its float copy if the
+ * float tensor has been built (otherwise the first FP32 use builds it), and the inverse diagonal if it came from
+ * pmg_laplacian_compute_diag_inverse -- 1 / (diag(A) + d), 1 on marked rows (a diagonal installed with
+ * pmg_laplacian_set_diag_inverse is left alone).  d is summed with atomics: two sets of the same values agree to
+ * rounding, not bit for bit.  An assembled matrix follows with pmg_matrix_update_values (d on the diagonal of the
+ * unmarked rows); a smoother's eigenvalue bound and an AMG hierarchy (d on the diagonal of its level 0) are the
+ * caller's to renew.  The first set and the removal change a kernel argument, so cached V-cycle graphs re-capture; a
+ * second set with other values keeps them valid.  Like the other set-up calls it allocates and synchronises the
+ * stream: not inside a stream capture (refused).  pmg_laplacian_apply_lifting, pmg_laplacian_set_bc,
+ * pmg_laplacian_assemble_rhs and pmg_laplacian_assemble_neumann do not change: a diagonal term couples no unmarked row
+ * to a marked column.
+ * pmg_laplacian_has_reaction: 1 / 0, -1 for NULL. */
+int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma, pmg_stream stream);
+int pmg_laplacian_has_reaction(pmg_laplacian op);
 /* GLL-collocated load vector b_i = sum_cells kappa * w_q * detJ_q * f_i at q = i
  * (what dolfinx assemble_vector does for L = inner(f, v)*dx with the GLL rule,
  * examples/pmg/poisson.py:40; examples/pmg/main.cpp:289-295), then set_bc:

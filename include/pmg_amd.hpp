@@ -681,6 +681,25 @@ public:
       check(pmg_laplacian_set_coefficient_tensor(_op, nullptr, nullptr));
   }
   bool has_coefficient_tensor() const { return _op && pmg_laplacian_has_coefficient_tensor(_op) == 1; }
+  /// Reaction term (pmg_laplacian_set_reaction; not in the reference): sigma is device memory of ncells values, one
+  /// finite value >= 0 per local cell, ghost cells included; the operator becomes -div(K grad u) + sigma u, i.e.
+  /// y = A x + d .* x on unmarked rows with the lumped GLL mass vector d of sigma.  The library keeps d, not sigma.  A
+  /// computed inverse diagonal follows; an assembled MatrixOperator follows with update_values().
+  /// The handle must exist: it is created with the first vector or index map the operator sees (handle(map)).
+  void set_reaction(std::span<const T> sigma)
+  {
+    if (sigma.size() != _kappa.size())
+      throw std::runtime_error("MatFreeLaplacian: the reaction coefficient holds one value per cell");
+    if (!_op)
+      throw std::runtime_error("MatFreeLaplacian: set_reaction before the operator has seen an index map");
+    check(pmg_laplacian_set_reaction(_op, sigma.data(), nullptr));
+  }
+  void clear_reaction()
+  {
+    if (_op)
+      check(pmg_laplacian_set_reaction(_op, nullptr, nullptr));
+  }
+  bool has_reaction() const { return _op && pmg_laplacian_has_reaction(_op) == 1; }
   /// b = GLL-collocated load vector of the nodal source f, BC rows zeroed
   /// (assemble_vector + set_bc, examples/pmg/main.cpp:289-300).  The scaling is by the per-cell coefficient only.
   template <typename Vector>

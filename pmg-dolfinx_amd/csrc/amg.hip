@@ -54,6 +54,7 @@ namespace pmg
 {
 int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
 const double* laplacian_diag_inv(pmg_laplacian op);
+const double* laplacian_reaction(pmg_laplacian op); // nullptr = none
 pmg_layout laplacian_layout(pmg_laplacian op);
 PatchView laplacian_patches(pmg_laplacian op);
 struct LaplacianInputs
@@ -1034,6 +1035,17 @@ static int amg_create(pmg_amg* out, pmg_laplacian op, const int64_t* global_inde
           add(row, col, Ke[i][j]);
         }
       }
+    }
+    // the reaction term of the operator (pmg_laplacian_set_reaction): its vector on the diagonal of the owned,
+    // unmarked rows (the vector is zero on marked dofs; a row no cell lists keeps its identity)
+    if (const double* dreact = laplacian_reaction(op))
+    {
+      std::vector<double> react(n);
+      if (n > 0)
+        PMG_HIP(hipMemcpy(react.data(), dreact, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+      for (int i = 0; i < n; ++i)
+        if (!bc[i] && cnt[i] > 0 && react[i] != 0.0)
+          add(i, i, react[i]);
     }
     A0.n = n;
     A0.m = replicated ? total : n;

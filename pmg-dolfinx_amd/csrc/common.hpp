@@ -292,6 +292,7 @@ void launch_cg_direction(int n, double* p, const double* y, double rnorm, const 
 // conversions between the caller's FP64 vectors and the cycle's float ones (vector.hip).
 int laplacian_f32_supported(pmg_laplacian op, const char* who); // PMG_OK, or the refusal (ghosts, batched geometry)
 int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s);      // float tensor and table on first use (allocates)
+int laplacian_f32_reaction(pmg_laplacian op, hipStream_t s);     // bring the float copy of the reaction vector up to date (if the float tensor exists)
 int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s);      // recompute the float tensor in place (if it exists)
 int laplacian_f32_diag(pmg_laplacian op, const float** d, hipStream_t s, bool* changed);
 long long laplacian_diag_version(pmg_laplacian op);

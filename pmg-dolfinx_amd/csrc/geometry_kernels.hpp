@@ -212,12 +212,16 @@ __global__ void diagonal_kernel(long long slot0, long long nslots, int nd, int K
     atomicAdd(&diag[dof], kappa[cell] * s);
 }
 
-__global__ void diag_invert_kernel(int n, const int8_t* __restrict__ bc, double* __restrict__ d)
+// (react, optional: the reaction vector, added to the diagonal of A before the inversion; zero on marked dofs)
+__global__ void diag_invert_kernel(int n, const int8_t* __restrict__ bc, const double* __restrict__ react,
+                                   double* __restrict__ d)
 {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n)
   {
     double v = d[i];
+    if (react)
+      v += react[i];
     d[i] = bc[i] ? 1.0 : (v != 0.0 ? 1.0 / v : 0.0);
   }
 }
@@ -245,4 +249,28 @@ __global__ void rhs_kernel(long long nslots, int nq, const int32_t* __restrict__
   double K[3][3], detJ;
   jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
   atomicAdd(&b[dof], kappa[c] * w[q] * detJ * f[dof]);
+}
+
+// ---- reaction vector: d[dof] = sum over the listed cells' points on the dof of sigma_c w_q detJ_q, the weights of
+// rhs_kernel with sigma in place of kappa and f = 1 (d is zeroed first; marked dofs stay 0: their rows are y = x) ----
+__global__ void reaction_kernel(long long nslots, int nq, const int32_t* __restrict__ pcell,
+                                const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                                const double* __restrict__ dphi, const double* __restrict__ w,
+                                const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc,
+                                const double* __restrict__ sigma, double* __restrict__ d)
+{
+  long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * nq)
+    return;
+  long long slot = gid / nq;
+  int q = (int)(gid - slot * nq);
+  int c = pcell[slot];
+  if (c < 0)
+    return;
+  int32_t dof = dofmap[(size_t)c * nq + q];
+  if (bc[dof])
+    return;
+  double K[3][3], detJ;
+  jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
+  atomicAdd(&d[dof], sigma[c] * w[q] * detJ);
 }

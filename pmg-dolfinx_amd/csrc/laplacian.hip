@@ -145,7 +145,7 @@ int launch_stiffness(pmg_laplacian op, const double* x, double* y, int first, in
     constexpr bool AFF = decltype(aff)::value, NT = decltype(nt)::value;
     stiffness_column_kernel<P, AFF, NT><<<count, Shape<P>::WTHREADS, 0, s>>>(
         x, y, G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
-        first, atomic_out);
+        op->react, first, atomic_out);
   });
   op->launches++;
   return PMG_OK;
@@ -232,8 +232,10 @@ int run_launches(pmg_laplacian op, const double* x, double* y, int l0, int l1, h
   int issued = 0;
   // the interior as chains: one launch per chain colour instead of the patch colours (the whole interior or nothing;
   // the stored tensor, resident)
+  // (an operator with a reaction term runs the column launches instead: the chain kernel's carried dofs have no
+  // first patch to start from, and the form is opt-in and measured slower -- DESIGN.md section 14)
   const bool chain = op->chain_on && l0 == 0 && l1 >= op->n_launch_l && op->n_launch_l > 0 && !two
-                     && op->batch_patches == 0 && op->geometry_mode == 0;
+                     && op->batch_patches == 0 && op->geometry_mode == 0 && !op->react;
   if (chain)
   {
     PMG_TRY(launch_chains(op, x, y, s));
@@ -298,7 +300,7 @@ int launch_stiffness_restrict(pmg_laplacian op, const TransferView& tv, const do
     constexpr bool AFF = decltype(aff)::value, NT = decltype(nt)::value;
     stiffness_restrict_kernel<P, PC, AFF, NT><<<op->npatch, Shape<P>::WTHREADS, 0, s>>>(
         z, r, coarse, op->G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell,
-        op->kappa, op->D, R);
+        op->kappa, op->D, op->react, R);
   });
   PMG_HIP(hipGetLastError());
   return PMG_OK;
@@ -351,6 +353,7 @@ int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
 const double* laplacian_diag_inv(pmg_laplacian op) { return op->diag_inv; }
+const double* laplacian_reaction(pmg_laplacian op) { return op->react; } // matrix.hip, amg.hip: nullptr = none
 pmg_layout laplacian_layout(pmg_laplacian op) { return op->layout; }
 long long laplacian_launches(pmg_laplacian op) { return op->applies; }
 struct LaplacianInputs
@@ -368,12 +371,14 @@ long long laplacian_capture_state(pmg_laplacian op)
 {
   if (op->profiling)
     return -1;
+  // (reaction term: the first set and the removal change a kernel argument of every apply launch, and which launches
+  // an operator in chain form issues; a later set rewrites the vector in place)
   // (batched geometry: the captured geometry launches carry the field's and the coefficient tensor's addresses -- one
   // epoch counts both; the resident tensor is rebuilt in place by pmg_laplacian_set_coefficient_field / _tensor, so a
   // graph over it stays valid)
   const long long field = op->batch_patches > 0 ? (op->kfield_epoch & 0x3fff) << 44 : 0;
   return ((long long)op->geometry_mode << 40) ^ ((long long)op->batch_patches << 8) ^ (long long)(op->have_diag ? 1 : 0)
-         ^ (long long)(op->chain_on ? 2 : 0) ^ field;
+         ^ (long long)(op->chain_on ? 2 : 0) ^ (long long)(op->react ? 4 : 0) ^ field;
 }
 
 PatchView laplacian_patches(pmg_laplacian op)
@@ -763,6 +768,8 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->Gaff);
   (void)hipFree(op->kfield);
   (void)hipFree(op->ktensor);
+  (void)hipFree(op->react_buf);
+  (void)hipFree(op->react32_buf);
   (void)hipFree(op->W1);
   (void)hipFree(op->dphi_geom);
   (void)hipFree(op->gweights);
@@ -867,7 +874,7 @@ extern "C" int pmg_laplacian_compute_diag_inverse(pmg_laplacian op, pmg_stream s
                                                               op->diag_inv);
   }));
   if (total > 0)
-    diag_invert_kernel<<<(total + 255) / 256, 256, 0, s>>>(total, op->bc, op->diag_inv);
+    diag_invert_kernel<<<(total + 255) / 256, 256, 0, s>>>(total, op->bc, op->react, op->diag_inv);
   PMG_HIP(hipGetLastError());
   op->have_diag = true;
   op->diag_computed = true;
@@ -1034,6 +1041,74 @@ extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const doub
   return PMG_OK;
 }
 
+// number of entries of sigma[0, ncells) that are not finite and >= 0, added to *bad (zeroed by the caller)
+__global__ void reaction_check_kernel(int ncells, const double* __restrict__ sigma, double* __restrict__ bad)
+{
+  int mine = 0;
+  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < ncells;
+       c += (long long)gridDim.x * blockDim.x)
+  {
+    const double v = sigma[c];
+    mine += !(v >= 0.0 && v <= 1.79769313486231570e308); // NaN fails the first comparison, +inf the second
+  }
+  if (mine)
+    atomicAdd(bad, (double)mine);
+}
+
+extern "C" int pmg_laplacian_has_reaction(pmg_laplacian op) { return op ? (op->react ? 1 : 0) : -1; }
+
+extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma, pmg_stream stream)
+{
+  PMG_REQUIRE(op, "pmg_laplacian_set_reaction: NULL argument");
+  hipStream_t s = S(stream);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  PMG_HIP(hipStreamIsCapturing(s, &cap));
+  PMG_REQUIRE(cap == hipStreamCaptureStatusNone,
+              "pmg_laplacian_set_reaction: not inside a stream capture (it allocates and synchronises)");
+  pmg_layout l = op->layout;
+  const int total = l->total();
+  if (!sigma)
+  {
+    if (!op->react)
+      return PMG_OK;
+    op->react = nullptr; // (the allocations stay with the handle: laplacian.hpp)
+    op->react32 = nullptr;
+  }
+  else
+  {
+    // every cell's value finite and >= 0, on every rank (the count is summed over the ranks: all of them refuse, or
+    // none; a cell that is a ghost elsewhere is counted on each rank that holds it)
+    double* bad = red_slot(l, 0);
+    PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
+    if (op->ncells > 0)
+      reaction_check_kernel<<<std::min((op->ncells + 255) / 256, 1024), 256, 0, s>>>(op->ncells, sigma, bad);
+    PMG_HIP(hipGetLastError());
+    PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
+    double nbad = 0.0;
+    PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
+    if (nbad != 0.0)
+      return fail(PMG_ERR_INVALID, "pmg_laplacian_set_reaction: %lld cells have a value that is not finite and >= 0",
+                  (long long)nbad);
+    if (!op->react_buf)
+      PMG_HIP(hipMalloc(&op->react_buf, sizeof(double) * (total ? total : 1)));
+    op->react = op->react_buf;
+    // (summed with atomics in no fixed order: two sets of the same values agree to rounding, not bit for bit)
+    PMG_HIP(hipMemsetAsync(op->react, 0, sizeof(double) * (total ? total : 1), s));
+    const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
+    if (n > 0)
+      reaction_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->N, op->pcell, op->xgeom, op->geom_dofmap,
+                                                                 op->dphi_geom, op->gweights, op->dofmap, op->bc,
+                                                                 sigma, op->react);
+    PMG_HIP(hipGetLastError());
+  }
+  // what depends on the vector, each in its own buffer
+  PMG_TRY(laplacian_f32_reaction(op, s));
+  if (op->have_diag && op->diag_computed)
+    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
+  PMG_HIP(hipStreamSynchronize(s)); // the caller may free sigma on return
+  return PMG_OK;
+}
+
 extern "C" int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream stream)
 {
   PMG_REQUIRE(op && G_out, "pmg_laplacian_get_geometry: NULL argument");
@@ -1174,7 +1249,8 @@ extern "C" int pmg_laplacian_launches_per_apply(pmg_laplacian op)
   if (!op)
     return -1;
   int n = 0;
-  const bool chain = op->chain_on && op->batch_patches == 0 && op->geometry_mode == 0 && op->launch_stream.empty();
+  const bool chain = op->chain_on && op->batch_patches == 0 && op->geometry_mode == 0 && op->launch_stream.empty()
+                     && !op->react;
   for (size_t l = chain ? (size_t)op->n_launch_l : 0; l < op->launch_count.size(); ++l)
     n += op->launch_count[l] > 0;
   if (chain)

@@ -31,6 +31,17 @@ struct pmg_laplacian_s
   // coordinates, (xx, xy, xz, yy, yz, zz); folded into G, the float tensor and Gaff where they are built
   // (G_q = adj(J) K_c adj(J)^T w_q / detJ); nullptr = none.  Allocating or freeing it bumps kfield_epoch.
   double* ktensor = nullptr;   // [ncells][6]
+  // reaction term (pmg_laplacian_set_reaction): y = A x + react .* x on unmarked rows.  GLL collocation makes the mass
+  // matrix diagonal, so the term is one vector, react[dof] = sum over the listed cells' points on the dof of
+  // sigma_c w_q detJ_q (0 on marked dofs); it does not depend on G.  The apply kernels start the first patch's
+  // accumulator of a dof at react[dof] * x[dof] (stiffness_column.hpp); nullptr = none.
+  double* react = nullptr;     // [size_local + num_ghosts], ghost entries as diag_inv's: this rank's cells only
+  float* react32 = nullptr;    // float copy, present while react and the float tensor G32 both are
+  // the two allocations behind them, made on first need and kept until the handle goes: a term that is removed and set
+  // again has its vectors where a captured graph of the first one read them (laplacian_capture_state tells set from
+  // removed, not one allocation from the next)
+  double* react_buf = nullptr;
+  float* react32_buf = nullptr;
   bool diag_computed = false;  // diag_inv came from pmg_laplacian_compute_diag_inverse (it follows a change of field)
   double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell (K Kc K^T / detJ with a coefficient tensor)
   double* W1 = nullptr;        // [nd] 1-D GLL weights

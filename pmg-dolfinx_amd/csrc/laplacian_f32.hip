@@ -106,7 +106,8 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
                          const int32_t* __restrict__ poff, const uint32_t* __restrict__ pdofs,
                          const int32_t* __restrict__ lmap_id, const uint16_t* __restrict__ lmaps,
                          const int32_t* __restrict__ pcell, const int32_t* __restrict__ pncell,
-                         const double* __restrict__ kappa, const float* __restrict__ Dg, int first, int atomic_out)
+                         const double* __restrict__ kappa, const float* __restrict__ Dg,
+                         const float* __restrict__ react, int first, int atomic_out)
 {
   using Sh = Shape32<P>;
   constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, NG = Sh::NG, WPC = Sh::WPC, WL = Sh::WL;
@@ -145,7 +146,8 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
       const uint32_t dof = m[k] & PD_MASK;
       const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
       xv[k] = x[dof];
-      yv[k] = *(acc ? (const float*)(y + dof) : x + dof);
+      // (no sum to continue: the reaction vector where the operator has one, else x again -- stiffness_column.hpp)
+      yv[k] = *(acc ? (const float*)(y + dof) : react ? react + dof : x + dof);
     }
 #pragma unroll
     for (int k = 0; k < ITER; ++k)
@@ -155,7 +157,8 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
       {
         const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
         sx[i] = (m[k] & PD_BC) ? 0.0f : xv[k];
-        sy[i] = acc ? yv[k] : 0.0f;
+        const bool starts = react && !(m[k] & (PD_ACC | PD_BC)); // the dof's first patch starts at react * x
+        sy[i] = acc ? yv[k] : starts ? yv[k] * xv[k] : 0.0f;
       }
     }
   }
@@ -283,11 +286,11 @@ void launch_f32(pmg_laplacian op, const float* x, float* y, int first, int count
   if (nt)
     stiffness_f32_kernel<P, true><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
                                                                       op->lmap_id, op->lmaps, op->pcell, op->pncell,
-                                                                      op->kappa, op->D32, first, atomic_out);
+                                                                      op->kappa, op->D32, op->react32, first, atomic_out);
   else
     stiffness_f32_kernel<P, false><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
                                                                        op->lmap_id, op->lmaps, op->pcell, op->pncell,
-                                                                       op->kappa, op->D32, first, atomic_out);
+                                                                       op->kappa, op->D32, op->react32, first, atomic_out);
 }
 
 int launch_patches_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, bool nt,
@@ -338,6 +341,22 @@ int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s)
   return PMG_OK;
 }
 
+// The float copy of the reaction vector: in use exactly while the vector and the float tensor both exist (allocated
+// once, rewritten in place by a later set; pmg_laplacian_set_reaction(op, NULL) takes it out of use with the vector)
+int laplacian_f32_reaction(pmg_laplacian op, hipStream_t s)
+{
+  if (!op->G32 || !op->react)
+    return PMG_OK;
+  const int total = op->layout->total();
+  if (!op->react32_buf)
+    PMG_HIP(hipMalloc(&op->react32_buf, sizeof(float) * (total ? total : 1)));
+  op->react32 = op->react32_buf;
+  if (total > 0)
+    to_float_kernel<<<grid_for(total), 256, 0, s>>>(total, op->react, op->react32);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
 // The float tensor and 1-D table, built on the first FP32 use (outside any stream capture: it allocates)
 int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
 {
@@ -347,6 +366,7 @@ int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
   PMG_HIP(hipMalloc(&op->G32, sizeof(float2) * 3 * (size_t)(n > 0 ? n : 1)));
   PMG_HIP(hipMalloc(&op->D32, sizeof(float) * op->nd * op->nd));
   to_float_kernel<<<1, 256, 0, s>>>(op->nd * op->nd, op->D, op->D32);
+  PMG_TRY(laplacian_f32_reaction(op, s));
   return laplacian_f32_refresh(op, s);
 }
 

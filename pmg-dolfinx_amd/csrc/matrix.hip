@@ -24,6 +24,7 @@ using namespace pmg;
 namespace pmg
 {
 int laplacian_geometry_ascending(pmg_laplacian op, double* G_out, hipStream_t s); // laplacian.hip
+const double* laplacian_reaction(pmg_laplacian op);                               // laplacian.hip; nullptr = none
 }
 
 struct pmg_matrix_s
@@ -92,7 +93,8 @@ __global__ void __launch_bounds__(256)
                          double* __restrict__ vals, double* __restrict__ dinv, const int32_t* __restrict__ inc_off,
                          const int32_t* __restrict__ inc_cell, const int32_t* __restrict__ inc_loc,
                          const int32_t* __restrict__ dofmap, const double* __restrict__ Gc,
-                         const double* __restrict__ kappa, const int8_t* __restrict__ bc, const double* __restrict__ Dg)
+                         const double* __restrict__ kappa, const int8_t* __restrict__ bc, const double* __restrict__ Dg,
+                         const double* __restrict__ react)
 {
   constexpr int NSQ = ND * ND, N = NSQ * ND;
   extern __shared__ double lds[];
@@ -117,6 +119,7 @@ __global__ void __launch_bounds__(256)
       acc[dpos] = 1.0;
   }
   else
+  {
     for (int m = inc_off[row]; m < inc_off[row + 1]; ++m)
     {
       const int cell = inc_cell[m], t = inc_loc[m];
@@ -156,6 +159,10 @@ __global__ void __launch_bounds__(256)
       }
       __builtin_amdgcn_wave_barrier(); // the next cell's updates stay behind this cell's
     }
+    // the reaction term of the operator (pmg_laplacian_set_reaction): diagonal, unmarked rows only
+    if (react && sub == 0)
+      acc[dpos] += react[row];
+  }
   __builtin_amdgcn_wave_barrier();
   for (int k = sub; k < len; k += W)
     vals[rs + k] = acc[k];
@@ -216,7 +223,7 @@ void launch_values(pmg_matrix M, int W, int groups, size_t lds, const double* Gc
   const pmg_laplacian op = M->op;
   matrix_values_kernel<ND><<<(M->n + groups - 1) / groups, W * groups, lds, s>>>(
       M->n, W, M->cap, M->rp, M->ci, M->v, M->dinv, M->inc_off, M->inc_cell, M->inc_loc, op->dofmap, Gc, op->kappa,
-      op->bc, op->D);
+      op->bc, op->D, laplacian_reaction(op));
 }
 
 int check_source(pmg_laplacian op, const char* who)

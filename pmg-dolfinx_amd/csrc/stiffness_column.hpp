@@ -169,7 +169,8 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
                             const int32_t* __restrict__ lmap_id,
                             const uint16_t* __restrict__ lmaps, const int32_t* __restrict__ pcell,
                             const int32_t* __restrict__ pncell, const double* __restrict__ kappa,
-                            const double* __restrict__ Dg, int first, int atomic_out)
+                            const double* __restrict__ Dg, const double* __restrict__ react, int first,
+                            int atomic_out)
 {
   using Sh = Shape<P>;
   constexpr int ND = Sh::ND, N = Sh::N, K = Sh::K, NQ2 = Sh::NQ2, CW = Sh::CW, NG = Sh::NG, WPC = Sh::WPC;
@@ -222,7 +223,9 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
       const uint32_t dof = m[k] & PD_MASK;
       const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
       xv[k] = x[dof];
-      const double* ya = acc ? (const double*)(y + dof) : (x + dof);
+      // (an entry that does not accumulate loads all the same: the reaction vector where the operator has one --
+      // `react` is a kernel argument, the branch wave-uniform -- and otherwise x again, an L2-hot dummy)
+      const double* ya = acc ? (const double*)(y + dof) : react ? (react + dof) : (x + dof);
       yv[k] = *ya;
     }
     const double kapk = kappa[cellk >= 0 ? cellk : 0];
@@ -234,7 +237,10 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
       {
         const bool acc = !atomic_out && (m[k] & (PD_ACC | PD_BC)) == PD_ACC;
         sx[i] = (m[k] & PD_BC) ? 0.0 : xv[k]; // src/laplacian.hpp:186-189
-        sy[i] = acc ? yv[k] : 0.0;
+        // the dof's FIRST patch (PD_ACC clear, in coloured and merged launches alike: patches.hpp) starts its sum at
+        // the reaction term react[dof] * x[dof]; Dirichlet rows carry none (y = x)
+        const bool starts = react && !(m[k] & (PD_ACC | PD_BC));
+        sy[i] = acc ? yv[k] : starts ? yv[k] * xv[k] : 0.0;
         if constexpr (LIST_IN_LDS)
           sm[i] = m[k];
       }

@@ -8,7 +8,8 @@
 // The patch workgroup of the apply therefore restricts each cell's own contribution straight from its registers: it
 // never sums into the fine output, never writes q and never waits on a colour -- all patches of the operator go in ONE
 // launch.  On Dirichlet rows the apply's rule is q = z (stiffness_column.hpp, patch_write_back), so their share is
-// (r - z) / mult and the cell's product is dropped there.
+// (r - z) / mult and the cell's product is dropped there.  A reaction term (pmg_laplacian_set_reaction) is diagonal:
+// r - (A + D) z = (r - d z) - A z, so the unmarked rows' share is (r - d z) / mult and nothing else moves.
 //
 // The gather and the cell loop follow stiffness_column_kernel (WPC == 1 shapes without the transposition identity); the
 // layer march, the lane's table rows, the tensor stream and the packed positions are the shared ones of
@@ -56,7 +57,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
                               const uint32_t* __restrict__ pdofs, const int32_t* __restrict__ lmap_id,
                               const uint16_t* __restrict__ lmaps, const int32_t* __restrict__ pcell,
                               const int32_t* __restrict__ pncell, const double* __restrict__ kappa,
-                              const double* __restrict__ Dg, RestrictLists R)
+                              const double* __restrict__ Dg, const double* __restrict__ react, RestrictLists R)
 {
   using Sh = Shape<P>;
   using Rs = RestrictShape<P, PC>;
@@ -121,6 +122,17 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
       {
         sx[i] = bc ? 0.0 : zv[k];                                   // src/laplacian.hpp:186-189
         sy[i] = (bc ? rv[k] - zv[k] : rv[k]) / (double)mu[k];       // src/interpolate.hpp:81-82
+      }
+      // reaction term (wave-uniform branch on the kernel argument): the residual is r - (A + D) z = (r - d z) - A z.
+      // Every cell that holds the dof adds its share once, in whichever patch it lies, so the diagonal part is
+      // spread like r itself: the share of an unmarked row becomes (r - d z) / mult in every patch -- not a start
+      // value of the dof's first patch as in the column kernel, whose accumulator is per dof where this one is per
+      // cell.  Loaded here, behind the other gathers, so that no third array of registers is held.
+      if (react)
+      {
+        const double dv = react[m[k] & PD_MASK];
+        if (i < M && !bc)
+          sy[i] = (rv[k] - dv * zv[k]) / (double)mu[k];
       }
       const unsigned long long rows = __builtin_amdgcn_ballot_w64(bc); // the wave's entries are i & ~63 .. + 63
       if ((t & 63) == 0)

@@ -192,6 +192,32 @@ class MatFreeLaplacian:
     def has_coefficient_tensor(self) -> bool:
         return bool(call("pmg_laplacian_has_coefficient_tensor", self._handle))
 
+    def set_reaction(self, sigma):
+        """Per-cell reaction coefficient (``pmg_laplacian_set_reaction``): the operator becomes
+        -div(K grad u) + sigma u, i.e. y = A x + d * x on unmarked rows with the lumped (GLL) mass vector d of sigma.
+        ``sigma`` is a float64 numpy array (uploaded here) or torch tensor of shape ``(ncells,)``, one finite value
+        >= 0 per local cell, ghost cells included; or ``None`` to remove the term.  The library keeps d, not sigma.  A
+        computed inverse diagonal is rebuilt; not inside a stream capture."""
+        import torch
+
+        if sigma is None:
+            call("pmg_laplacian_set_reaction", self._handle, None, current_stream())
+            return
+        if not isinstance(sigma, (np.ndarray, torch.Tensor)):
+            raise TypeError("set_reaction takes a float64 numpy array or torch tensor, or None")
+        if sigma.dtype not in (np.float64, torch.float64):
+            raise TypeError(f"the reaction coefficient must be float64, not {sigma.dtype}")
+        if tuple(sigma.shape) != (self.ncells,):
+            raise ValueError(f"the reaction coefficient has shape {tuple(sigma.shape)}, the operator needs "
+                             f"({self.ncells},)")
+        if isinstance(sigma, np.ndarray):
+            sigma = torch.from_numpy(np.ascontiguousarray(sigma))
+        sigma = sigma.to(self.layout.device).contiguous()
+        call("pmg_laplacian_set_reaction", self._handle, ptr(sigma), current_stream())
+
+    def has_reaction(self) -> bool:
+        return bool(call("pmg_laplacian_has_reaction", self._handle))
+
     def geometry(self):
         """G in the reference layout [ncells, nq, 6] (device tensor), as the kernels read it (with the
         coefficient field and the coefficient tensor, if set)."""

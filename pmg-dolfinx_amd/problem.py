@@ -26,7 +26,7 @@ class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
                  node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None,
-                 kappa_tensor=None):
+                 kappa_tensor=None, reaction=None):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
@@ -36,6 +36,11 @@ class PoissonHierarchy:
         vertices) to ``[ncells, 6]``, one symmetric positive-definite diffusion tensor per cell as
         (xx, xy, xz, yy, yz, zz); it is set on every level's operator
         (``MatFreeLaplacian.set_coefficient_tensor``) beside ``kappa_field``, before the diagonal and the eigenvalue
+        estimate.
+
+        ``reaction`` (optional): a callable mapping cell centres ``[ncells, 3]`` to ``[ncells]``, one reaction
+        coefficient sigma >= 0 per cell; every level's operator becomes -div(K grad u) + sigma u
+        (``MatFreeLaplacian.set_reaction``), set next to ``kappa_tensor``, before the diagonal and the eigenvalue
         estimate.
 
         ``dirichlet`` (optional): a callable mapping dof coordinates ``[n, 3]`` to a boolean array; on every level
@@ -63,6 +68,10 @@ class PoissonHierarchy:
         if kappa_tensor is not None:  # the cells are the same on every level
             centres = part.xgeom[part.geom_dofmap].mean(axis=1)
             ktensor = torch.from_numpy(np.ascontiguousarray(kappa_tensor(centres), dtype=np.float64)).to(dev)
+        sigma = None
+        if reaction is not None:
+            centres = part.xgeom[part.geom_dofmap].mean(axis=1)
+            sigma = torch.from_numpy(np.ascontiguousarray(reaction(centres), dtype=np.float64).reshape(-1)).to(dev)
         for P in self.orders:
             lv = part.level(P)
             if level_hook is not None:  # bench.py --corrupt-halo: a deliberately wrong halo plan for the gate's own test
@@ -86,6 +95,8 @@ class PoissonHierarchy:
                 del kq
             if ktensor is not None:
                 op.set_coefficient_tensor(ktensor)
+            if sigma is not None:
+                op.set_reaction(sigma)
             op.compute_diag_inverse()  # replaces :274-279
             self.levels.append(lv)
             self.layouts.append(layout)
