@@ -50,24 +50,6 @@
 
 using namespace pmg;
 
-namespace pmg
-{
-int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
-const double* laplacian_diag_inv(pmg_laplacian op);
-const double* laplacian_reaction(pmg_laplacian op); // nullptr = none
-pmg_layout laplacian_layout(pmg_laplacian op);
-PatchView laplacian_patches(pmg_laplacian op);
-struct LaplacianInputs
-{
-  int degree;
-  int32_t ncells;
-  const int32_t* dofmap; // device
-  const int8_t* bc;      // device
-  const double* kappa;   // device
-};
-LaplacianInputs laplacian_inputs(pmg_laplacian op);
-} // namespace pmg
-
 namespace
 {
 struct StageTimer

@@ -240,18 +240,10 @@ extern "C" int pmg_laplacian_apply_lifting(pmg_laplacian op, double* g, const do
   PMG_TRY(scatter_fwd_whole(op->layout, g, s)); // ghosts of g (side effect, as pmg_laplacian_apply has on `in`)
   if (op->n_lift == 0)
     return PMG_OK;
-  switch (op->nd)
-  {
-  case 2: launch_lifting<2>(op, g, x0, alpha, b, s); break;
-  case 3: launch_lifting<3>(op, g, x0, alpha, b, s); break;
-  case 4: launch_lifting<4>(op, g, x0, alpha, b, s); break;
-  case 5: launch_lifting<5>(op, g, x0, alpha, b, s); break;
-  case 6: launch_lifting<6>(op, g, x0, alpha, b, s); break;
-  case 7: launch_lifting<7>(op, g, x0, alpha, b, s); break;
-  case 8: launch_lifting<8>(op, g, x0, alpha, b, s); break;
-  case 9: launch_lifting<9>(op, g, x0, alpha, b, s); break;
-  default: return fail(PMG_ERR_INVALID, "pmg_laplacian_apply_lifting: unsupported degree");
-  }
+  PMG_TRY(with_degree(op->P, [&](auto P) {
+    launch_lifting<decltype(P)::value + 1>(op, g, x0, alpha, b, s);
+    return PMG_OK;
+  }));
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace pmg
@@ -54,6 +55,25 @@ int upload(T** dst, const T* src, size_t n, hipStream_t s)
 }
 
 constexpr int MAXND = PMG_MAX_DEGREE + 1;
+
+// f(std::integral_constant<int, P>{}) -> int for the run-time degree P: the one dispatch onto the kernels' degree
+template <typename F>
+int with_degree(int P, F&& f)
+{
+  switch (P)
+  {
+  case 1: return f(std::integral_constant<int, 1>{});
+  case 2: return f(std::integral_constant<int, 2>{});
+  case 3: return f(std::integral_constant<int, 3>{});
+  case 4: return f(std::integral_constant<int, 4>{});
+  case 5: return f(std::integral_constant<int, 5>{});
+  case 6: return f(std::integral_constant<int, 6>{});
+  case 7: return f(std::integral_constant<int, 7>{});
+  case 8: return f(std::integral_constant<int, 8>{});
+  default: return fail(PMG_ERR_INVALID, "Unsupported degree"); // src/laplacian.hpp:346,479
+  }
+}
+static_assert(PMG_MAX_DEGREE == 8, "with_degree lists the degrees");
 
 // 1-D tables on the host (tables.cpp)
 void gll_table(int n, double* x, double* w);
@@ -285,6 +305,46 @@ void launch_cg_update2(int n, double* x, double* r, const double* p, const doubl
                        const double* d_py, hipStream_t s);
 void launch_cg_direction(int n, double* p, const double* y, double rnorm, const double* d_new,
                          const double* d_sub, hipStream_t s);
+
+// laplacian.hip -- the matrix-free operator, as the solvers, the AMG set-up and the assembled operator use it
+int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
+int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
+int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
+bool laplacian_wants_zeroed_output(pmg_laplacian op);
+const double* laplacian_diag_inv(pmg_laplacian op);
+const double* laplacian_reaction(pmg_laplacian op); // nullptr = none
+pmg_layout laplacian_layout(pmg_laplacian op);
+long long laplacian_launches(pmg_laplacian op);
+long long laplacian_capture_state(pmg_laplacian op); // -1 = not capturable right now
+int laplacian_geometry_ascending(pmg_laplacian op, double* G_out, hipStream_t s);
+struct LaplacianInputs
+{
+  int degree;
+  int32_t ncells;
+  const int32_t* dofmap; // device
+  const int8_t* bc;      // device
+  const double* kappa;   // device
+};
+LaplacianInputs laplacian_inputs(pmg_laplacian op);
+// interpolate.hip -- the p-transfers of the V-cycle
+int interp_prolong(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s);
+int interp_restrict(pmg_interpolator ip, double* fine, double* coarse, hipStream_t s);
+int interp_prolong_add(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s);
+bool interp_is_patched(pmg_interpolator ip);
+bool interp_restricts_difference(pmg_interpolator ip);
+int interp_restrict_difference(pmg_interpolator ip, double* fine, const double* fine_sub, double* coarse,
+                               hipStream_t s);
+bool interp_fuses_residual(pmg_interpolator ip, pmg_laplacian op);
+int interp_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z, const double* r, double* coarse,
+                             hipStream_t s);
+// amg.hip -- the coarse solver
+int amg_solve(pmg_amg amg, double* x, const double* b, hipStream_t s);
+pmg_layout amg_layout(pmg_amg amg);
+long long amg_capture_state(pmg_amg amg);
+// matrix.hip -- the assembled form of a level's operator
+int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s);
+const double* matrix_diag_inv(pmg_matrix M);
+pmg_layout matrix_layout(pmg_matrix M);
 
 // ---- the FP32 V-cycle (pmg_multigrid_set_precision; single domain only) ----
 // It runs the smoother loop, the vector passes and the patch-form transfer kernels of the FP64 cycle instantiated for

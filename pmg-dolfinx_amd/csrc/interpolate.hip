@@ -20,15 +20,6 @@
 
 using namespace pmg;
 
-namespace pmg
-{
-PatchView laplacian_patches(pmg_laplacian op);
-pmg_layout laplacian_layout(pmg_laplacian op);
-bool laplacian_fuses_restriction(pmg_laplacian op, int coarse_degree);
-int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const double* z, const double* r,
-                             double* coarse, hipStream_t s);
-}
-
 struct pmg_interpolator_s
 {
   pmg_layout lc = nullptr, lf = nullptr;

@@ -99,17 +99,6 @@ int for_each_geometry_chunk(pmg_laplacian op, hipStream_t s, F f)
   return PMG_OK;
 }
 
-// tensor bytes above which the stream is non-temporal.  The Infinity Cache holds 256 MiB, but inside a V-cycle the
-// smoother's vectors pass through it between two applications: measured per cycle, default / nt policy, at 24^3
-// cells (83 MB) 0.417 / 0.445 ms, 32^3 (196 MB) 0.821 / 0.809, 40^3 1.59 / 1.46, 64^3 5.71 / 5.10.
-// PMG_STREAM_POLICY=0 / 1 forces the default / the streaming policy (measurements).
-bool streams_past_the_cache(long long tensor_bytes)
-{
-  if (const char* e = std::getenv("PMG_STREAM_POLICY"))
-    return e[0] != '0';
-  return tensor_bytes > (128LL << 20);
-}
-
 // The (AFF, NT) instantiation of an apply kernel that an operator runs, chosen in one place: launch(AFF, NT) is called
 // with the two as std::bool_constant.  Cache policy: a tensor that is read once per application and is larger than the
 // Infinity Cache is streamed (nt), so that it does not displace x, y and the tables; a tensor that fits stays resident
@@ -151,138 +140,44 @@ int launch_stiffness(pmg_laplacian op, const double* x, double* y, int first, in
   return PMG_OK;
 }
 
-// one launch of the stiffness kernel over patches [first, first + count)
-static int launch_patches(pmg_laplacian op, const double* x, double* y, int first, int count, int atomic_out,
-                          hipStream_t s)
-{
-  switch (op->P)
-  {
-  case 1:
-    return launch_stiffness<1>(op, x, y, first, count, atomic_out, s);
-  case 2:
-    return launch_stiffness<2>(op, x, y, first, count, atomic_out, s);
-  case 3:
-    return launch_stiffness<3>(op, x, y, first, count, atomic_out, s);
-  case 4:
-    return launch_stiffness<4>(op, x, y, first, count, atomic_out, s);
-  case 5:
-    return launch_stiffness<5>(op, x, y, first, count, atomic_out, s);
-  case 6:
-    return launch_stiffness<6>(op, x, y, first, count, atomic_out, s);
-  case 7:
-    return launch_stiffness<7>(op, x, y, first, count, atomic_out, s);
-  case 8:
-    return launch_stiffness<8>(op, x, y, first, count, atomic_out, s);
-  default:
-    return fail(PMG_ERR_INVALID, "Unsupported degree"); // src/laplacian.hpp:346,479
-  }
-}
-
-// the interior of one application as chains: one launch per chain colour (stiffness_chain_kernel)
-static int launch_chains(pmg_laplacian op, const double* x, double* y, hipStream_t s)
+// the chains [first, first + count) of one chain colour (stiffness_chain_kernel)
+static int launch_chains(pmg_laplacian op, const double* x, double* y, int first, int count, hipStream_t s)
 {
   if constexpr (chain_form(4))
   {
     if (op->P != 4)
       return fail(PMG_ERR_INVALID, "internal: chain form at degree %d", op->P);
-    const bool nt = op->stream_policy;
-    for (size_t c = 0; c < op->chain_count.size(); ++c)
-    {
-      if (op->chain_count[c] <= 0)
-        continue;
-      if (nt)
-        stiffness_chain_kernel<4, true><<<op->chain_count[c], ChainShape<4>::THREADS, 0, s>>>(
-            x, y, op->G, op->poff, op->cdofs, op->ccar, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
-            op->chain_off, op->chain_patch, op->chain_first[c]);
-      else
-        stiffness_chain_kernel<4, false><<<op->chain_count[c], ChainShape<4>::THREADS, 0, s>>>(
-            x, y, op->G, op->poff, op->cdofs, op->ccar, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
-            op->chain_off, op->chain_patch, op->chain_first[c]);
-      op->launches++;
-    }
+    auto launch = [&](auto nt) {
+      stiffness_chain_kernel<4, decltype(nt)::value><<<count, ChainShape<4>::THREADS, 0, s>>>(
+          x, y, op->G, op->poff, op->cdofs, op->ccar, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
+          op->chain_off, op->chain_patch, first);
+    };
+    op->stream_policy ? launch(std::true_type{}) : launch(std::false_type{});
+    op->launches++;
   }
   return PMG_OK;
+}
+
+// The form of an application, from everything in the operator's state that bears on it.  Two streams need the resident
+// tensor.  Chains need it too, in the stored (not the affine) mode, and no reaction term: the chain kernel's carried
+// dofs have no first patch to start from, and the form is opt-in and measured slower.
+ApplyForm apply_form(pmg_laplacian op)
+{
+  const bool resident = op->batch_patches == 0;
+  return {resident && !op->launch_stream.empty(),
+          resident && op->chain_on && op->geometry_mode == 0 && !op->react, resident};
 }
 
 // launches [l0, l1) of the plan, in stream order
 int run_launches(pmg_laplacian op, const double* x, double* y, int l0, int l1, hipStream_t s)
 {
-  const bool prof = op->profiling && l1 > l0;
-  if (prof)
-  {
-    if (op->prof_used + 2 > op->prof_events.size())
-    {
-      hipEvent_t a, b;
-      PMG_HIP(hipEventCreate(&a));
-      op->prof_events.push_back(a);
-      PMG_HIP(hipEventCreate(&b));
-      op->prof_events.push_back(b);
-    }
-    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used], s));
-  }
-  // Two halves of the interior: the launches of the second half go to the operator's second stream, forked from and
-  // joined to `s` with events (inside a stream capture these become two branches of the graph).  One ordering event
-  // between the halves: patches.hip.
-  const bool two = !op->launch_stream.empty() && l0 == 0 && l1 >= op->n_launch_l && l1 > l0 && op->batch_patches == 0;
-  if (two)
-  {
-    PMG_HIP(hipEventRecord(op->ev_fork, s));
-    PMG_HIP(hipStreamWaitEvent(op->stream2, op->ev_fork, 0));
-  }
-  int issued = 0;
-  // the interior as chains: one launch per chain colour instead of the patch colours (the whole interior or nothing;
-  // the stored tensor, resident)
-  // (an operator with a reaction term runs the column launches instead: the chain kernel's carried dofs have no
-  // first patch to start from, and the form is opt-in and measured slower -- DESIGN.md section 14)
-  const bool chain = op->chain_on && l0 == 0 && l1 >= op->n_launch_l && op->n_launch_l > 0 && !two
-                     && op->batch_patches == 0 && op->geometry_mode == 0 && !op->react;
-  if (chain)
-  {
-    PMG_TRY(launch_chains(op, x, y, s));
-    issued += (int)op->chain_count.size();
-    l0 = op->n_launch_l;
-  }
-  auto join = [&]() -> int {
-    PMG_HIP(hipEventRecord(op->ev_join, op->stream2));
-    PMG_HIP(hipStreamWaitEvent(s, op->ev_join, 0));
-    return PMG_OK;
-  };
-  for (int l = l0; l < l1; ++l)
-  {
-    int first = op->launch_first[l], count = op->launch_count[l];
-    const int atomic_out = (l >= op->n_plain) ? 1 : 0; // merged launches add with atomics
-    hipStream_t sl = s;
-    if (two && l < op->n_launch_l)
-    {
-      if (l == op->launch_wait)
-        PMG_HIP(hipStreamWaitEvent(s, op->ev_order, 0));
-      sl = op->launch_stream[l] ? op->stream2 : s;
-    }
-    if (two && l == op->n_launch_l)
-      PMG_TRY(join());
-    // consecutive atomic launches over contiguous patches that the caller asked for together: one launch
-    while (atomic_out && l + 1 < l1 && op->launch_first[l + 1] == first + count && !two && op->batch_patches == 0)
-      count += op->launch_count[++l];
-    if (count > 0)
-    {
-      PMG_TRY(launch_patches(op, x, y, first, count, atomic_out, sl));
-      ++issued;
-    }
-    if (two && l == op->launch_signal)
-    {
-      PMG_HIP(hipEventRecord(op->ev_order, op->stream2));
-    }
-  }
-  if (two && l1 == op->n_launch_l)
-    PMG_TRY(join());
-  PMG_HIP(hipGetLastError());
-  if (prof)
-  {
-    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used + 1], s));
-    op->prof_used += 2;
-    op->prof_launches += issued;
-  }
-  return PMG_OK;
+  return walk_launches(op, l0, l1, apply_form(op), s, [&](const LaunchStep& st, hipStream_t sl) {
+    if (st.kind == LaunchStep::CHAINS)
+      return launch_chains(op, x, y, st.first, st.count, sl);
+    return with_degree(op->P, [&](auto P) {
+      return launch_stiffness<decltype(P)::value>(op, x, y, st.first, st.count, st.atomic_out, sl);
+    });
+  });
 }
 
 // (fine degree, coarse degree) pairs stiffness_restrict_kernel is instantiated for
@@ -310,6 +205,17 @@ int launch_stiffness_restrict(pmg_laplacian op, const TransferView& tv, const do
 
 namespace pmg
 {
+// tensor bytes above which the stream is non-temporal.  The Infinity Cache holds 256 MiB, but inside a V-cycle the
+// smoother's vectors pass through it between two applications: measured per cycle, default / nt policy, at 24^3
+// cells (83 MB) 0.417 / 0.445 ms, 32^3 (196 MB) 0.821 / 0.809, 40^3 1.59 / 1.46, 64^3 5.71 / 5.10.
+// PMG_STREAM_POLICY=0 / 1 forces the default / the streaming policy (measurements).
+bool streams_past_the_cache(long long tensor_bytes)
+{
+  if (const char* e = std::getenv("PMG_STREAM_POLICY"))
+    return e[0] != '0';
+  return tensor_bytes > (128LL << 20);
+}
+
 // Is the fused apply-and-restrict available on this operator towards degree `coarse_degree`?  (pmg_amd.h,
 // pmg_interpolator_restrict_residual: no ghosts, resident geometry, an instantiated pair -- which leaves out the
 // shared-item degrees 5 and 8)
@@ -348,22 +254,10 @@ int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const dou
   return PMG_OK;
 }
 
-// used by solvers.hip
-int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
-int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
-int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
 const double* laplacian_diag_inv(pmg_laplacian op) { return op->diag_inv; }
 const double* laplacian_reaction(pmg_laplacian op) { return op->react; } // matrix.hip, amg.hip: nullptr = none
 pmg_layout laplacian_layout(pmg_laplacian op) { return op->layout; }
 long long laplacian_launches(pmg_laplacian op) { return op->applies; }
-struct LaplacianInputs
-{
-  int degree;
-  int32_t ncells;
-  const int32_t* dofmap;
-  const int8_t* bc;
-  const double* kappa;
-};
 LaplacianInputs laplacian_inputs(pmg_laplacian op) { return {op->P, op->ncells, op->dofmap, op->bc, op->kappa}; }
 
 // what a captured graph of launches of this operator depends on; -1 = not capturable right now
@@ -408,19 +302,26 @@ PatchView laplacian_patches(pmg_laplacian op)
 // Does an application zero-fill its whole output first (every first writer adds with atomics: the merged launch of a
 // small level)?  Then a caller that hands over an output that is zero already can skip the fill
 // (laplacian_apply_zeroed; the smoother's vector kernels clear the vector behind themselves).
-static bool zero_fills_output(pmg_laplacian op)
+bool laplacian_wants_zeroed_output(pmg_laplacian op)
 {
-  return op->needs_zero || op->launch_first.empty() || 2LL * op->n_bzero > op->layout->total();
+  return zero_fills_output(op->needs_zero, op->launch_first.size(), op->n_bzero, op->layout->total());
 }
-bool laplacian_wants_zeroed_output(pmg_laplacian op) { return zero_fills_output(op); }
 
 // Interior and boundary patches in ONE launch behind a whole exchange?  Only where both lists add with atomics
-// anyway (n_plain == 0: the merged form of a small level), the geometry is resident, and the layout's exchange is one
-// launch (halo windows).  The transfers of the level follow the operator (interpolate.hip).
+// anyway (the merged form of a small level) and the geometry is resident -- the two launches of the plan, walked whole,
+// are then one step over all patches -- and the layout's exchange is one launch (halo windows).  The transfers of the
+// level follow the operator (interpolate.hip).
 bool laplacian_single_launch(pmg_laplacian op)
 {
-  return op->n_plain == 0 && op->batch_patches == 0 && (int)op->launch_first.size() == 2
-         && op->launch_first[1] == op->launch_first[0] + op->launch_count[0] && layout_exchanges_whole(op->layout);
+  if (op->launch_first.size() != 2)
+    return false;
+  int steps = 0, all = 0;
+  for_each_launch_step(*op, op->chain_first, op->chain_count, 0, 2, apply_form(op), [&](const LaunchStep& st) {
+    steps += st.launches();
+    all += st.kind == LaunchStep::PATCHES && st.atomic_out && st.count == op->npatch;
+    return PMG_OK;
+  });
+  return steps == 1 && all == 1 && layout_exchanges_whole(op->layout);
 }
 
 // operator()(in, out), src/laplacian.hpp:462-482 + impl_operator :373-460
@@ -431,7 +332,7 @@ static int apply_impl(pmg_laplacian op, double* in, double* out, bool out_is_zer
   const int nl = (int)op->launch_first.size();
   // :466 -- but only where needed: dofs no patch touches, or (most of the vector) dofs whose
   // first writer adds with atomics; everything else is stored by its first writer
-  const bool zero_all = zero_fills_output(op);
+  const bool zero_all = laplacian_wants_zeroed_output(op);
   if (zero_all && !out_is_zero)
     launch_zero(l->total(), out, s);
   if (op->n_bzero > 0 && !zero_all)
@@ -467,7 +368,7 @@ int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hi
 // `out` is zero over the whole layout already (only meaningful when laplacian_wants_zeroed_output)
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s)
 {
-  return apply_impl(op, in, out, zero_fills_output(op), s);
+  return apply_impl(op, in, out, laplacian_wants_zeroed_output(op), s);
 }
 } // namespace pmg
 
@@ -1248,14 +1149,12 @@ extern "C" int pmg_laplacian_launches_per_apply(pmg_laplacian op)
 {
   if (!op)
     return -1;
+  // (the two walks of apply_impl; a whole walk may coalesce them: laplacian_single_launch)
   int n = 0;
-  const bool chain = op->chain_on && op->batch_patches == 0 && op->geometry_mode == 0 && op->launch_stream.empty()
-                     && !op->react;
-  for (size_t l = chain ? (size_t)op->n_launch_l : 0; l < op->launch_count.size(); ++l)
-    n += op->launch_count[l] > 0;
-  if (chain)
-    for (int32_t c : op->chain_count)
-      n += c > 0;
+  const int nl = (int)op->launch_first.size();
+  const auto count = [&](const LaunchStep& st) { return n += st.launches(), PMG_OK; };
+  for_each_launch_step(*op, op->chain_first, op->chain_count, 0, op->n_launch_l, apply_form(op), count);
+  for_each_launch_step(*op, op->chain_first, op->chain_count, op->n_launch_l, nl, apply_form(op), count);
   return n;
 }
 
@@ -1275,6 +1174,6 @@ extern "C" int pmg_laplacian_set_chain_form(pmg_laplacian op, int on)
 // 2 if the interior launches of an application run as two halves on two streams, else 1
 extern "C" int pmg_laplacian_apply_streams(pmg_laplacian op)
 {
-  return !op ? -1 : (!op->launch_stream.empty() && op->batch_patches == 0) ? 2 : 1;
+  return !op ? -1 : apply_form(op).two_streams ? 2 : 1;
 }
 

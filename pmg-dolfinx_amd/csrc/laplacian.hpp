@@ -80,6 +80,7 @@ struct pmg_laplacian_s
   int32_t* chain_patch = nullptr;
   std::vector<int32_t> chain_first, chain_count; // chains of each colour
   bool stream_policy = true; // the stored tensor exceeds the Infinity Cache: nt loads / stores (launch_stiffness)
+  bool stream_policy32 = false; // the same decision for the float tensor, taken where it is built (laplacian_f32_prepare)
   double* diag_inv = nullptr; // [size_local + num_ghosts]
   bool have_diag = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -109,6 +110,63 @@ struct pmg_laplacian_s
 
 namespace pmg
 {
+// Is a tensor of this many bytes, read once per application, streamed past the Infinity Cache (nt loads and stores)?
+// Asked where a tensor is built or resized, never per application; it reads PMG_STREAM_POLICY (laplacian.hip).
+bool streams_past_the_cache(long long tensor_bytes);
+
+// The launches [l0, l1) of the operator's plan under `form` (patches.hpp for_each_launch_step) as HIP calls on `s` and
+// on the operator's second stream; launch(step, stream) issues the kernels of a PATCHES or CHAINS step.  Both precisions
+// apply through this walk.  With profiling on, the walk is bracketed by a pair of events and the steps that launch are
+// counted (pmg_laplacian_read_profile).
+template <typename L>
+int walk_launches(pmg_laplacian op, int l0, int l1, ApplyForm form, hipStream_t s, L&& launch)
+{
+  const bool prof = op->profiling && l1 > l0;
+  if (prof)
+  {
+    while (op->prof_events.size() < op->prof_used + 2)
+    {
+      hipEvent_t e;
+      PMG_HIP(hipEventCreate(&e));
+      op->prof_events.push_back(e);
+    }
+    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used], s));
+  }
+  int issued = 0;
+  // (inside a stream capture the fork and the join make the two halves two branches of the graph)
+  PMG_TRY(for_each_launch_step(*op, op->chain_first, op->chain_count, l0, l1, form, [&](const LaunchStep& st) -> int {
+    switch (st.kind)
+    {
+    case LaunchStep::FORK:
+      PMG_HIP(hipEventRecord(op->ev_fork, s));
+      PMG_HIP(hipStreamWaitEvent(op->stream2, op->ev_fork, 0));
+      break;
+    case LaunchStep::WAIT_ORDER:
+      PMG_HIP(hipStreamWaitEvent(s, op->ev_order, 0));
+      break;
+    case LaunchStep::RECORD_ORDER:
+      PMG_HIP(hipEventRecord(op->ev_order, op->stream2));
+      break;
+    case LaunchStep::JOIN:
+      PMG_HIP(hipEventRecord(op->ev_join, op->stream2));
+      PMG_HIP(hipStreamWaitEvent(s, op->ev_join, 0));
+      break;
+    default:
+      PMG_TRY(launch(st, st.stream ? op->stream2 : s));
+      ++issued;
+    }
+    return PMG_OK;
+  }));
+  PMG_HIP(hipGetLastError());
+  if (prof)
+  {
+    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used + 1], s));
+    op->prof_used += 2;
+    op->prof_launches += issued;
+  }
+  return PMG_OK;
+}
+
 // ---- geometry: J, adj(J), det at one quadrature point (src/laplacian.hpp:72-97) ----
 __device__ inline void jacobian(const double* __restrict__ xgeom,
                                 const int32_t* __restrict__ gdofs, const double* __restrict__ dphi,

@@ -279,35 +279,20 @@ __global__ void to_float_kernel(int n, const double* __restrict__ in, float* __r
 
 int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 2048); }
 
-template <int P>
-void launch_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, bool nt,
-                hipStream_t s)
+// one launch of the float stiffness kernel over the patches [first, first + count); the tensor streams past the
+// Infinity Cache under the FP64 rule at half the bytes (stream_policy32: nt loads and stores)
+int launch_patches_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, hipStream_t s)
 {
-  if (nt)
-    stiffness_f32_kernel<P, true><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
-                                                                      op->lmap_id, op->lmaps, op->pcell, op->pncell,
-                                                                      op->kappa, op->D32, op->react32, first, atomic_out);
-  else
-    stiffness_f32_kernel<P, false><<<count, Shape32<P>::THREADS, 0, s>>>(x, y, op->G32, op->poff, op->pdofs,
-                                                                       op->lmap_id, op->lmaps, op->pcell, op->pncell,
-                                                                       op->kappa, op->D32, op->react32, first, atomic_out);
-}
-
-int launch_patches_f32(pmg_laplacian op, const float* x, float* y, int first, int count, int atomic_out, bool nt,
-                       hipStream_t s)
-{
-  switch (op->P)
-  {
-  case 1: launch_f32<1>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 2: launch_f32<2>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 3: launch_f32<3>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 4: launch_f32<4>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 5: launch_f32<5>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 6: launch_f32<6>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 7: launch_f32<7>(op, x, y, first, count, atomic_out, nt, s); break;
-  case 8: launch_f32<8>(op, x, y, first, count, atomic_out, nt, s); break;
-  default: return fail(PMG_ERR_INVALID, "Unsupported degree");
-  }
+  PMG_TRY(with_degree(op->P, [&](auto degree) {
+    constexpr int P = decltype(degree)::value;
+    auto launch = [&](auto nt) {
+      stiffness_f32_kernel<P, decltype(nt)::value><<<count, Shape32<P>::THREADS, 0, s>>>(
+          x, y, op->G32, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D32,
+          op->react32, first, atomic_out);
+    };
+    (P >= NT_FROM && op->stream_policy32) ? launch(std::true_type{}) : launch(std::false_type{});
+    return PMG_OK;
+  }));
   op->launches++;
   return PMG_OK;
 }
@@ -366,6 +351,7 @@ int laplacian_f32_prepare(pmg_laplacian op, hipStream_t s)
   PMG_HIP(hipMalloc(&op->G32, sizeof(float2) * 3 * (size_t)(n > 0 ? n : 1)));
   PMG_HIP(hipMalloc(&op->D32, sizeof(float) * op->nd * op->nd));
   to_float_kernel<<<1, 256, 0, s>>>(op->nd * op->nd, op->D, op->D32);
+  op->stream_policy32 = streams_past_the_cache((long long)sizeof(float2) * 3 * n);
   PMG_TRY(laplacian_f32_reaction(op, s));
   return laplacian_f32_refresh(op, s);
 }
@@ -399,51 +385,17 @@ long long laplacian_diag_version(pmg_laplacian op) { return op->diag_version; }
 int laplacian_apply_f32(pmg_laplacian op, const float* in, float* out, hipStream_t s)
 {
   pmg_layout l = op->layout;
-  const int nl = (int)op->launch_first.size();
-  const bool zero_all = op->needs_zero || nl == 0 || 2LL * op->n_bzero > l->total();
-  if (zero_all)
+  if (laplacian_wants_zeroed_output(op))
   {
     if (l->total() > 0)
       fill_f32_kernel<<<grid_for(l->total()), 256, 0, s>>>(l->total(), out);
   }
   else if (op->n_bzero > 0)
     zero_list_f32_kernel<<<grid_for(op->n_bzero), 256, 0, s>>>(op->n_bzero, op->bzero, out);
-  const bool prof = op->profiling && nl > 0;
-  if (prof)
-  {
-    if (op->prof_used + 2 > op->prof_events.size())
-    {
-      hipEvent_t a, b;
-      PMG_HIP(hipEventCreate(&a));
-      op->prof_events.push_back(a);
-      PMG_HIP(hipEventCreate(&b));
-      op->prof_events.push_back(b);
-    }
-    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used], s));
-  }
-  // the tensor streams past the Infinity Cache (the FP64 rule at half the bytes): nt loads and stores
-  const bool nt = op->P >= 2 && (long long)sizeof(float2) * 3 * op->npatch * op->K * op->N > (128LL << 20);
-  int issued = 0;
-  for (int i = 0; i < nl; ++i)
-  {
-    const int first = op->launch_first[i];
-    int count = op->launch_count[i];
-    const int atomic_out = i >= op->n_plain ? 1 : 0;
-    while (atomic_out && i + 1 < nl && op->launch_first[i + 1] == first + count) // contiguous atomic launches: one
-      count += op->launch_count[++i];
-    if (count > 0)
-    {
-      PMG_TRY(launch_patches_f32(op, in, out, first, count, atomic_out, nt, s));
-      ++issued;
-    }
-  }
-  PMG_HIP(hipGetLastError());
-  if (prof)
-  {
-    PMG_HIP(hipEventRecord(op->prof_events[op->prof_used + 1], s));
-    op->prof_used += 2;
-    op->prof_launches += issued;
-  }
+  // (the default form: one stream, no chains)
+  PMG_TRY(walk_launches(op, 0, (int)op->launch_first.size(), ApplyForm{}, s, [&](const LaunchStep& st, hipStream_t sl) {
+    return launch_patches_f32(op, in, out, st.first, st.count, st.atomic_out, sl);
+  }));
   op->applies++;
   return PMG_OK;
 }

@@ -21,12 +21,6 @@
 
 using namespace pmg;
 
-namespace pmg
-{
-int laplacian_geometry_ascending(pmg_laplacian op, double* G_out, hipStream_t s); // laplacian.hip
-const double* laplacian_reaction(pmg_laplacian op);                               // laplacian.hip; nullptr = none
-}
-
 struct pmg_matrix_s
 {
   pmg_laplacian op = nullptr; // source of G, kappa, the BC marker and the dofmap; must outlive the matrix
@@ -256,17 +250,10 @@ int assemble_values(pmg_matrix M, hipStream_t s)
     const size_t table = sizeof(double) * M->nd * M->nd, rowb = sizeof(double) * (size_t)M->cap;
     const int groups = (int)std::max<size_t>(1, std::min<size_t>(256 / W, (LDS_LIMIT - table) / rowb));
     const size_t lds = table + rowb * groups;
-    switch (M->nd)
-    {
-    case 2: launch_values<2>(M, W, groups, lds, Gc, s); break;
-    case 3: launch_values<3>(M, W, groups, lds, Gc, s); break;
-    case 4: launch_values<4>(M, W, groups, lds, Gc, s); break;
-    case 5: launch_values<5>(M, W, groups, lds, Gc, s); break;
-    case 6: launch_values<6>(M, W, groups, lds, Gc, s); break;
-    case 7: launch_values<7>(M, W, groups, lds, Gc, s); break;
-    case 8: launch_values<8>(M, W, groups, lds, Gc, s); break;
-    default: launch_values<9>(M, W, groups, lds, Gc, s); break;
-    }
+    rc = with_degree(M->nd - 1, [&](auto P) {
+      launch_values<decltype(P)::value + 1>(M, W, groups, lds, Gc, s);
+      return PMG_OK;
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
       rc = fail(PMG_ERR_HIP, "matrix_values_kernel: %s", hipGetErrorString(e));

@@ -171,6 +171,12 @@ struct TransferView
   const double* M1 = nullptr; // [ndf][ndc]
 };
 
+// laplacian.hip -- what the transfers (interpolate.hip) and the AMG set-up (amg.hip) ask of an operator's patches
+PatchView laplacian_patches(pmg_laplacian op);
+bool laplacian_fuses_restriction(pmg_laplacian op, int coarse_degree);
+int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const double* z, const double* r,
+                             double* coarse, hipStream_t s);
+
 // Chains (round 4, second half): the interior patches of a large level strung together along the axis with the fewest
 // patch positions (z on a box whose patches are long in z), one PERSISTENT workgroup per chain (stiffness_chain_kernel,
 // laplacian.hip).  A chain is walked in order, so the dofs two consecutive patches share never pass through global
@@ -204,6 +210,100 @@ int build_chain_plan(ChainPlan& cp, const PatchPlan& plan, int32_t ndofs, const 
 int build_patch_plan(PatchPlan& plan, int P, int32_t ncells, const int32_t* dofmap,
                      const int8_t* bc, int32_t ndofs, const float* centroid,
                      const int32_t* lcells, int32_t n_l, const int32_t* bcells, int32_t n_b);
+
+// ---- the launch schedule of one operator application -----------------------------------------------------------------
+// Which launches the range [l0, l1) of a plan issues, in which order, on which stream and behind which events, is decided
+// here and nowhere else: the FP64 and FP32 applies (laplacian.hpp walk_launches) turn the steps into HIP calls, the
+// count of pmg_laplacian_launches_per_apply counts them, and the host checker (tests/host/plan_check.cpp) executes them
+// serially.  No HIP call, nothing on the heap.
+
+// The form of an application, as far as it is the operator's state and not the plan's (laplacian.hip apply_form).
+struct ApplyForm
+{
+  bool two_streams = false; // a split plan may run its interior as two halves on two streams
+  bool chains = false;      // the interior runs as chains (one launch per chain colour) where it is walked whole
+  // contiguous atomic launches inside one walk become one launch (not with batched geometry, whose executor cuts every
+  // launch into batches of its own -- the one thing the schedule has to know about that mode)
+  bool coalesce = true;
+};
+
+struct LaunchStep
+{
+  enum Kind
+  {
+    FORK,         // the second stream waits for everything issued to the caller's stream so far
+    WAIT_ORDER,   // the caller's stream waits for the ordering event
+    PATCHES,      // stiffness kernel over the patches [first, first + count)
+    CHAINS,       // chain kernel over the chains [first, first + count) of chain colour `colour`
+    RECORD_ORDER, // the ordering event is recorded on the second stream
+    JOIN          // the caller's stream waits for everything issued to the second stream so far
+  } kind;
+  int first = 0, count = 0;
+  int atomic_out = 0; // PATCHES: the launch adds with atomics (a merged launch)
+  int stream = 0;     // PATCHES: 0 = the caller's stream, 1 = the second
+  int colour = 0;     // CHAINS
+  bool launches() const { return kind == PATCHES || kind == CHAINS; }
+};
+
+// f(const LaunchStep&) -> int (PMG_OK to go on) for the steps of the launches [l0, l1), in issue order.  `plan` is
+// anything with PatchPlan's launch fields (the plan itself, the operator handle that copied them); chain_first /
+// chain_count are the chains of each colour (ChainPlan::launch_first / launch_count; empty: no chains).
+//   two streams  a split plan walked from 0 through its whole interior: fork, the launches of the halves on their
+//                streams with one ordering event between them, the join in front of launch n_launch_l (or at the end)
+//   chains       replace the launches [0, n_launch_l) of a walk that covers them, unless it runs on two streams
+//   atomic_out   launch index >= n_plain
+//   coalescing   see ApplyForm; never on two streams
+// Empty launches and empty chain colours yield no step; the events around an empty launch are kept.
+template <typename Plan, typename F>
+int for_each_launch_step(const Plan& plan, const std::vector<int32_t>& chain_first,
+                         const std::vector<int32_t>& chain_count, int l0, int l1, ApplyForm form, F&& f)
+{
+  const int nli = plan.n_launch_l;
+  const bool two = form.two_streams && !plan.launch_stream.empty() && l0 == 0 && l1 >= nli && l1 > l0;
+  LaunchStep st{};
+  auto emit = [&](LaunchStep::Kind kind) { return st.kind = kind, f(st); };
+  if (two)
+    PMG_TRY(emit(LaunchStep::FORK));
+  if (form.chains && l0 == 0 && l1 >= nli && nli > 0 && !two)
+  {
+    for (size_t c = 0; c < chain_count.size(); ++c)
+      if (chain_count[c] > 0)
+      {
+        st = LaunchStep{LaunchStep::CHAINS, chain_first[c], chain_count[c], 0, 0, (int)c};
+        PMG_TRY(f(st));
+      }
+    l0 = nli;
+  }
+  for (int l = l0; l < l1; ++l)
+  {
+    st = LaunchStep{LaunchStep::PATCHES, plan.launch_first[l], plan.launch_count[l], l >= plan.n_plain ? 1 : 0, 0, 0};
+    if (two && l < nli)
+    {
+      if (l == plan.launch_wait)
+        PMG_TRY(emit(LaunchStep::WAIT_ORDER));
+      st.stream = plan.launch_stream[l] ? 1 : 0;
+    }
+    if (two && l == nli)
+      PMG_TRY(emit(LaunchStep::JOIN));
+    while (st.atomic_out && form.coalesce && !two && l + 1 < l1 && plan.launch_first[l + 1] == st.first + st.count)
+      st.count += plan.launch_count[++l];
+    if (st.count > 0)
+      PMG_TRY(emit(LaunchStep::PATCHES));
+    if (two && l == plan.launch_signal)
+      PMG_TRY(emit(LaunchStep::RECORD_ORDER));
+  }
+  if (two && l1 == nli)
+    PMG_TRY(emit(LaunchStep::JOIN));
+  return PMG_OK;
+}
+
+// Does an application zero-fill its whole output first?  Where some dof belongs to no patch (needs_zero), where nothing
+// is launched, or where most of the vector would be on the list of dofs to clear anyway (n_bzero: the dofs whose first
+// writer adds with atomics -- the merged launch of a small level).
+inline bool zero_fills_output(bool needs_zero, size_t n_launches, long long n_bzero, long long total)
+{
+  return needs_zero || n_launches == 0 || 2 * n_bzero > total;
+}
 
 // The coarse side of the patch-form p-transfers: per patch of the fine operator, the sorted list of the coarse dofs of
 // its cells (PD_ACC = a patch of an earlier launch holds the dof), the position of every (slot, coarse t) in that list

@@ -21,35 +21,6 @@
 
 using namespace pmg;
 
-namespace pmg
-{
-int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
-const double* laplacian_diag_inv(pmg_laplacian op);
-pmg_layout laplacian_layout(pmg_laplacian op);
-long long laplacian_launches(pmg_laplacian op);
-int interp_prolong(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s);
-int interp_restrict(pmg_interpolator ip, double* fine, double* coarse, hipStream_t s);
-int interp_prolong_add(pmg_interpolator ip, double* coarse, double* fine, hipStream_t s);
-bool interp_is_patched(pmg_interpolator ip);
-bool interp_restricts_difference(pmg_interpolator ip);
-int interp_restrict_difference(pmg_interpolator ip, double* fine, const double* fine_sub, double* coarse,
-                               hipStream_t s);
-bool interp_fuses_residual(pmg_interpolator ip, pmg_laplacian op);
-int interp_restrict_residual(pmg_interpolator ip, pmg_laplacian op, const double* z, const double* r, double* coarse,
-                             hipStream_t s);
-int amg_solve(pmg_amg amg, double* x, const double* b, hipStream_t s);
-pmg_layout amg_layout(pmg_amg amg);
-long long amg_capture_state(pmg_amg amg);
-long long laplacian_capture_state(pmg_laplacian op);
-bool laplacian_wants_zeroed_output(pmg_laplacian op);
-int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
-int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
-// matrix.hip -- the assembled form of a level's operator
-int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s);
-const double* matrix_diag_inv(pmg_matrix M);
-pmg_layout matrix_layout(pmg_matrix M);
-} // namespace pmg
-
 struct pmg_chebyshev_s
 {
   pmg_layout layout = nullptr;

@@ -4,7 +4,10 @@
 // when the race happens to lose.  This program needs no GPU: it is compiled host-only together with csrc/patches.hip
 // (tests/test_patch_plans.py, with the address and undefined-behaviour sanitizers), builds plans for meshes it
 // generates itself, checks every structural invariant, and then EXECUTES each schedule serially in exact integer
-// arithmetic, in several legal orders, against the plain cell-by-cell scatter-add.
+// arithmetic, in several legal orders, against the plain cell-by-cell scatter-add.  The schedule is the library's own:
+// the steps of an application (forks, waits, patch and chain launches, records, joins) and the zero-fill rule come from
+// the functions the operator's apply walks (patches.hpp for_each_launch_step, zero_fills_output); the checker's own are
+// the generic meaning of the steps, the linearisations it draws from that and the serial execution.
 //
 //   plan_check <group>        run the cases of one group; one line per case, then a summary line with coverage flags
 //   plan_check --list         the group names
@@ -79,7 +82,8 @@ const char* const FLAGS[] = {"tensor_grouping", "morton_grouping", "halved_group
                              "chain_refused_grid", "chain_refused_colours", "chain_refused_few_chains",
                              "boundary_only", "interior_only", "single_cell_patch", "ragged_blocks", "below_one_patch",
                              "empty_plan", "zero_all_rule", "bzero_list_rule", "coarse_coloured", "coarse_merged",
-                             "coarse_refused"};
+                             "coarse_refused", "form_two_calls", "form_whole", "coalesced_step", "fp32_unsplit",
+                             "form_chains"};
 std::set<std::string> g_cov;
 void cover(const char* f) { g_cov.insert(f); }
 
@@ -286,70 +290,145 @@ std::vector<int32_t> launch_of_patches(const PatchPlan& pl)
   return lo;
 }
 
-// The happens-before relation run_launches (laplacian.hip) creates, as direct edges pred[l] -> l.
-std::vector<std::vector<int>> launch_edges(const PatchPlan& pl)
+// ---- the library's schedule ---------------------------------------------------------------------------------------------
+// The steps of one operator application come from the library (patches.hpp for_each_launch_step): a sequence of walks
+// (l0, l1) under one form, as its callers issue them.  Nothing below restates which steps a plan yields.
+struct Application
 {
+  const char* name;
+  std::vector<LaunchStep> steps;
+};
+enum Walks
+{
+  TWO_CALLS, // (0, n_launch_l) then (n_launch_l, nl): an application with its halo exchange between the two
+  WHOLE      // (0, nl): the timing loop, the single launch of a small level, the FP32 apply
+};
+Application application(const char* name, const PatchPlan& pl, const ChainPlan* cp, Walks walks, ApplyForm form)
+{
+  static const std::vector<int32_t> none;
+  Application app{name, {}};
   const int nl = (int)pl.launch_first.size();
-  std::vector<std::vector<int>> pred(nl);
-  if (pl.launch_stream.empty())
+  auto walk = [&](int l0, int l1) {
+    for_each_launch_step(pl, cp ? cp->launch_first : none, cp ? cp->launch_count : none, l0, l1, form,
+                         [&](const LaunchStep& st) { return app.steps.push_back(st), 0; });
+  };
+  if (walks == TWO_CALLS)
   {
-    for (int l = 1; l < nl; ++l)
-      pred[l].push_back(l - 1);
-    return pred;
+    walk(0, pl.n_launch_l);
+    walk(pl.n_launch_l, nl);
   }
-  int last[2] = {-1, -1};
-  for (int l = 0; l < pl.n_launch_l; ++l)
-  {
-    const int st = pl.launch_stream[l] ? 1 : 0;
-    if (last[st] >= 0)
-      pred[l].push_back(last[st]); // a stream runs its launches in index order
-    last[st] = l;
-  }
-  // the ordering event: recorded on stream 1 behind launch_signal, waited for on stream 0 in front of launch_wait (an
-  // event that is waited for before it was recorded orders nothing, hence signal < wait in issue order: checked)
-  if (pl.launch_signal >= 0 && pl.launch_wait >= 0 && pl.launch_signal < nl && pl.launch_wait < nl)
-    pred[pl.launch_wait].push_back(pl.launch_signal);
-  for (int l = pl.n_launch_l; l < nl; ++l) // the join in front of the boundary launches
-  {
-    if (l == pl.n_launch_l)
-      for (int st = 0; st < 2; ++st)
-        if (last[st] >= 0)
-          pred[l].push_back(last[st]);
-    if (l > pl.n_launch_l)
-      pred[l].push_back(l - 1);
-  }
-  return pred;
+  else
+    walk(0, nl);
+  return app;
+}
+ApplyForm fp64_form(bool chains = false)
+{
+  ApplyForm f;
+  f.two_streams = true;
+  f.chains = chains;
+  return f;
 }
 
-// a linearisation of the launches that the relation allows: launches of stream `prefer` as early as possible
-std::vector<int> linearise(const PatchPlan& pl, int prefer)
+// What a sequence of steps means, whatever rule produced it.  A stream runs its steps in issue order.  The fork makes the
+// second stream wait for what the caller's has been given so far, the join the caller's for the second.  A wait for the
+// ordering event follows the latest record issued before it; with none it orders nothing.
+struct StepOrder
 {
-  const int nl = (int)pl.launch_first.size();
-  const auto pred = launch_edges(pl);
-  std::vector<char> done(nl, 0);
+  std::vector<std::vector<int>> pred; // direct edges pred[i] -> i
+  std::vector<int> on;                // the stream whose order step i joins
+};
+StepOrder step_order(const std::vector<LaunchStep>& steps)
+{
+  StepOrder so{std::vector<std::vector<int>>(steps.size()), std::vector<int>(steps.size(), 0)};
+  int last[2] = {-1, -1}, recorded = -1;
+  for (int i = 0; i < (int)steps.size(); ++i)
+  {
+    int on = 0, also = -1;
+    switch (steps[i].kind)
+    {
+    case LaunchStep::FORK: on = 1, also = last[0]; break;
+    case LaunchStep::JOIN: also = last[1]; break;
+    case LaunchStep::WAIT_ORDER: also = recorded; break;
+    case LaunchStep::RECORD_ORDER: on = 1, recorded = i; break;
+    case LaunchStep::PATCHES: on = steps[i].stream; break;
+    case LaunchStep::CHAINS: break;
+    }
+    if (last[on] >= 0)
+      so.pred[i].push_back(last[on]);
+    if (also >= 0)
+      so.pred[i].push_back(also);
+    last[on] = i;
+    so.on[i] = on;
+  }
+  return so;
+}
+
+// a linearisation of the steps that the relation allows: steps of stream `prefer` as early as possible
+std::vector<int> linearise(const std::vector<LaunchStep>& steps, int prefer)
+{
+  const int n = (int)steps.size();
+  const StepOrder so = step_order(steps);
+  std::vector<char> done(n, 0);
   std::vector<int> out;
-  while ((int)out.size() < nl)
+  while ((int)out.size() < n)
   {
     int pick = -1;
     for (int pass = 0; pass < 2 && pick < 0; ++pass)
-      for (int l = 0; l < nl && pick < 0; ++l)
+      for (int i = 0; i < n && pick < 0; ++i)
       {
-        if (done[l])
-          continue;
-        const int st = (!pl.launch_stream.empty() && l < pl.n_launch_l && pl.launch_stream[l]) ? 1 : 0;
-        if (pass == 0 && st != prefer)
+        if (done[i] || (pass == 0 && so.on[i] != prefer))
           continue;
         bool ready = true;
-        for (int q : pred[l])
+        for (int q : so.pred[i])
           ready = ready && done[q];
         if (ready)
-          pick = l;
+          pick = i;
       }
-    CHECK(pick >= 0, "two streams", "the launch order has a cycle");
+    CHECK(pick >= 0, "two streams", "the step order has a cycle");
     done[pick] = 1;
     out.push_back(pick);
   }
   return out;
+}
+
+// Two launch steps that touch a common dof are ordered as their patches are.  (Patches of one plain launch are
+// disjoint: checked with the colours.)
+void check_ordering(const PatchPlan& pl, int32_t ndofs, const Application& app)
+{
+  const int n = (int)app.steps.size();
+  const StepOrder so = step_order(app.steps);
+  std::vector<std::vector<char>> hb(n, std::vector<char>(n, 0));
+  for (int i = 0; i < n; ++i) // (edges point forward in issue order: one sweep closes the relation)
+    for (int q : so.pred[i])
+    {
+      hb[q][i] = 1;
+      for (int r = 0; r < q; ++r)
+        if (hb[r][q])
+          hb[r][i] = 1;
+    }
+  std::vector<int> step_of(pl.npatch, -1);
+  for (int i = 0; i < n; ++i)
+    if (app.steps[i].kind == LaunchStep::PATCHES)
+      for (int p = app.steps[i].first; p < app.steps[i].first + app.steps[i].count; ++p)
+      {
+        CHECK(p >= 0 && p < pl.npatch && step_of[p] < 0, "schedule", "%s: patch %d is launched twice or out of range",
+              app.name, p);
+        step_of[p] = i;
+      }
+  std::vector<int32_t> last_step(ndofs, -1);
+  for (int p = 0; p < pl.npatch; ++p)
+  {
+    CHECK(step_of[p] >= 0, "schedule", "%s: patch %d is never launched", app.name, p);
+    for (int i = pl.poff[p]; i < pl.poff[p + 1]; ++i)
+    {
+      const int32_t d = (int32_t)(pl.pdofs[i] & PD_MASK);
+      const int q = last_step[d], t = step_of[p];
+      CHECK(q < 0 || q == t || hb[q][t], "two streams: launches that share a dof are ordered",
+            "%s: the launches at patches %d and %d both touch dof %d (patch %d) and nothing orders them", app.name,
+            app.steps[q].first, app.steps[t].first, d, p);
+      last_step[d] = t;
+    }
+  }
 }
 
 // ---- exact arithmetic ------------------------------------------------------------------------------------------------
@@ -423,12 +502,10 @@ void patch_sums(const PatchPlan& pl, int p, std::vector<double>& sum)
       sum[lm[(size_t)sl * N + table_index(nd, t)]] += contrib(pl.pcell[(size_t)p * K + sl], t);
 }
 
-// what apply_impl clears (laplacian.hip: zero_fills_output, zero_list_kernel)
+// what an application clears first: everything where the library's rule says so, else the listed dofs
 void clear_output(const PatchPlan& pl, const Reference& ref, std::vector<double>& y)
 {
-  const bool needs_zero = !ref.all_touched; // (laplacian.hip: a dof no patch lists)
-  const bool zero_all = needs_zero || pl.launch_first.empty() || 2LL * (long long)pl.bzero.size() > (long long)y.size();
-  if (zero_all)
+  if (zero_fills_output(!ref.all_touched, pl.launch_first.size(), (long long)pl.bzero.size(), (long long)y.size()))
   {
     std::fill(y.begin(), y.end(), 0.0);
     cover("zero_all_rule");
@@ -443,10 +520,10 @@ void clear_output(const PatchPlan& pl, const Reference& ref, std::vector<double>
 }
 
 // one launch of the patch kernel (stiffness_column.hpp: the gather of phase 0 and patch_write_back)
-void run_patch_launch(const PatchPlan& pl, int l, Order o, std::vector<double>& y)
+void run_patch_launch(const PatchPlan& pl, const LaunchStep& st, Order o, std::vector<double>& y)
 {
-  const bool atomic_out = l >= pl.n_plain;
-  const std::vector<int> order = patch_order(pl.launch_first[l], pl.launch_count[l], o == LOCKSTEP ? FORWARD : o);
+  const bool atomic_out = st.atomic_out != 0;
+  const std::vector<int> order = patch_order(st.first, st.count, o == LOCKSTEP ? FORWARD : o);
   std::vector<std::vector<double>> acc(order.size());
   std::vector<double> sum;
   auto gather = [&](size_t i) {
@@ -499,21 +576,74 @@ void compare(const Reference& ref, const std::vector<double>& y, const char* wha
           "linearisation %d)", d, y[d], ref.y[d], ref.touched[d] ? "touched" : "untouched", order, lin);
 }
 
-void interpret_plan(const PatchPlan& pl, const Reference& ref)
+void run_chain_launch(const PatchPlan& pl, const ChainPlan& cp, const LaunchStep& st, Order o, std::vector<double>& y);
+
+// every step of an application, serially: in each linearisation the step order allows and each order of the patches
+// inside a launch (a chain is walked in order: no lockstep there)
+void interpret(const PatchPlan& pl, const ChainPlan* cp, const Reference& ref, const Application& app)
 {
-  const int nlin = pl.launch_stream.empty() ? 1 : 2;
+  bool second_stream = false;
+  for (const LaunchStep& st : app.steps)
+    second_stream = second_stream || st.kind == LaunchStep::FORK;
+  const int nlin = second_stream ? 2 : 1;
   for (int lin = 0; lin < nlin; ++lin)
   {
-    const std::vector<int> seq = linearise(pl, nlin == 1 ? 0 : (lin == 0 ? 1 : 0));
-    for (int o = 0; o < N_ORDERS; ++o)
+    const std::vector<int> seq = linearise(app.steps, nlin == 1 ? 0 : (lin == 0 ? 1 : 0));
+    for (int o = 0; o < (cp ? LOCKSTEP : N_ORDERS); ++o)
     {
       std::vector<double> y(ref.y.size(), std::numeric_limits<double>::quiet_NaN());
       clear_output(pl, ref, y);
-      for (int l : seq)
-        run_patch_launch(pl, l, (Order)o, y);
-      compare(ref, y, "serial interpretation", ORDER_NAME[o], lin);
+      for (int i : seq)
+        if (app.steps[i].kind == LaunchStep::PATCHES)
+          run_patch_launch(pl, app.steps[i], (Order)o, y);
+        else if (app.steps[i].kind == LaunchStep::CHAINS)
+          run_chain_launch(pl, *cp, app.steps[i], (Order)o, y);
+      compare(ref, y, app.name, ORDER_NAME[o], lin);
     }
   }
+}
+
+int count_steps(const Application& app, LaunchStep::Kind kind)
+{
+  return (int)std::count_if(app.steps.begin(), app.steps.end(), [&](const LaunchStep& st) { return st.kind == kind; });
+}
+
+// the forms in which the library walks a plan without chains
+std::vector<Application> plan_applications(const PatchPlan& pl)
+{
+  std::vector<Application> apps;
+  apps.push_back(application("serial interpretation", pl, nullptr, TWO_CALLS, fp64_form()));
+  cover("form_two_calls");
+  apps.push_back(application("serial interpretation of the whole walk", pl, nullptr, WHOLE, fp64_form()));
+  cover("form_whole");
+  int nonempty = 0;
+  for (int32_t c : pl.launch_count)
+    nonempty += c > 0;
+  if (count_steps(apps.back(), LaunchStep::PATCHES) < nonempty)
+    cover("coalesced_step");
+  // (a cell list has at most one atomic launch, so neither call of an application finds two to coalesce:
+  // pmg_laplacian_launches_per_apply counts these steps and documents one per non-empty launch of the plan)
+  CHECK(count_steps(apps[0], LaunchStep::PATCHES) == nonempty, "schedule",
+        "the two calls of an application issue %d launches for %d non-empty launches of the plan",
+        count_steps(apps[0], LaunchStep::PATCHES), nonempty);
+  if (!pl.launch_stream.empty())
+  {
+    CHECK(count_steps(apps[0], LaunchStep::FORK) == 1 && count_steps(apps[0], LaunchStep::JOIN) == 1
+              && count_steps(apps[1], LaunchStep::FORK) == 1 && count_steps(apps[1], LaunchStep::JOIN) == 1,
+          "schedule", "a split plan is walked without one fork and one join");
+    // the FP32 apply: the same plan, one stream
+    apps.push_back(application("serial interpretation of the FP32 walk", pl, nullptr, WHOLE, ApplyForm{}));
+    for (const LaunchStep& st : apps.back().steps)
+      CHECK(st.kind == LaunchStep::PATCHES && st.stream == 0, "schedule", "the FP32 walk of a split plan is split");
+    cover("fp32_unsplit");
+  }
+  return apps;
+}
+
+void interpret_plan(const PatchPlan& pl, const Reference& ref)
+{
+  for (const Application& app : plan_applications(pl))
+    interpret(pl, nullptr, ref, app);
 }
 
 // ---- structural invariants of a patch plan ----------------------------------------------------------------------------
@@ -690,29 +820,8 @@ void check_plan(const Geo& g, const Space& s, const PatchPlan& pl)
   }
   else
     CHECK(pl.launch_signal == -1 && pl.launch_wait == -1, "two streams", "signal / wait set without launch_stream");
-  {
-    const auto pred = launch_edges(pl);
-    std::vector<std::vector<char>> hb(nl, std::vector<char>(nl, 0));
-    for (int l = 0; l < nl; ++l) // (edges point forward in index order: one sweep closes the relation)
-      for (int q : pred[l])
-      {
-        CHECK(q < l, "two streams", "ordering edge %d -> %d points backwards", q, l);
-        hb[q][l] = 1;
-        for (int r = 0; r < q; ++r)
-          if (hb[r][q])
-            hb[r][l] = 1;
-      }
-    std::vector<int32_t> last_launch(s.ndofs, -1);
-    for (int p = 0; p < np; ++p)
-      for (int i = pl.poff[p]; i < pl.poff[p + 1]; ++i)
-      {
-        const int32_t d = (int32_t)(pl.pdofs[i] & PD_MASK);
-        const int q = last_launch[d];
-        CHECK(q < 0 || q == lo[p] || hb[q][lo[p]], "two streams: launches that share a dof are ordered",
-              "launches %d and %d both touch dof %d (patch %d) and nothing orders them", q, lo[p], d, p);
-        last_launch[d] = lo[p];
-      }
-  }
+  for (const Application& app : plan_applications(pl))
+    check_ordering(pl, s.ndofs, app);
 }
 
 // ---- chain plan --------------------------------------------------------------------------------------------------------
@@ -747,8 +856,9 @@ void check_chain(const Space& s, const PatchPlan& pl, const ChainPlan& cp)
   int next = 0;
   for (int l = 0; l < ncl; ++l)
   {
-    CHECK(cp.launch_first[l] == next && cp.launch_count[l] >= 0, "chain launches tile the chains",
-          "launch %d starts at chain %d, expected %d", l, cp.launch_first[l], next);
+    // (no empty colour: the profile of an application counts one kernel launch per chain colour)
+    CHECK(cp.launch_first[l] == next && cp.launch_count[l] > 0, "chain launches tile the chains",
+          "launch %d starts at chain %d with %d chains, expected start %d", l, cp.launch_first[l], cp.launch_count[l], next);
     for (int q = 0; q < cp.launch_count[l]; ++q)
       claunch[next++] = l;
   }
@@ -817,54 +927,61 @@ void check_chain(const Space& s, const PatchPlan& pl, const ChainPlan& cp)
           "dof %d has %d", d, nbcfirst[d]);
 }
 
-// the chain walk of stiffness_chain_kernel in place of the interior launches, then the boundary launches
+// one launch of stiffness_chain_kernel: the chains of a step, each walked in order
+void run_chain_launch(const PatchPlan& pl, const ChainPlan& cp, const LaunchStep& st, Order o, std::vector<double>& y)
+{
+  for (int ch : patch_order(st.first, st.count, o))
+  {
+    const int len = cp.chain_off[ch + 1] - cp.chain_off[ch];
+    std::vector<double> prev, cur, sum, ynext;
+    auto read_y = [&](int p) { // the gather of a patch is issued before the previous patch's write-back
+      ynext.assign(pl.poff[p + 1] - pl.poff[p], 0.0);
+      for (size_t k = 0; k < ynext.size(); ++k)
+        if (cp.ccar[pl.poff[p] + k] & CC_ACC)
+          ynext[k] = y[cp.cdofs[pl.poff[p] + k] & CD_MASK];
+    };
+    read_y(cp.chain_patch[cp.chain_off[ch]]);
+    for (int c = 0; c < len; ++c)
+    {
+      const int p = cp.chain_patch[cp.chain_off[ch] + c];
+      patch_sums(pl, p, sum);
+      cur.assign(sum.size(), 0.0);
+      for (size_t k = 0; k < sum.size(); ++k)
+      {
+        const uint32_t w = cp.ccar[pl.poff[p] + k], cpos = w & 0xffffu;
+        CHECK(cpos == CC_NONE || cpos < prev.size(), "ccar", "chain %d patch %d entry %zu: carry position %u of %zu",
+              ch, p, k, cpos, prev.size());
+        cur[k] = ynext[k] + (cpos != CC_NONE ? prev[cpos] : 0.0) + sum[k];
+      }
+      if (c + 1 < len)
+        read_y(cp.chain_patch[cp.chain_off[ch] + c + 1]);
+      for (size_t k = 0; k < sum.size(); ++k)
+      {
+        const uint32_t v = cp.cdofs[pl.poff[p] + k];
+        if (!(v & (CD_BC | CD_SKIP)))
+          y[v & CD_MASK] = cur[k];
+        if (v & CD_BCFIRST)
+          y[v & CD_MASK] = xval((int32_t)(v & CD_MASK));
+      }
+      prev.swap(cur);
+    }
+  }
+}
+
+// the chain form of an application: the library's chain steps in place of the interior launches, then the boundary's
 void interpret_chain(const PatchPlan& pl, const ChainPlan& cp, const Reference& ref)
 {
-  const int nl = (int)pl.launch_first.size();
-  for (int o = 0; o < LOCKSTEP; ++o)
+  for (Walks walks : {TWO_CALLS, WHOLE})
   {
-    std::vector<double> y(ref.y.size(), std::numeric_limits<double>::quiet_NaN());
-    clear_output(pl, ref, y);
-    for (size_t l = 0; l < cp.launch_first.size(); ++l)
-      for (int ch : patch_order(cp.launch_first[l], cp.launch_count[l], (Order)o))
-      {
-        const int len = cp.chain_off[ch + 1] - cp.chain_off[ch];
-        std::vector<double> prev, cur, sum, ynext;
-        auto read_y = [&](int p) { // the gather of a patch is issued before the previous patch's write-back
-          ynext.assign(pl.poff[p + 1] - pl.poff[p], 0.0);
-          for (size_t k = 0; k < ynext.size(); ++k)
-            if (cp.ccar[pl.poff[p] + k] & CC_ACC)
-              ynext[k] = y[cp.cdofs[pl.poff[p] + k] & CD_MASK];
-        };
-        read_y(cp.chain_patch[cp.chain_off[ch]]);
-        for (int c = 0; c < len; ++c)
-        {
-          const int p = cp.chain_patch[cp.chain_off[ch] + c];
-          patch_sums(pl, p, sum);
-          cur.assign(sum.size(), 0.0);
-          for (size_t k = 0; k < sum.size(); ++k)
-          {
-            const uint32_t w = cp.ccar[pl.poff[p] + k], cpos = w & 0xffffu;
-            CHECK(cpos == CC_NONE || cpos < prev.size(), "ccar", "chain %d patch %d entry %zu: carry position %u of %zu",
-                  ch, p, k, cpos, prev.size());
-            cur[k] = ynext[k] + (cpos != CC_NONE ? prev[cpos] : 0.0) + sum[k];
-          }
-          if (c + 1 < len)
-            read_y(cp.chain_patch[cp.chain_off[ch] + c + 1]);
-          for (size_t k = 0; k < sum.size(); ++k)
-          {
-            const uint32_t v = cp.cdofs[pl.poff[p] + k];
-            if (!(v & (CD_BC | CD_SKIP)))
-              y[v & CD_MASK] = cur[k];
-            if (v & CD_BCFIRST)
-              y[v & CD_MASK] = xval((int32_t)(v & CD_MASK));
-          }
-          prev.swap(cur);
-        }
-      }
-    for (int l = pl.n_launch_l; l < nl; ++l)
-      run_patch_launch(pl, l, (Order)o, y);
-    compare(ref, y, "serial interpretation of the chain form", ORDER_NAME[o], 0);
+    const Application app = application("serial interpretation of the chain form", pl, &cp, walks, fp64_form(true));
+    CHECK(count_steps(app, LaunchStep::CHAINS) == (int)cp.launch_count.size(), "schedule",
+          "%d chain steps for %zu chain colours", count_steps(app, LaunchStep::CHAINS), cp.launch_count.size());
+    const int np_l = pl.n_launch_l < (int)pl.launch_first.size() ? pl.launch_first[pl.n_launch_l] : pl.npatch;
+    for (const LaunchStep& st : app.steps)
+      CHECK(st.kind != LaunchStep::PATCHES || st.first >= np_l, "schedule",
+            "the chain form launches the interior patches from %d as well", st.first);
+    interpret(pl, &cp, ref, app);
+    cover("form_chains");
   }
 }
 

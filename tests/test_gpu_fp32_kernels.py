@@ -130,6 +130,12 @@ def test_fp32_apply_full_patches(pm, P, n, merge):
     A = po.Laplacian(P, 2.0, lv.dofmap, part.xgeom, part.geom_dofmap, lv.bc_marker)
     u = np.random.default_rng(100 + P).standard_normal(lv.ndofs)
     _check_apply(op, u, A.apply(_f32(u)), lv.bc_marker)
+    if (P, n) in ((2, (4, 4, 16)), (4, (4, 4, 8))):
+        # the profile counts the kernel launches the FP32 walk of the plan issued
+        op.set_profiling(True)
+        _apply32(op, u)
+        assert op.read_profile()[1] == op.launches_per_apply()
+        op.set_profiling(False)
 
 
 # the smallest cube whose float tensor (24 B per quadrature point) is past the 128 MiB above which the kernel streams it

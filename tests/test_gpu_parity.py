@@ -772,6 +772,15 @@ def test_apply_parity_random_small_meshes(pm):
         assert _relerr(y.data_copy(), A.apply(u)) < 1e-12, (case, P, n)
 
 
+def _profiled_launches(op, x, y):
+    """The kernel launches the operator's profile counts for one application."""
+    op.set_profiling(True)
+    op(x, y)
+    n = op.read_profile()[1]
+    op.set_profiling(False)
+    return n
+
+
 # every degree, on meshes that give at least two full patches per colour (patch shapes:
 # patches.hpp patch_shape) -- the coloured launches are the path the bench times
 @pytest.mark.parametrize("P,n", [(1, (8, 8, 32)), (2, (8, 8, 32)), (3, (4, 4, 32)), (4, (4, 4, 32)), (5, (4, 4, 14)),
@@ -799,6 +808,8 @@ def test_merged_and_coloured_launches_agree(pm, P, n):
             first = y.data_copy()
             op(x, y)  # second application onto the first one's output: nothing may carry over
             got[name] = (first, op.launches_per_apply(), y.data_copy())
+            if name == "coloured":
+                assert _profiled_launches(op, x, y) == op.launches_per_apply()
     finally:
         pm.set_merge_threshold(-1)
     assert got["coloured"][1] >= 8 and got["merged"][1] == 1
@@ -853,6 +864,7 @@ def test_two_stream_halves_agree_with_oracle(pm, P, n, shuffle, monkeypatch):
         y.set(float(rep))
         op(x, y)
         assert _relerr(y.data_copy(), ref) < 1e-12, rep
+    assert _profiled_launches(op, x, y) == op.launches_per_apply()
     # captured: the fork / join become two branches of the graph
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -922,6 +934,7 @@ def test_chain_form_agrees_with_oracle(pm, n, wf, bc, monkeypatch):
         op(x, y)
         assert _relerr(y.data_copy(), ref) < 1e-12, rep
     chained = y.data_copy()
+    assert _profiled_launches(op, x, y) == colours
     op.set_chain_form(False)
     assert op.launches_per_apply() >= 8
     y.set(3.0)

@@ -390,7 +390,10 @@ def test_chain_form_requested(pm, monkeypatch):
     assert op.chain_form()  # still requested ...
     assert op.launches_per_apply() == columns  # ... and bypassed
     A = _oracle(P, kappa, sigma, part, lv)
+    op.set_profiling(True)  # (the profile counts the kernel launches of the application below)
     assert _rows(_apply(pm, op, layout, u).data_copy(), A.apply(u), u, bc) < 1e-12
+    assert op.read_profile()[1] == columns
+    op.set_profiling(False)
     # an apply that dropped the term would be this far off: on this mesh the cells are 1/4 x 1/4 x 1/64, the stiffness
     # part grows with 1 / h_z and the term is a few 1e-4 of a row (a property of the reference alone, computed on the
     # host) -- what matters is that it is many orders above the 1e-12 just asserted

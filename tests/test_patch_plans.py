@@ -5,7 +5,9 @@ dof first, which launches may store without atomics and what has to be zero befo
 on the device, which a parity test sees only when the race happens to lose.  ``tests/host/plan_check.cpp`` is a
 stand-alone program, compiled host-only together with patches.hip under the address and undefined-behaviour
 sanitizers: it builds plans for meshes it generates, checks every structural invariant and executes every schedule
-serially in exact integer arithmetic against the cell-by-cell scatter-add.  It is never loaded into Python.
+serially in exact integer arithmetic against the cell-by-cell scatter-add.  The schedule it executes is the library's:
+the steps come from the function the operator's apply walks (patches.hpp ``for_each_launch_step``), not from a model
+of it.  It is never loaded into Python.
 
 Each test runs one group of cases in a subprocess and asserts exit status 0 and the coverage flags of the group's
 summary line, so a case that silently stops reaching a path fails."""
@@ -18,21 +20,29 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pmg-dolfinx_amd", "csrc")
 
-# group -> (coverage flags its cases must reach, time limit in seconds).  Measured under the sanitizers on one core: 0.2
-# to 1.8 s per group, 3.0 s for chains_production, 0.6 s for the mutations; the limits are a few times that.
+# group -> (coverage flags its cases must reach, time limit in seconds).  Measured under the sanitizers on one core: boxes
+# 0.5 s, permuted 0.3, irregular 0.2, lists 0.7, coloured 0.6, split 2.2, chains 1.1, chains_production 3.5, transfers
+# 0.8, the mutations 0.8; the limits are a few times that.  The form_* flags: every plan is executed as the library's
+# own schedule (patches.hpp for_each_launch_step) yields it -- as the two calls of an application, as one whole walk
+# (coalesced_step: a walk that merges contiguous atomic launches was reached), as the FP32 apply walks a split plan
+# (fp32_unsplit), and in chain form.
+WALKS = ["form_two_calls", "form_whole"]
 GROUPS = {
     "boxes": (["tensor_grouping", "ragged_blocks", "below_one_patch", "single_cell_patch", "merged_interior",
-               "coloured_interior", "interior_only", "boundary_only", "zero_all_rule", "bzero_list_rule"], 10),
-    "permuted": (["ragged_blocks", "merged_interior", "coloured_interior", "interior_only"], 10),
+               "coloured_interior", "interior_only", "boundary_only", "zero_all_rule", "bzero_list_rule"] + WALKS, 10),
+    "permuted": (["ragged_blocks", "merged_interior", "coloured_interior", "interior_only", "coalesced_step"] + WALKS,
+                 10),
     "irregular": (["morton_grouping", "halved_group", "halved_group_high_degree", "merged_interior",
-                   "coloured_interior", "boundary_only"], 10),
-    "lists": (["boundary_only", "interior_only", "empty_plan", "merged_interior", "coloured_interior"], 10),
-    "coloured": (["coloured_interior", "tensor_grouping"], 10),
-    "split": (["split_plan", "split_refused", "split_refused_colours", "coloured_interior"], 10),
+                   "coloured_interior", "boundary_only", "coalesced_step"] + WALKS, 10),
+    "lists": (["boundary_only", "interior_only", "empty_plan", "merged_interior", "coloured_interior",
+               "coalesced_step"] + WALKS, 10),
+    "coloured": (["coloured_interior", "tensor_grouping"] + WALKS, 10),
+    "split": (["split_plan", "split_refused", "split_refused_colours", "coloured_interior", "fp32_unsplit"] + WALKS,
+              10),
     "chains": (["chain_ok", "chain_refused_merged", "chain_refused_split", "chain_refused_grid",
-                "chain_refused_colours", "chain_refused_few_chains"], 10),
-    "chains_production": (["chain_ok"], 20),
-    "transfers": (["coarse_coloured", "coarse_merged", "coarse_refused"], 10),
+                "chain_refused_colours", "chain_refused_few_chains", "form_chains"] + WALKS, 10),
+    "chains_production": (["chain_ok", "form_chains"] + WALKS, 20),
+    "transfers": (["coarse_coloured", "coarse_merged", "coarse_refused", "coalesced_step"] + WALKS, 10),
 }
 
 
