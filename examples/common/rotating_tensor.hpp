@@ -4,6 +4,8 @@
 // pmg_laplacian_set_coefficient_tensor.
 #pragma once
 
+#include "box_mesh.hpp"
+
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -51,5 +53,39 @@ inline std::vector<double> linear_reaction(const std::vector<double>& xgeom,
     sigma[c] = S * (1.0 + x);
   }
   return sigma;
+}
+
+// The drivers' Robin boundary (--robin A): the Dirichlet marker is kept on the face x = 0 only, and the other five
+// faces of the box carry alpha = A (1 + y) at their facet points.  `ef` are the exterior facets of the cells held
+// (local facet 0 lies on x = 0 and is dropped), `dofmap` the ascending dofmap of degree P and `x` the dof coordinates
+// [ndofs][3].  Returns the facet lists and alpha [nfacets][nd * nd], the layout of pmg_laplacian_set_robin.
+struct RobinBoundary
+{
+  std::vector<std::int32_t> cells;
+  std::vector<std::int8_t> local_facets;
+  std::vector<double> alpha;
+};
+inline RobinBoundary linear_robin(const ExteriorFacets& ef, const std::vector<std::int32_t>& dofmap,
+                                  const std::vector<double>& x, int P, double A)
+{
+  const std::size_t nd = P + 1, nf = nd * nd, N = nf * nd;
+  RobinBoundary out;
+  for (std::size_t F = 0; F < ef.cells.size(); ++F)
+  {
+    if (ef.local_facets[F] == 0)
+      continue;
+    out.cells.push_back(ef.cells[F]);
+    out.local_facets.push_back(ef.local_facets[F]);
+    for (std::int32_t t : facet_nodes(P, ef.local_facets[F]))
+      out.alpha.push_back(A * (1.0 + x[3 * (std::size_t)dofmap[(std::size_t)ef.cells[F] * N + t] + 1]));
+  }
+  return out;
+}
+// ... and its marker: `bc_marker` (the whole boundary) restricted to the dofs on x = 0
+inline void keep_marker_on_x0(std::vector<std::int8_t>& bc_marker, const std::vector<double>& x)
+{
+  for (std::size_t d = 0; d < bc_marker.size(); ++d)
+    if (x[3 * d] > 1e-12)
+      bc_marker[d] = 0;
 }
 } // namespace examples

@@ -12,6 +12,9 @@
 // stencil comparison is left out as well.
 // --reaction S adds the reaction term sigma u with sigma_c = S (1 + x_c) at the cell centre (not in the reference;
 // pmg_laplacian_set_reaction); it combines with the two above, and the stencil comparison is left out as well.
+// --robin A keeps the Dirichlet marker on the face x = 0 only and puts a Robin term with alpha = A (1 + y) at the facet
+// points of the other five faces (not in the reference; pmg_laplacian_set_robin); it combines with the three above,
+// and the stencil comparison is left out as well.
 // --lift restates the right-hand side the reference's driver has commented out (:252-255): u = the assembled load of
 // f = 0 (:133,143: the interpolation of f is commented out as well), lifted with the boundary value 1.3 (:165) and
 // set_bc -- pmg_laplacian_assemble_rhs, _apply_lifting, _set_bc on the one operator -- instead of u = 1.
@@ -37,6 +40,7 @@ int main(int argc, char** argv)
   std::size_t ndofs = 0;
   bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false;
   double reaction = 0.0; // S of --reaction; 0 = no term
+  double robin = 0.0;    // A of --robin; 0 = no term
   std::size_t batch_size = 0; // :38,46-50: cells whose geometry tensor is held at a time (0 = all, resident)
   for (int i = 1; i < argc; ++i)
   {
@@ -57,6 +61,8 @@ int main(int argc, char** argv)
       kappa_tensor = true;
     else if (!std::strcmp(argv[i], "--reaction"))
       reaction = std::atof(next());
+    else if (!std::strcmp(argv[i], "--robin"))
+      robin = std::atof(next());
     else if (!std::strcmp(argv[i], "--lift"))
       lift = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
@@ -64,7 +70,7 @@ int main(int argc, char** argv)
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--lift]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--lift]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -81,6 +87,9 @@ int main(int argc, char** argv)
     examples::BoxMesh mesh(n);
     examples::FunctionSpace V(mesh, degree, gll);
     std::cout << "Mesh " << n << "^3 hexes, degree " << degree << ", " << V.ndofs << " dofs\n";
+
+    if (robin > 0.0) // Dirichlet on x = 0 only; the other five faces carry the Robin term
+      examples::keep_marker_on_x0(V.bc_marker, V.x);
 
     auto map = std::make_shared<const IndexMap>(V.ndofs, 0);
     device_array<double> kappa(std::vector<double>(mesh.ncells(), 2.0)); // :132
@@ -107,7 +116,15 @@ int main(int argc, char** argv)
       op.handle(map);
       op.set_reaction(sigma.span()); // the library keeps the vector it builds from it
     }
-    if (kappa_field || kappa_tensor || reaction > 0.0)
+    if (robin > 0.0)
+    {
+      const examples::RobinBoundary rb
+          = examples::linear_robin(examples::exterior_facets(mesh), V.dofmap, V.x, degree, robin);
+      device_array<double> alpha(rb.alpha);
+      op.handle(map);
+      op.set_robin(rb.cells, rb.local_facets, alpha.span()); // the library keeps the vector it builds from it
+    }
+    if (kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0)
     {
       std::vector<double> kh(V.ndofs);
       // u = 1 lies in the kernel of the operator away from the boundary whatever the coefficient: a vector that
@@ -176,7 +193,7 @@ int main(int argc, char** argv)
       std::printf("CSR Matvec: %d reps, %.3f us per apply\n", nreps, ms * 1e3 / nreps);
       std::printf("CSR nnz = %zu\n", mat.nnz());
       acc::axpy(ec, -1.0, y, zc);
-      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0)
+      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0)
       {
         std::printf("Norm of z = %.15e\n", acc::norm(zc));
         std::printf("Norm of error = %.3e\n", acc::norm(ec));

@@ -27,6 +27,9 @@
 //   --kappa-tensor   a per-cell diffusion tensor on every level: eigenvalues (1, 2 + x, 4), rotated by
 //                    Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z) at the cell centre (pmg_laplacian_set_coefficient_tensor);
 //                    combines with --kappa-field, --amg, --pcg, --fp32-cycle, --csr
+//   --robin A        a Robin boundary K grad u . n + alpha u = 0 on every level: the Dirichlet marker is kept on the
+//                    face x = 0 only, the other five faces carry alpha = A (1 + y) at their facet points
+//                    (pmg_laplacian_set_robin); combines with every flag --reaction combines with, and with it
 //   --reaction S     the reaction term sigma u on every level, sigma_c = S (1 + x_c) at the cell centre
 //                    (pmg_laplacian_set_reaction); combines with --kappa-field, --kappa-tensor, --amg, --pcg,
 //                    --fp32-cycle, --csr
@@ -91,6 +94,7 @@ struct Options : examples::RankOptions
   bool kappa_field = false;    // --kappa-field: the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z
   bool kappa_tensor = false;   // --kappa-tensor: per-cell tensor, eigenvalues (1, 2 + x, 4) rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z)
   double reaction = 0.0;       // --reaction S: sigma_c = S (1 + x_c); 0 = no term
+  double robin = 0.0;          // --robin A: Dirichlet on x = 0 only, alpha = A (1 + y) on the other five faces; 0 = no term
   bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
   std::vector<int> csr_levels; // empty with --csr: every level
 };
@@ -128,6 +132,8 @@ void solve(const Options& o)
     std::vector<double> gll(nd), w(nd);
     check(pmg_gll_table(nd, gll.data(), w.data()));
     V[i] = std::make_shared<Space>(Space{std::make_shared<Element>(Element{{P}}), mesh.level(P, gll)});
+    if (o.robin > 0.0) // Dirichlet on x = 0 only; the other five faces carry the Robin term
+      examples::keep_marker_on_x0(V[i]->lv.bc_marker, V[i]->lv.x);
     const examples::PartitionLevel& lv = V[i]->lv;
     if (comm)
       maps[i] = std::make_shared<const common::IndexMap>(lv.size_local, lv.num_ghosts, lv.send_indices,
@@ -180,6 +186,14 @@ void solve(const Options& o)
       device_array<T> sigma(examples::linear_reaction(mesh.xgeom, mesh.geom_dofmap, o.reaction));
       operators[i]->handle(maps[i]);
       operators[i]->set_reaction(sigma.span());
+    }
+    if (o.robin > 0.0) // K grad u . n + alpha u = 0 on the five faces other than x = 0, at this level's facet points
+    {
+      const examples::RobinBoundary rb
+          = examples::linear_robin(mesh.exterior_facets(), lv.dofmap, lv.x, order[i], o.robin);
+      device_array<T> alpha(rb.alpha);
+      operators[i]->handle(maps[i]);
+      operators[i]->set_robin(rb.cells, rb.local_facets, alpha.span()); // (collective: a rank without a facet calls too)
     }
     operators[i]->compute_diag_inverse(maps[i]);                  // replaces :274-279 (no CSR)
 
@@ -436,6 +450,8 @@ int main(int argc, char** argv)
         o.kappa_tensor = true;
       else if (!std::strcmp(argv[i], "--reaction") && i + 1 < argc)
         o.reaction = std::atof(argv[++i]);
+      else if (!std::strcmp(argv[i], "--robin") && i + 1 < argc)
+        o.robin = std::atof(argv[++i]);
       else if (!std::strcmp(argv[i], "--csr"))
       {
         o.csr = true;
@@ -502,7 +518,7 @@ int main(int argc, char** argv)
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
                      "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
-                     "           [--kappa-field] [--kappa-tensor] [--reaction S]\n"
+                     "           [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"

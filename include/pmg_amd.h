@@ -424,7 +424,9 @@ int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op);
  * stream: not inside a stream capture (refused).  pmg_laplacian_apply_lifting, pmg_laplacian_set_bc,
  * pmg_laplacian_assemble_rhs and pmg_laplacian_assemble_neumann do not change: a diagonal term couples no unmarked row
  * to a marked column.
- * pmg_laplacian_has_reaction: 1 / 0, -1 for NULL. */
+ * pmg_laplacian_has_reaction: 1 / 0, -1 for NULL: "a sigma is set".  A Robin boundary term (pmg_laplacian_set_robin,
+ * below) is a second component of the same vector, set and removed independently: while one is set, sigma = NULL
+ * leaves the vector equal to that component, and "d" above reads d_sigma + d_R. */
 int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma, pmg_stream stream);
 int pmg_laplacian_has_reaction(pmg_laplacian op);
 /* GLL-collocated load vector b_i = sum_cells kappa * w_q * detJ_q * f_i at q = i
@@ -474,6 +476,43 @@ int pmg_laplacian_set_bc(pmg_laplacian op, const double* g, const double* x0, do
 int pmg_laplacian_assemble_neumann(pmg_laplacian op, int32_t nfacets, const int32_t* facet_cells,
                                    const int8_t* facet_local, const double* h, double* b, pmg_stream stream);
 int pmg_laplacian_lift_cell_count(pmg_laplacian op);
+/* ---- Robin boundary term: K grad u . n + alpha u = g on the listed facets (not in the reference: its drivers get
+ * boundary terms from dolfinx forms).  The weak form gains int_Gamma alpha u v ds on the operator and int_Gamma g v ds
+ * on the right-hand side.  With GLL collocation the face quadrature points are the face nodes, so the face mass matrix
+ * is diagonal, with the weights pmg_laplacian_assemble_neumann uses:
+ *     d_R[dof] = sum over listed facets F and points s with dof(F, s) = dof:  w1[i1] * w1[i2] * |dS| * alpha[F][s],
+ * zero on marked dofs, over size_local + num_ghosts (ghost entries hold this rank's facets only, as the other diagonal
+ * vectors do).  The operator becomes y = A x + (d_sigma + d_R) .* x on unmarked rows, d_sigma the vector of
+ * pmg_laplacian_set_reaction; marked rows stay y = x.  The two terms are set and removed independently; each component
+ * is kept in a buffer of its own, and the kernels read one vector: an exact copy of the only component present, or
+ * d_sigma + d_R in that order, always in the same allocation once it exists.  So everything said of the reaction term
+ * holds for this one through the same code: no apply form takes a further pass (FP64, FP32, fused restriction), the
+ * chain form is bypassed while either term is set (pmg_laplacian_launches_per_apply counts the column launches), the
+ * float copy and an inverse diagonal computed by pmg_laplacian_compute_diag_inverse -- 1 / (diag(A) + d_sigma + d_R)
+ * -- follow the call, pmg_matrix_update_values and pmg_amg_create* read the summed vector, and the smoother's
+ * eigenvalue bound and an AMG hierarchy are the caller's to renew.  Setting either term a second time, or adding the
+ * second term beside the first, rewrites the vector in place: cached V-cycle graphs stay valid.  The first term set and
+ * the last term removed change a kernel argument: they re-capture.  pmg_laplacian_set_reaction(op, NULL) while a Robin
+ * term is set leaves the vector equal to d_R.
+ *
+ * facet_cells / facet_local are HOST arrays with the conventions of pmg_laplacian_assemble_neumann: local facet =
+ * 2 * axis + side, ghost cells included (each rank lists the exterior facets of all cells it holds), and the same
+ * refusals for a cell outside the operator's lists and a facet outside 0..5.  `alpha` is a DEVICE array
+ * [nfacets][nd*nd], one value per facet point in the order of `h` there (s = i1*nd + i2, ascending coordinate, also
+ * for an operator created in another cell-local node order); per facet point, not per dof: a dof on an edge between two
+ * Robin faces gets both faces' weights.  Every value must be finite and >= 0 (all zeros is legal); the bad values are
+ * counted on the device and the count is summed over the ranks, so all ranks refuse or none does: PMG_ERR_INVALID, the
+ * message names the count, nothing has changed.  nfacets == 0 removes the term (alpha and the lists may then be NULL);
+ * a rank that holds no listed facet passes 0 too.  The call is collective on several ranks in every case.  It
+ * allocates and synchronises the stream: refused inside a stream capture.  d_R is summed with atomics: two sets of
+ * the same values agree to rounding, not bit for bit.
+ * pmg_laplacian_apply_lifting, pmg_laplacian_set_bc, pmg_laplacian_assemble_rhs and pmg_laplacian_assemble_neumann do
+ * not change: a diagonal term couples no unmarked row to a marked column.  The Robin data g (= alpha u_inf for a
+ * convective boundary alpha (u - u_inf)) enters the right-hand side through pmg_laplacian_assemble_neumann with h = g.
+ * pmg_laplacian_has_robin: 1 / 0, -1 for NULL; pmg_laplacian_has_reaction keeps meaning "a sigma is set". */
+int pmg_laplacian_set_robin(pmg_laplacian op, int32_t nfacets, const int32_t* facet_cells,
+                            const int8_t* facet_local, const double* alpha, pmg_stream stream);
+int pmg_laplacian_has_robin(pmg_laplacian op);
 int pmg_laplacian_degree(pmg_laplacian op);
 /* Geometry mode of the apply.  0 (default): the reference's data structure, the
  * stored tensor G[cell][q][6] is streamed (48 bytes per quadrature point).

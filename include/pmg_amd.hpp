@@ -754,6 +754,29 @@ public:
     check(pmg_laplacian_assemble_neumann(handle(b.map()), (std::int32_t)cells.size(), cells.data(), local_facets.data(),
                                          h.data(), b.mutable_array().data(), nullptr));
   }
+  /// Robin boundary term K grad u . n + alpha u = g on the listed facets (pmg_laplacian_set_robin; not in the
+  /// reference): host lists of cells and local facets as for assemble_neumann, alpha a device array
+  /// [nfacets][nd * nd], one finite value >= 0 per facet point.  The operator gains the diagonal face mass of alpha
+  /// beside the reaction term's vector; g enters the right-hand side through assemble_neumann.  A computed inverse
+  /// diagonal follows; an assembled MatrixOperator follows with update_values().  Empty lists remove the term.
+  /// The handle must exist: it is created with the first vector or index map the operator sees (handle(map)).
+  void set_robin(std::span<const std::int32_t> cells, std::span<const std::int8_t> local_facets,
+                 std::span<const T> alpha)
+  {
+    const std::size_t nf = (std::size_t)(_degree + 1) * (_degree + 1);
+    if (cells.size() != local_facets.size() || alpha.size() != cells.size() * nf)
+      throw std::runtime_error("MatFreeLaplacian::set_robin: list sizes do not match");
+    if (!_op)
+      throw std::runtime_error("MatFreeLaplacian: set_robin before the operator has seen an index map");
+    check(pmg_laplacian_set_robin(_op, (std::int32_t)cells.size(), cells.data(), local_facets.data(), alpha.data(),
+                                  nullptr));
+  }
+  void clear_robin()
+  {
+    if (_op)
+      check(pmg_laplacian_set_robin(_op, 0, nullptr, nullptr, nullptr, nullptr));
+  }
+  bool has_robin() const { return _op && pmg_laplacian_has_robin(_op) == 1; }
   int degree() const { return _degree; }
 
   pmg_laplacian handle(const std::shared_ptr<const IndexMap>& map)

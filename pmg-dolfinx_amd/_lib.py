@@ -113,6 +113,8 @@ _SIGS = {
     "pmg_laplacian_set_bc": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
     "pmg_laplacian_assemble_neumann": (C.c_int, [vp, C.c_int32, c_ip, c_bp, vp, vp, vp]),
     "pmg_laplacian_lift_cell_count": (C.c_int, [vp]),
+    "pmg_laplacian_set_robin": (C.c_int, [vp, C.c_int32, c_ip, c_bp, vp, vp]),
+    "pmg_laplacian_has_robin": (C.c_int, [vp]),
     "pmg_laplacian_degree": (C.c_int, [vp]),
     "pmg_laplacian_is_affine": (C.c_int, [vp]),
     "pmg_laplacian_set_geometry_mode": (C.c_int, [vp, C.c_int]),
@@ -209,7 +211,7 @@ _SIGS = {
 # functions whose int return value is a count, not a status
 _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplacian_geometry_bytes", "pmg_comm_rank", "pmg_comm_size", "pmg_comm_capture_overlaps", "pmg_cg_coefficients", "pmg_cg_compute_eigenvalues", "pmg_multigrid_apply_counts", "pmg_version",
                 "pmg_laplacian_degree", "pmg_multigrid_precision", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine",
-                "pmg_laplacian_has_coefficient_field", "pmg_laplacian_has_coefficient_tensor", "pmg_laplacian_has_reaction", "pmg_laplacian_lift_cell_count",
+                "pmg_laplacian_has_coefficient_field", "pmg_laplacian_has_coefficient_tensor", "pmg_laplacian_has_reaction", "pmg_laplacian_has_robin", "pmg_laplacian_lift_cell_count",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_layout_forward_scatters",
                 "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions"}

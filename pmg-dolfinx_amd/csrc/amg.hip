@@ -1018,7 +1018,7 @@ static int amg_create(pmg_amg* out, pmg_laplacian op, const int64_t* global_inde
         }
       }
     }
-    // the reaction term of the operator (pmg_laplacian_set_reaction): its vector on the diagonal of the owned,
+    // the diagonal term of the operator (pmg_laplacian_set_reaction, pmg_laplacian_set_robin): its vector on the diagonal of the owned,
     // unmarked rows (the vector is zero on marked dofs; a row no cell lists keeps its identity)
     if (const double* dreact = laplacian_reaction(op))
     {

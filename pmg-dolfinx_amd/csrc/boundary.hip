@@ -135,8 +135,33 @@ __global__ void set_bc_kernel(int n, const int8_t* __restrict__ bc, const double
     b[i] = alpha * (x0 ? g[i] - x0[i] : g[i]);
 }
 
-// One thread per (facet, face point s = i * nd + j over the two remaining axes in increasing axis order):
-// b[dof] += w1[i] w1[j] |row `axis` of adj(J)| h[facet][s] on unmarked owned rows.
+// The facet point gid = F * nd^2 + s of the listed facets, s = i * nd + j over the two remaining axes in increasing
+// axis order: its dof and its surface weight w1[i] w1[j] |row `axis` of adj(J)|.  false (and no geometry computed) for
+// a marked dof and for one at or past `ndofs`.
+__device__ __forceinline__ bool facet_point(long long gid, int nd, const int32_t* __restrict__ fcells,
+                                            const int8_t* __restrict__ flocal, const int32_t* __restrict__ dofmap,
+                                            const int8_t* __restrict__ bc, int32_t ndofs,
+                                            const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                                            const double* __restrict__ dphi, const double* __restrict__ w1,
+                                            int32_t& dof, double& wdS)
+{
+  const int nf = nd * nd, N = nf * nd;
+  const long long F = gid / nf;
+  const int sp = (int)(gid - F * nf), i = sp / nd, j = sp - i * nd;
+  const int cell = fcells[F], lf = flocal[F], axis = lf >> 1, fixed = (lf & 1) ? nd - 1 : 0;
+  const int t = axis == 0 ? (fixed * nd + i) * nd + j : axis == 1 ? (i * nd + fixed) * nd + j : (i * nd + j) * nd + fixed;
+  dof = dofmap[(size_t)cell * N + t];
+  if (bc[dof] || dof >= ndofs)
+    return false;
+  double K[3][3], detJ;
+  jacobian(xgeom, geom_dofmap + (size_t)cell * 8, dphi, N, t, K, detJ);
+  const double* r = K[axis];
+  const double dS = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  wdS = w1[i] * w1[j] * dS;
+  return true;
+}
+
+// One thread per facet point: b[dof] += w1[i] w1[j] |dS| h[facet][s] on unmarked owned rows.
 __global__ void neumann_kernel(long long npoints, int nd, const int32_t* __restrict__ fcells,
                                const int8_t* __restrict__ flocal, const double* __restrict__ h,
                                const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc, int32_t size_local,
@@ -147,19 +172,40 @@ __global__ void neumann_kernel(long long npoints, int nd, const int32_t* __restr
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= npoints)
     return;
-  const int nf = nd * nd, N = nf * nd;
-  const long long F = gid / nf;
-  const int sp = (int)(gid - F * nf), i = sp / nd, j = sp - i * nd;
-  const int cell = fcells[F], lf = flocal[F], axis = lf >> 1, fixed = (lf & 1) ? nd - 1 : 0;
-  const int t = axis == 0 ? (fixed * nd + i) * nd + j : axis == 1 ? (i * nd + fixed) * nd + j : (i * nd + j) * nd + fixed;
-  const int32_t dof = dofmap[(size_t)cell * N + t];
-  if (bc[dof] || dof >= size_local)
+  int32_t dof;
+  double wdS;
+  if (facet_point(gid, nd, fcells, flocal, dofmap, bc, size_local, xgeom, geom_dofmap, dphi, w1, dof, wdS))
+    atomicAdd(&b[dof], wdS * h[gid]);
+}
+
+// The face mass of a Robin term, one thread per facet point: d[dof] += w1[i] w1[j] |dS| alpha[facet][s] on the
+// unmarked dofs, ghosts included (`total` = size_local + num_ghosts: a ghost entry holds this rank's facets only).
+__global__ void robin_kernel(long long npoints, int nd, const int32_t* __restrict__ fcells,
+                             const int8_t* __restrict__ flocal, const double* __restrict__ alpha,
+                             const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc, int32_t total,
+                             const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                             const double* __restrict__ dphi, const double* __restrict__ w1, double* __restrict__ d)
+{
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= npoints)
     return;
-  double K[3][3], detJ;
-  jacobian(xgeom, geom_dofmap + (size_t)cell * 8, dphi, N, t, K, detJ);
-  const double* r = K[axis];
-  const double dS = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-  atomicAdd(&b[dof], w1[i] * w1[j] * dS * h[gid]);
+  int32_t dof;
+  double wdS;
+  if (facet_point(gid, nd, fcells, flocal, dofmap, bc, total, xgeom, geom_dofmap, dphi, w1, dof, wdS))
+    atomicAdd(&d[dof], wdS * alpha[gid]);
+}
+
+// number of entries of alpha[0, n) that are not finite and >= 0, added to *bad (zeroed by the caller)
+__global__ void robin_check_kernel(long long n, const double* __restrict__ alpha, double* __restrict__ bad)
+{
+  int mine = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+  {
+    const double v = alpha[i];
+    mine += !(v >= 0.0 && v <= 1.79769313486231570e308); // NaN fails the first comparison, +inf the second
+  }
+  if (mine)
+    atomicAdd(bad, (double)mine);
 }
 
 // do p[0, np) and q[0, nq) share memory?
@@ -176,6 +222,28 @@ int not_capturing(hipStream_t s, const char* what)
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   PMG_HIP(hipStreamIsCapturing(s, &cap));
   PMG_REQUIRE(cap == hipStreamCaptureStatusNone, "%s", what);
+  return PMG_OK;
+}
+
+// Are the (host) facet lists those of cells the operator holds, and of local facets 0..5?
+int check_facets(pmg_laplacian op, const char* who, int32_t nfacets, const int32_t* facet_cells,
+                 const int8_t* facet_local)
+{
+  if (op->listed.empty() && op->ncells > 0)
+  {
+    op->listed.assign(op->ncells, 0);
+    for (int32_t c : op->pcell_h)
+      if (c >= 0)
+        op->listed[c] = 1;
+  }
+  for (int32_t i = 0; i < nfacets; ++i)
+  {
+    const int32_t c = facet_cells[i];
+    PMG_REQUIRE(c >= 0 && c < op->ncells, "%s: facet %d: cell %d outside [0, %d)", who, i, c, op->ncells);
+    PMG_REQUIRE(op->listed[c], "%s: facet %d: cell %d is not among the operator's cells", who, i, c);
+    PMG_REQUIRE(facet_local[i] >= 0 && facet_local[i] <= 5, "%s: facet %d: local facet %d outside 0..5", who, i,
+                (int)facet_local[i]);
+  }
   return PMG_OK;
 }
 
@@ -274,23 +342,7 @@ extern "C" int pmg_laplacian_assemble_neumann(pmg_laplacian op, int32_t nfacets,
   const size_t nf = (size_t)op->nd * op->nd;
   PMG_REQUIRE(!overlaps(b, (size_t)op->layout->total(), h, (size_t)nfacets * nf),
               "pmg_laplacian_assemble_neumann: b must not alias h");
-  if (op->listed.empty() && op->ncells > 0)
-  {
-    op->listed.assign(op->ncells, 0);
-    for (int32_t c : op->pcell_h)
-      if (c >= 0)
-        op->listed[c] = 1;
-  }
-  for (int32_t i = 0; i < nfacets; ++i)
-  {
-    const int32_t c = facet_cells[i];
-    PMG_REQUIRE(c >= 0 && c < op->ncells, "pmg_laplacian_assemble_neumann: facet %d: cell %d outside [0, %d)", i, c,
-                op->ncells);
-    PMG_REQUIRE(op->listed[c], "pmg_laplacian_assemble_neumann: facet %d: cell %d is not among the operator's cells", i,
-                c);
-    PMG_REQUIRE(facet_local[i] >= 0 && facet_local[i] <= 5,
-                "pmg_laplacian_assemble_neumann: facet %d: local facet %d outside 0..5", i, (int)facet_local[i]);
-  }
+  PMG_TRY(check_facets(op, "pmg_laplacian_assemble_neumann", nfacets, facet_cells, facet_local));
   hipStream_t s = S(stream);
   PMG_TRY(not_capturing(s, "pmg_laplacian_assemble_neumann: not inside a stream capture (it uploads the facet lists)"));
   int32_t* d_cells = nullptr;
@@ -316,4 +368,79 @@ extern "C" int pmg_laplacian_assemble_neumann(pmg_laplacian op, int32_t nfacets,
   if (e != hipSuccess)
     return fail(PMG_ERR_HIP, "pmg_laplacian_assemble_neumann: %s", hipGetErrorString(e));
   return PMG_OK;
+}
+
+extern "C" int pmg_laplacian_has_robin(pmg_laplacian op) { return op ? (op->has_robin ? 1 : 0) : -1; }
+
+extern "C" int pmg_laplacian_set_robin(pmg_laplacian op, int32_t nfacets, const int32_t* facet_cells,
+                                       const int8_t* facet_local, const double* alpha, pmg_stream stream)
+{
+  PMG_REQUIRE(op, "pmg_laplacian_set_robin: NULL argument");
+  PMG_REQUIRE(nfacets >= 0, "pmg_laplacian_set_robin: negative facet count");
+  PMG_REQUIRE(nfacets == 0 || (alpha && facet_cells && facet_local), "pmg_laplacian_set_robin: NULL argument");
+  PMG_TRY(check_facets(op, "pmg_laplacian_set_robin", nfacets, facet_cells, facet_local));
+  hipStream_t s = S(stream);
+  PMG_TRY(not_capturing(s, "pmg_laplacian_set_robin: not inside a stream capture (it allocates and synchronises)"));
+  pmg_layout l = op->layout;
+  const int total = l->total();
+  const long long np = (long long)nfacets * op->nd * op->nd;
+  // every value finite and >= 0, on every rank (the count is summed over the ranks: all of them refuse, or none -- a
+  // rank without a facet takes part with a count of zero, so the call is collective whatever each rank lists)
+  double* bad = red_slot(l, 0);
+  PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
+  if (np > 0)
+    robin_check_kernel<<<(unsigned)std::min<long long>((np + 255) / 256, 1024), 256, 0, s>>>(np, alpha, bad);
+  PMG_HIP(hipGetLastError());
+  PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
+  double nbad = 0.0;
+  PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
+  if (nbad != 0.0)
+    return fail(PMG_ERR_INVALID, "pmg_laplacian_set_robin: %lld facet points have a value that is not finite and >= 0",
+                (long long)nbad);
+  if (nfacets == 0)
+  {
+    if (!op->has_robin)
+      return PMG_OK;
+    op->has_robin = false; // (a reaction term stays: the vector becomes d_sigma)
+    return laplacian_diagonal_term_changed(op, s);
+  }
+  int32_t* d_cells = nullptr;
+  int8_t* d_local = nullptr;
+  double* d_new = op->robin_buf;
+  hipError_t e = hipSuccess;
+  if (!d_new)
+    e = hipMalloc(&d_new, sizeof(double) * (total ? total : 1));
+  if (e == hipSuccess)
+    e = hipMalloc(&d_cells, sizeof(int32_t) * nfacets);
+  if (e == hipSuccess)
+    e = hipMalloc(&d_local, sizeof(int8_t) * nfacets);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_cells, facet_cells, sizeof(int32_t) * nfacets, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_local, facet_local, sizeof(int8_t) * nfacets, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) // (nothing of the operator has changed so far: a failed allocation leaves it as it was)
+  {
+    op->robin_buf = d_new;
+    // (summed with atomics in no fixed order: two sets of the same values agree to rounding, not bit for bit)
+    e = hipMemsetAsync(op->robin_buf, 0, sizeof(double) * (total ? total : 1), s);
+  }
+  if (e == hipSuccess)
+  {
+    robin_kernel<<<(unsigned)((np + 255) / 256), 256, 0, s>>>(np, op->nd, d_cells, d_local, alpha, op->dofmap, op->bc,
+                                                            total, op->xgeom, op->geom_dofmap, op->dphi_geom, op->W1,
+                                                            op->robin_buf);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(s); // the lists are released below, the caller's host arrays on return
+  (void)hipFree(d_cells);
+  (void)hipFree(d_local);
+  if (e != hipSuccess)
+  {
+    if (!op->robin_buf)
+      (void)hipFree(d_new);
+    return fail(PMG_ERR_HIP, "pmg_laplacian_set_robin: %s", hipGetErrorString(e));
+  }
+  op->has_robin = true;
+  return laplacian_diagonal_term_changed(op, s);
 }

@@ -312,7 +312,10 @@ int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_
 int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
 bool laplacian_wants_zeroed_output(pmg_laplacian op);
 const double* laplacian_diag_inv(pmg_laplacian op);
-const double* laplacian_reaction(pmg_laplacian op); // nullptr = none
+const double* laplacian_reaction(pmg_laplacian op); // the diagonal term, d_sigma + d_R; nullptr = none
+// a component of the diagonal term was set or removed (pmg_laplacian_set_reaction, pmg_laplacian_set_robin): rebuild
+// the summed vector in place and what follows it (float copy, computed inverse diagonal); waits for the stream
+int laplacian_diagonal_term_changed(pmg_laplacian op, hipStream_t s);
 pmg_layout laplacian_layout(pmg_laplacian op);
 long long laplacian_launches(pmg_laplacian op);
 long long laplacian_capture_state(pmg_laplacian op); // -1 = not capturable right now

@@ -212,7 +212,8 @@ __global__ void diagonal_kernel(long long slot0, long long nslots, int nd, int K
     atomicAdd(&diag[dof], kappa[cell] * s);
 }
 
-// (react, optional: the reaction vector, added to the diagonal of A before the inversion; zero on marked dofs)
+// (react, optional: the diagonal term's vector -- reaction and Robin components summed --, added to the diagonal of A
+// before the inversion; zero on marked dofs)
 __global__ void diag_invert_kernel(int n, const int8_t* __restrict__ bc, const double* __restrict__ react,
                                    double* __restrict__ d)
 {

@@ -255,7 +255,8 @@ int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const dou
 }
 
 const double* laplacian_diag_inv(pmg_laplacian op) { return op->diag_inv; }
-const double* laplacian_reaction(pmg_laplacian op) { return op->react; } // matrix.hip, amg.hip: nullptr = none
+// matrix.hip, amg.hip: the reaction and Robin components summed (laplacian_diagonal_term_changed); nullptr = none
+const double* laplacian_reaction(pmg_laplacian op) { return op->react; }
 pmg_layout laplacian_layout(pmg_laplacian op) { return op->layout; }
 long long laplacian_launches(pmg_laplacian op) { return op->applies; }
 LaplacianInputs laplacian_inputs(pmg_laplacian op) { return {op->P, op->ncells, op->dofmap, op->bc, op->kappa}; }
@@ -265,8 +266,9 @@ long long laplacian_capture_state(pmg_laplacian op)
 {
   if (op->profiling)
     return -1;
-  // (reaction term: the first set and the removal change a kernel argument of every apply launch, and which launches
-  // an operator in chain form issues; a later set rewrites the vector in place)
+  // (diagonal term, reaction or Robin: the first component set and the last one removed change a kernel argument of
+  // every apply launch, and which launches an operator in chain form issues; a later set of either, and the second
+  // component beside the first, rewrite the vector in place)
   // (batched geometry: the captured geometry launches carry the field's and the coefficient tensor's addresses -- one
   // epoch counts both; the resident tensor is rebuilt in place by pmg_laplacian_set_coefficient_field / _tensor, so a
   // graph over it stays valid)
@@ -670,6 +672,8 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->kfield);
   (void)hipFree(op->ktensor);
   (void)hipFree(op->react_buf);
+  (void)hipFree(op->sigma_buf);
+  (void)hipFree(op->robin_buf);
   (void)hipFree(op->react32_buf);
   (void)hipFree(op->W1);
   (void)hipFree(op->dphi_geom);
@@ -956,7 +960,56 @@ __global__ void reaction_check_kernel(int ncells, const double* __restrict__ sig
     atomicAdd(bad, (double)mine);
 }
 
-extern "C" int pmg_laplacian_has_reaction(pmg_laplacian op) { return op ? (op->react ? 1 : 0) : -1; }
+// react = d_sigma + d_R, in that order (both components present)
+__global__ void diagonal_term_sum_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
+                                         double* __restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    out[i] = a[i] + b[i];
+}
+
+namespace pmg
+{
+// The diagonal term changed: a component (d_sigma in sigma_buf, d_R in robin_buf) was set, rewritten or removed.
+// Rebuilds the one vector the kernels read -- an exact copy of the only component present, or d_sigma + d_R, always in
+// react_buf, so a second set or a second component rewrites it at the address a captured graph read it from; nullptr
+// when neither is present -- and what follows it: the float copy and a computed inverse diagonal.  apply_form,
+// pmg_laplacian_launches_per_apply and laplacian_capture_state read `react` itself.  Waits for the stream.
+int laplacian_diagonal_term_changed(pmg_laplacian op, hipStream_t s)
+{
+  const int total = op->layout->total();
+  const size_t bytes = sizeof(double) * (total ? total : 1);
+  if (!op->has_sigma && !op->has_robin)
+  {
+    op->react = nullptr; // (the allocations stay with the handle: laplacian.hpp)
+    op->react32 = nullptr;
+  }
+  else
+  {
+    if (!op->react_buf)
+      PMG_HIP(hipMalloc(&op->react_buf, bytes));
+    op->react = op->react_buf;
+    if (op->has_sigma && op->has_robin)
+    {
+      if (total > 0)
+        diagonal_term_sum_kernel<<<(total + 255) / 256, 256, 0, s>>>(total, op->sigma_buf, op->robin_buf, op->react);
+      PMG_HIP(hipGetLastError());
+    }
+    else
+      PMG_HIP(hipMemcpyAsync(op->react, op->has_sigma ? op->sigma_buf : op->robin_buf, bytes, hipMemcpyDeviceToDevice,
+                             s));
+  }
+  // what depends on the vector, each in its own buffer
+  PMG_TRY(laplacian_f32_reaction(op, s));
+  if (op->have_diag && op->diag_computed)
+    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, (pmg_stream)s));
+  PMG_HIP(hipStreamSynchronize(s));
+  return PMG_OK;
+}
+} // namespace pmg
+
+extern "C" int pmg_laplacian_has_reaction(pmg_laplacian op) { return op ? (op->has_sigma ? 1 : 0) : -1; }
 
 extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma, pmg_stream stream)
 {
@@ -970,10 +1023,9 @@ extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma,
   const int total = l->total();
   if (!sigma)
   {
-    if (!op->react)
+    if (!op->has_sigma)
       return PMG_OK;
-    op->react = nullptr; // (the allocations stay with the handle: laplacian.hpp)
-    op->react32 = nullptr;
+    op->has_sigma = false; // (a Robin term stays: the vector becomes d_R)
   }
   else
   {
@@ -990,24 +1042,19 @@ extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma,
     if (nbad != 0.0)
       return fail(PMG_ERR_INVALID, "pmg_laplacian_set_reaction: %lld cells have a value that is not finite and >= 0",
                   (long long)nbad);
-    if (!op->react_buf)
-      PMG_HIP(hipMalloc(&op->react_buf, sizeof(double) * (total ? total : 1)));
-    op->react = op->react_buf;
+    if (!op->sigma_buf)
+      PMG_HIP(hipMalloc(&op->sigma_buf, sizeof(double) * (total ? total : 1)));
+    op->has_sigma = true;
     // (summed with atomics in no fixed order: two sets of the same values agree to rounding, not bit for bit)
-    PMG_HIP(hipMemsetAsync(op->react, 0, sizeof(double) * (total ? total : 1), s));
+    PMG_HIP(hipMemsetAsync(op->sigma_buf, 0, sizeof(double) * (total ? total : 1), s));
     const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
     if (n > 0)
       reaction_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->N, op->pcell, op->xgeom, op->geom_dofmap,
                                                                  op->dphi_geom, op->gweights, op->dofmap, op->bc,
-                                                                 sigma, op->react);
+                                                                 sigma, op->sigma_buf);
     PMG_HIP(hipGetLastError());
   }
-  // what depends on the vector, each in its own buffer
-  PMG_TRY(laplacian_f32_reaction(op, s));
-  if (op->have_diag && op->diag_computed)
-    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
-  PMG_HIP(hipStreamSynchronize(s)); // the caller may free sigma on return
-  return PMG_OK;
+  return laplacian_diagonal_term_changed(op, s); // (it waits for the stream: the caller may free sigma on return)
 }
 
 extern "C" int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream stream)

@@ -34,7 +34,8 @@ struct pmg_laplacian_s
   // reaction term (pmg_laplacian_set_reaction): y = A x + react .* x on unmarked rows.  GLL collocation makes the mass
   // matrix diagonal, so the term is one vector, react[dof] = sum over the listed cells' points on the dof of
   // sigma_c w_q detJ_q (0 on marked dofs); it does not depend on G.  The apply kernels start the first patch's
-  // accumulator of a dof at react[dof] * x[dof] (stiffness_column.hpp); nullptr = none.
+  // accumulator of a dof at react[dof] * x[dof] (stiffness_column.hpp); nullptr = none.  With a Robin boundary term
+  // (pmg_laplacian_set_robin) the vector is d_sigma + d_R, or d_R alone: see sigma_buf / robin_buf below.
   double* react = nullptr;     // [size_local + num_ghosts], ghost entries as diag_inv's: this rank's cells only
   float* react32 = nullptr;    // float copy, present while react and the float tensor G32 both are
   // the two allocations behind them, made on first need and kept until the handle goes: a term that is removed and set
@@ -42,6 +43,13 @@ struct pmg_laplacian_s
   // removed, not one allocation from the next)
   double* react_buf = nullptr;
   float* react32_buf = nullptr;
+  // The vector has two components, set and removed independently: d_sigma (pmg_laplacian_set_reaction) and d_R, the
+  // face mass of a Robin boundary term (pmg_laplacian_set_robin, boundary.hip).  Each is kept in a buffer of its own,
+  // made on first need and kept with the handle; `react` is an exact copy of the only one present, or d_sigma + d_R in
+  // that order (laplacian_diagonal_term_changed), always in react_buf.
+  double* sigma_buf = nullptr; // d_sigma [size_local + num_ghosts]
+  double* robin_buf = nullptr; // d_R     [size_local + num_ghosts]
+  bool has_sigma = false, has_robin = false;
   bool diag_computed = false;  // diag_inv came from pmg_laplacian_compute_diag_inverse (it follows a change of field)
   double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell (K Kc K^T / detJ with a coefficient tensor)
   double* W1 = nullptr;        // [nd] 1-D GLL weights

@@ -327,7 +327,8 @@ int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s)
 }
 
 // The float copy of the reaction vector: in use exactly while the vector and the float tensor both exist (allocated
-// once, rewritten in place by a later set; pmg_laplacian_set_reaction(op, NULL) takes it out of use with the vector)
+// once, rewritten in place by a later set of the reaction or the Robin term; the removal of the last of the two takes
+// it out of use with the vector -- laplacian_diagonal_term_changed)
 int laplacian_f32_reaction(pmg_laplacian op, hipStream_t s)
 {
   if (!op->G32 || !op->react)

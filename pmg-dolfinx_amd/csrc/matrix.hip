@@ -153,7 +153,8 @@ __global__ void __launch_bounds__(256)
       }
       __builtin_amdgcn_wave_barrier(); // the next cell's updates stay behind this cell's
     }
-    // the reaction term of the operator (pmg_laplacian_set_reaction): diagonal, unmarked rows only
+    // the diagonal term of the operator (pmg_laplacian_set_reaction, pmg_laplacian_set_robin: their summed vector):
+    // unmarked rows only
     if (react && sub == 0)
       acc[dpos] += react[row];
   }

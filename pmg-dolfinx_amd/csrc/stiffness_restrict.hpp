@@ -8,7 +8,8 @@
 // The patch workgroup of the apply therefore restricts each cell's own contribution straight from its registers: it
 // never sums into the fine output, never writes q and never waits on a colour -- all patches of the operator go in ONE
 // launch.  On Dirichlet rows the apply's rule is q = z (stiffness_column.hpp, patch_write_back), so their share is
-// (r - z) / mult and the cell's product is dropped there.  A reaction term (pmg_laplacian_set_reaction) is diagonal:
+// (r - z) / mult and the cell's product is dropped there.  A reaction term (pmg_laplacian_set_reaction) is diagonal,
+// and so is a Robin term (pmg_laplacian_set_robin; the two arrive summed in one vector):
 // r - (A + D) z = (r - d z) - A z, so the unmarked rows' share is (r - d z) / mult and nothing else moves.
 //
 // The gather and the cell loop follow stiffness_column_kernel (WPC == 1 shapes without the transposition identity); the

@@ -276,6 +276,39 @@ class MatFreeLaplacian:
         call("pmg_laplacian_assemble_neumann", self._handle, int(cells.size), cells.ctypes.data_as(_lib.c_ip),
              local_facets.ctypes.data_as(_lib.c_bp), ptr(h), ptr(b.data), current_stream())
 
+    def set_robin(self, cells, local_facets, alpha):
+        """Robin boundary term K grad u . n + alpha u = g on the listed facets (``pmg_laplacian_set_robin``): the
+        operator gains the diagonal face mass d_R[dof] = sum of w1[i] w1[j] |dS| alpha over the facet points on the
+        dof, beside the reaction term's vector; marked rows stay y = x.  ``cells`` (int32) and ``local_facets`` (int8,
+        2 * axis + side) are host arrays as in ``assemble_neumann``, e.g. ``BoxPartition.exterior_facets()``;
+        ``alpha`` [nfacets, nd*nd] holds one finite value >= 0 per facet point in the order of ``facet_nodes`` (numpy,
+        uploaded here, or a float64 device tensor).  ``cells`` of length 0 or ``alpha=None`` removes the term.  The
+        data g enters the right-hand side through ``assemble_neumann`` with ``h = g``.  A computed inverse diagonal is
+        rebuilt; collective on several ranks; not inside a stream capture."""
+        import torch
+
+        cells = np.ascontiguousarray(cells if cells is not None else [], dtype=np.int32)
+        if alpha is None or cells.size == 0:
+            call("pmg_laplacian_set_robin", self._handle, 0, None, None, None, current_stream())
+            return
+        local_facets = np.ascontiguousarray(local_facets, dtype=np.int8)
+        if cells.ndim != 1 or cells.shape != local_facets.shape:
+            raise ValueError("set_robin: cells and local_facets are two lists of one length")
+        nf = (self.degree + 1) ** 2
+        if isinstance(alpha, torch.Tensor):
+            if alpha.dtype != torch.float64 or not alpha.is_contiguous():
+                raise TypeError("set_robin: alpha must be a contiguous float64 tensor")
+        else:
+            alpha = _dev_f64(np.asarray(alpha, dtype=np.float64).reshape(-1), self.layout.device)
+        if alpha.numel() != cells.size * nf:
+            raise ValueError(f"set_robin: alpha has {alpha.numel()} entries, {cells.size} facets need "
+                             f"{cells.size * nf}")
+        call("pmg_laplacian_set_robin", self._handle, int(cells.size), cells.ctypes.data_as(_lib.c_ip),
+             local_facets.ctypes.data_as(_lib.c_bp), ptr(alpha), current_stream())
+
+    def has_robin(self) -> bool:
+        return bool(call("pmg_laplacian_has_robin", self._handle))
+
     def lift_cell_count(self) -> int:
         """Cells that hold a marked dof (the lifting's work list); -1 before the first ``apply_lifting``."""
         return int(_lib.lib().pmg_laplacian_lift_cell_count(self._handle))

@@ -307,6 +307,18 @@ class BoxPartition:
         order = np.lexsort((facets, cells))
         return cells[order].astype(np.int32), facets[order].astype(np.int8)
 
+    def facet_point_coordinates(self, P: int, cells, local_facets) -> np.ndarray:
+        """Physical coordinates [nfacets, nd*nd, 3] of the facet points of the listed facets at degree ``P``, in the
+        order of ``facet_nodes`` (what ``assemble_neumann``'s ``h`` and ``set_robin``'s ``alpha`` are indexed by)."""
+        nd = P + 1
+        dm = self.level(P).dofmap
+        coords = self.dof_coordinates(P)
+        nodes = np.stack([facet_nodes(P, f) for f in range(6)])  # [6, nd*nd]
+        cells, local_facets = np.asarray(cells, dtype=np.int64), np.asarray(local_facets, dtype=np.int64)
+        if cells.size == 0:
+            return np.zeros((0, nd * nd, 3))
+        return coords[dm[cells[:, None], nodes[local_facets]]]
+
     def dof_coordinates(self, P: int) -> np.ndarray:
         """Physical coordinates of the local dofs [ndofs_local, 3]: trilinear image
         of the reference GLL nodes of each cell."""

@@ -26,7 +26,7 @@ class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
                  node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None,
-                 kappa_tensor=None, reaction=None):
+                 kappa_tensor=None, reaction=None, robin=None):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
@@ -42,6 +42,13 @@ class PoissonHierarchy:
         coefficient sigma >= 0 per cell; every level's operator becomes -div(K grad u) + sigma u
         (``MatFreeLaplacian.set_reaction``), set next to ``kappa_tensor``, before the diagonal and the eigenvalue
         estimate.
+
+        ``robin`` (optional): a callable mapping facet-point coordinates ``[n, 3]`` to ``alpha >= 0``, the coefficient
+        of a Robin boundary term K grad u . n + alpha u = g.  It is evaluated on every level at that level's facet
+        points of ``part.exterior_facets()`` and set on the level's operator (``MatFreeLaplacian.set_robin``) next to
+        ``reaction``, before the diagonal and the eigenvalue estimate; marked dofs carry none, so together with
+        ``dirichlet`` it describes the whole problem (a problem without any Dirichlet dof included).  The data g
+        enters the caller's right-hand side through ``assemble_neumann``.
 
         ``dirichlet`` (optional): a callable mapping dof coordinates ``[n, 3]`` to a boolean array; on every level
         the Dirichlet marker becomes the exterior dofs for which it is true (default: the whole boundary).  The rest
@@ -97,6 +104,11 @@ class PoissonHierarchy:
                 op.set_coefficient_tensor(ktensor)
             if sigma is not None:
                 op.set_reaction(sigma)
+            if robin is not None:
+                fc, fl = part.exterior_facets()
+                pts = part.facet_point_coordinates(P, fc, fl)
+                alpha = np.ascontiguousarray(robin(pts.reshape(-1, 3)), dtype=np.float64).reshape(len(fc), -1)
+                op.set_robin(fc, fl, alpha)
             op.compute_diag_inverse()  # replaces :274-279
             self.levels.append(lv)
             self.layouts.append(layout)
