@@ -586,6 +586,18 @@ int pmg_chebyshev_set_max_iterations(pmg_chebyshev s, int max_iter);
 /* solve(A, x, b, verbose), :46-91.  x is in/out. */
 int pmg_chebyshev_solve(pmg_chebyshev s, pmg_laplacian A, double* x, const double* b,
                         pmg_stream stream);
+/* The recomputed form of a smooth of two or three steps: the residual is never stored, every operator product goes to
+ * a vector of its own and each vector kernel forms what it needs from b, the products and the inverse diagonal -- three
+ * passes over the level's vectors less per smooth, the same operator applications and launches, and the same
+ * arithmetic: results equal the stored form's bit for bit.  It costs two more work vectors on the smoother, allocated
+ * on first use.  mode: -1 automatic (the default: on levels of 4 Mi dofs and more, whose vectors are streamed), 0
+ * never, 1 wherever it applies.  It applies to FP64 smooths on the matrix-free operator that return no residual or
+ * feed the fused restriction, with coloured operator launches (no zeroed output) and no ghost bookkeeping; every
+ * other smooth runs the stored loop whatever the mode.  The environment variable PMG_CHEB_RECOMPUTE=0|1 is read once,
+ * by pmg_chebyshev_create, as the initial mode.  A multigrid's captured cycles are keyed on the mode. */
+int pmg_chebyshev_set_recompute(pmg_chebyshev s, int mode);
+/* Smooths of this smoother that have taken the recomputed form so far (a replayed graph counts what it captured). */
+long long pmg_chebyshev_recomputed(pmg_chebyshev s);
 
 /* ---- Jacobi-PCG + Lanczos eigenvalue estimate (acc::CGSolver, src/cg.hpp:93-250) */
 int pmg_cg_create(pmg_cg* out, pmg_layout layout);

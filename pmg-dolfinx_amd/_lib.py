@@ -131,6 +131,8 @@ _SIGS = {
     "pmg_chebyshev_destroy": (C.c_int, [vp]),
     "pmg_chebyshev_set_max_iterations": (C.c_int, [vp, C.c_int]),
     "pmg_chebyshev_solve": (C.c_int, [vp, vp, vp, vp, vp]),
+    "pmg_chebyshev_set_recompute": (C.c_int, [vp, C.c_int]),
+    "pmg_chebyshev_recomputed": (C.c_longlong, [vp]),
     "pmg_cg_create": (C.c_int, [C.POINTER(vp), vp]),
     "pmg_cg_destroy": (C.c_int, [vp]),
     "pmg_cg_set_max_iterations": (C.c_int, [vp, C.c_int]),
@@ -214,7 +216,8 @@ _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplac
                 "pmg_laplacian_has_coefficient_field", "pmg_laplacian_has_coefficient_tensor", "pmg_laplacian_has_reaction", "pmg_laplacian_has_robin", "pmg_laplacian_lift_cell_count",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_layout_forward_scatters",
-                "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions"}
+                "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions",
+                "pmg_chebyshev_recomputed"}
 
 _lib = None
 

@@ -23,6 +23,17 @@ class Chebyshev:
     def set_max_iterations(self, max_iter: int):  # :35
         call("pmg_chebyshev_set_max_iterations", self._handle, int(max_iter))
 
+    def set_recompute(self, mode=None):
+        """The recomputed form of a smooth of two or three steps (no stored residual, three vector passes less):
+        ``None`` (or -1), the default, automatic -- on levels whose vectors are streamed; ``False`` (or 0) never;
+        ``True`` (or 1) wherever it applies.  Results are the stored form's bit for bit.  See
+        ``pmg_chebyshev_set_recompute``."""
+        call("pmg_chebyshev_set_recompute", self._handle, -1 if mode is None else int(mode))
+
+    def recomputed(self) -> int:
+        """Smooths of this smoother that have taken the recomputed form so far."""
+        return call("pmg_chebyshev_recomputed", self._handle)
+
     def solve(self, A, x: Vector, b: Vector, verbose: bool = False):  # :46-91
         from .matrix import MatrixOperator
 

@@ -228,6 +228,8 @@ template <typename T>
 struct ChebWork
 {
   T *r = nullptr, *z = nullptr, *q = nullptr;
+  // given both: the smooth may take the recomputed form, whose three operator products go to q, q1 and q2
+  T *q1 = nullptr, *q2 = nullptr;
 };
 template <typename T>
 using ApplyFnT = std::function<int(T* in, T* out)>;
@@ -254,6 +256,16 @@ enum : int
 // of its own.  A_first (optional): the operator for the FIRST application, A x, when the caller knows that x's ghosts
 // are current already (no exchange).
 // T = float (the FP32 cycle, single domain): A alone; the scalar coefficients are formed in FP64 and rounded once.
+// The recomputed form (w.q1 and w.q2 given, T = double; ChebRecomputeF in vector.hip): a smooth of two or three steps
+// that returns no residual, or leaves its last application to a fused restriction, never stores r and touches x once
+// -- three passes over the level's vectors less, same applications, same launches, the same arithmetic bit for bit.
+// It needs plain operator outputs and no ghost bookkeeping; everywhere else the stored loop runs.
+inline bool cheb_recompute_applies(int max_iter, int need_r, bool has_split, bool zeroed_output, bool ghosts_tracked,
+                                   bool has_first)
+{
+  return (max_iter == 2 || max_iter == 3) && (need_r == ResidualNone || (need_r == ResidualFused && has_split))
+         && !zeroed_output && !ghosts_tracked && !has_first;
+}
 template <typename T>
 int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int n, double lmax, int max_iter, T* x,
                  const T* b, int need_r, bool x_zero, hipStream_t s, bool* split = nullptr,
@@ -280,6 +292,12 @@ void launch_cheb_step(int n, double* x, double* r, double* z, const double* q, c
 void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, const double* dinv, double c1,
                        double c2, int x_final, hipStream_t s, double* clear_q = nullptr, int n_total = 0);
 void launch_cheb_residual(int n, double* r, const double* q, hipStream_t s);
+// the recomputed form's kernels (stage 1, 2, 3 of ChebRecomputeF); c = {c0, c1 and c2 of step 1, c1 and c2 of step 2}
+void launch_cheb_recompute(int n, int stage, double* x, double* r_out, double* z_out, const double* b,
+                           const double* q0, const double* q1, const double* q2, const double* dinv, const double c[5],
+                           hipStream_t s);
+// does a level of n dofs stream its vectors (the nt policy of the smoother kernels)?
+bool vector_streams(int n);
 void launch_add(int n, double* x, const double* z, hipStream_t s);
 void launch_cheb_last(int n, double* x, double* r, const double* z, const double* q, bool assign, hipStream_t s);
 void launch_zero(int n, double* x, hipStream_t s);

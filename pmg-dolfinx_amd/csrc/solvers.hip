@@ -27,6 +27,11 @@ struct pmg_chebyshev_s
   double eig_min = 0, eig_max = 1;
   int max_iter = 1;
   double *r = nullptr, *z = nullptr, *q = nullptr; // work vectors (src/chebyshev.hpp:28-32)
+  // the recomputed form (pmg_chebyshev_set_recompute): -1 automatic, 0 never, 1 wherever it applies; the two further
+  // product vectors are allocated on its first use; recomputed = smooths that have taken it
+  int recompute_mode = -1;
+  double *q1 = nullptr, *q2 = nullptr;
+  long long recomputed = 0;
 };
 
 struct pmg_cg_s
@@ -71,6 +76,7 @@ struct pmg_multigrid_s
     hipGraphExec_t exec;
     std::vector<int> counts;
     int fused_count;
+    std::vector<int> recomputed; // per level: smooths of the captured cycle in the recomputed form
   };
   int graph_mode = -1; // pmg_multigrid_set_graph: 1 replay when capturable, 0 never, -1 (default) automatic: use_graph()
   std::vector<GraphEntry> graphs;
@@ -102,6 +108,34 @@ namespace pmg
 //                               b - A x = w.r - A w.z, for a restriction that forms A w.z on the fly
 //                               (interp_restrict_residual); a one-step smoother keeps its path and returns false.
 // T = float: the same loop on the float passes (vector.hip); every coefficient is formed in FP64 and rounded once.
+
+// The recomputed form of a smooth of k = 2 or 3 steps (cheb_recompute_applies, common.hpp), per entry the arithmetic
+// of the stored loop below: q0 = A x, q1 = A z_1, q2 = A z_2 each in a buffer of its own, and three (k = 2: two)
+// vector kernels that form the residual ((b - q0) - q1) - q2 in registers.  The last application is never issued:
+// without a residual nobody reads it, and in ResidualFused it is the consumer's (w.r, w.z as the stored loop leaves
+// them).  Launches and applications are those of the stored loop.
+static int cheb_iterate_recomputed(const ChebWork<double>& w, const ApplyFn& A, const double* dinv, int n, double lmax,
+                                   int k, double* x, const double* b, bool fused, bool x_zero, hipStream_t s)
+{
+  auto c1 = [](double i) { return (2.0 * i - 1.0) / (2.0 * i + 3.0); };
+  auto c2 = [lmax](double i) { return (8.0 * i + 4.0) / (2.0 * i + 3.0) / lmax; };
+  const double c[5] = {4.0 / (3.0 * lmax), c1(1), c2(1), c1(2), c2(2)};
+  const double* q0 = x_zero ? nullptr : w.q;
+  if (!x_zero)
+    PMG_TRY(A(x, w.q)); // :56
+  launch_cheb_recompute(n, 1, nullptr, nullptr, w.z, b, q0, nullptr, nullptr, dinv, c, s);
+  PMG_TRY(A(w.z, w.q1)); // :76, step 1
+  if (k == 3)
+  {
+    launch_cheb_recompute(n, 2, nullptr, nullptr, w.z, b, q0, w.q1, nullptr, dinv, c, s);
+    PMG_TRY(A(w.z, w.q2)); // :76, step 2
+  }
+  launch_cheb_recompute(n, 3, x, fused ? w.r : nullptr, fused ? w.z : nullptr, b, q0, w.q1, k == 3 ? w.q2 : nullptr,
+                        dinv, c, s);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
 template <typename T>
 int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int n, double lmax, int max_iter, T* x,
                  const T* b, int need_r, bool x_zero, hipStream_t s, bool* split, const ApplyFnT<T>* A_zeroed,
@@ -114,6 +148,19 @@ int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int 
   const ApplyFnT<T>& An = A_zeroed ? *A_zeroed : A; // ... which then needs no zero-fill
   const T c0 = (T)(4.0 / (3.0 * lmax));
   const int ng = track_ghosts && n_total > n ? n_total - n : 0; // ghost entries of x kept current (see common.hpp)
+  if constexpr (sizeof(T) == 8)
+  {
+    if (w.q1 && w.q2
+        && cheb_recompute_applies(max_iter, need_r, split != nullptr, A_zeroed != nullptr, ng > 0, A_first != nullptr))
+    {
+      const bool fused = need_r == ResidualFused;
+      if (fused)
+        *split = true; // x is final; w.r and w.z are what the consumer reads
+      return cheb_iterate_recomputed(w, A, dinv, n, lmax, max_iter, x, b, fused, x_zero, s);
+    }
+  }
+  else // the float loop keeps the stored form: no silent mixing
+    PMG_REQUIRE(!w.q1 && !w.q2, "cheb_iterate: the FP32 passes have no recomputed form");
   if (x_zero)
   {
     launch_cheb_init(n, w.r, w.z, b, nullptr, dinv, c0, s, clear_q, n_total);
@@ -199,6 +246,32 @@ int alloc_vec(pmg_layout l, T** p)
   return PMG_OK;
 }
 
+// Does this smoother take the recomputed form where a call qualifies?  On request, or by default where the level's
+// vectors are streamed: there a pass costs its bytes and three passes less per smooth show in the cycle
+// (profiles/chebyshev_recompute.md); a resident level's passes are cheap and the form would only add two vectors.
+bool wants_recompute(pmg_chebyshev sm)
+{
+  if (sm->max_iter != 2 && sm->max_iter != 3)
+    return false;
+  return sm->recompute_mode >= 0 ? sm->recompute_mode == 1 : vector_streams(sm->layout->size_local);
+}
+
+// the form's two further product vectors, on first use; a stream that is being captured cannot allocate: the call then
+// keeps the stored form (mg_apply_graph allocates before it captures)
+int recompute_buffers(pmg_chebyshev sm, hipStream_t s)
+{
+  if (sm->q1 && sm->q2)
+    return PMG_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (s && hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+    return PMG_OK;
+  if (!sm->q1)
+    PMG_TRY(alloc_vec(sm->layout, &sm->q1));
+  if (!sm->q2)
+    PMG_TRY(alloc_vec(sm->layout, &sm->q2));
+  return PMG_OK;
+}
+
 // src/chebyshev.hpp:46-91 on the operator `A` (see cheb_iterate)
 // track_ghosts / x_ghosts_current: the exchange bookkeeping of the V-cycle, see cheb_iterate (common.hpp)
 int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, int need_r,
@@ -207,14 +280,29 @@ int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, in
 {
   pmg_layout l = sm->layout;
   PMG_REQUIRE(laplacian_layout(A) == l, "Chebyshev: operator and smoother layouts differ");
-  const ChebWork<double> w{sm->r, sm->z, sm->q};
+  ChebWork<double> w{sm->r, sm->z, sm->q};
+  const bool zeroed = laplacian_wants_zeroed_output(A);
+  // the recomputed form, where the smoother's mode asks for it and this call qualifies (the test cheb_iterate makes)
+  bool recompute = wants_recompute(sm)
+                   && cheb_recompute_applies(sm->max_iter, need_r, split != nullptr, zeroed,
+                                             track_ghosts && l->total() > l->size_local, x_ghosts_current);
+  if (recompute)
+  {
+    PMG_TRY(recompute_buffers(sm, s));
+    recompute = sm->q1 && sm->q2;
+    w.q1 = sm->q1;
+    w.q2 = sm->q2;
+  }
   // eig_range[0] is unused (src/chebyshev.hpp:51); no per-call D2D copy of the diagonal (:53)
   const ApplyFn apply = [A, s](double* in, double* out) { return laplacian_apply(A, in, out, s); };
   const ApplyFn apply_zeroed = [A, s](double* in, double* out) { return laplacian_apply_zeroed(A, in, out, s); };
   const ApplyFn apply_local = [A, s](double* in, double* out) { return laplacian_apply_ghosts_current(A, in, out, s); };
-  return cheb_iterate(w, apply, laplacian_diag_inv(A), l->size_local, sm->eig_max, sm->max_iter, x, b, need_r, x_zero,
-                      s, split, laplacian_wants_zeroed_output(A) ? &apply_zeroed : nullptr, l->total(), track_ghosts,
-                      x_ghosts_current ? &apply_local : nullptr);
+  PMG_TRY(cheb_iterate(w, apply, laplacian_diag_inv(A), l->size_local, sm->eig_max, sm->max_iter, x, b, need_r, x_zero,
+                       s, split, zeroed ? &apply_zeroed : nullptr, l->total(), track_ghosts,
+                       x_ghosts_current ? &apply_local : nullptr));
+  if (recompute)
+    sm->recomputed++;
+  return PMG_OK;
 }
 
 // the same smoother on the assembled operator `M`: its product, its own inverse diagonal (single domain: no ghosts);
@@ -537,6 +625,9 @@ extern "C" int pmg_chebyshev_create(pmg_chebyshev* out, pmg_layout layout, doubl
   PMG_TRY(alloc_vec(layout, &sm->r));
   PMG_TRY(alloc_vec(layout, &sm->z));
   PMG_TRY(alloc_vec(layout, &sm->q));
+  if (const char* e = std::getenv("PMG_CHEB_RECOMPUTE")) // the initial mode of pmg_chebyshev_set_recompute
+    if ((e[0] == '0' || e[0] == '1') && !e[1])
+      sm->recompute_mode = e[0] - '0';
   *out = guard.release();
   return PMG_OK;
 }
@@ -548,9 +639,22 @@ extern "C" int pmg_chebyshev_destroy(pmg_chebyshev sm)
   (void)hipFree(sm->r);
   (void)hipFree(sm->z);
   (void)hipFree(sm->q);
+  (void)hipFree(sm->q1);
+  (void)hipFree(sm->q2);
   delete sm;
   return PMG_OK;
 }
+
+extern "C" int pmg_chebyshev_set_recompute(pmg_chebyshev sm, int mode)
+{
+  PMG_REQUIRE(sm, "pmg_chebyshev_set_recompute: NULL argument");
+  PMG_REQUIRE(mode >= -1 && mode <= 1, "pmg_chebyshev_set_recompute: mode %d (-1 automatic, 0 never, 1 wherever it applies)",
+              mode);
+  sm->recompute_mode = mode; // (part of the key of a multigrid's captured cycles: capture_config)
+  return PMG_OK;
+}
+
+extern "C" long long pmg_chebyshev_recomputed(pmg_chebyshev sm) { return sm ? sm->recomputed : -1; }
 
 extern "C" int pmg_chebyshev_set_max_iterations(pmg_chebyshev sm, int max_iter)
 {
@@ -1003,6 +1107,7 @@ long long capture_config(pmg_multigrid mg)
     if (i + 1 < mg->L)
       mix((uint64_t)(uintptr_t)mg->interps[i]);
     mix((uint64_t)mg->smoothers[i]->max_iter);
+    mix((uint64_t)(mg->smoothers[i]->recompute_mode + 1)); // the form decides which buffers the cycle's kernels hold
     uint64_t bits;
     static_assert(sizeof(bits) == sizeof(double), "");
     memcpy(&bits, &mg->smoothers[i]->eig_max, sizeof(bits));
@@ -1042,12 +1147,22 @@ int mg_apply_graph(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, 
       PMG_HIP(hipGraphLaunch(g.exec, s));
       mg->counts = g.counts;
       mg->fused_count = g.fused_count;
+      for (int i = 0; i < mg->L; ++i)
+        mg->smoothers[i]->recomputed += g.recomputed[i];
       mg->graph_replays++;
       *done = true;
       return PMG_OK;
     }
   if (mg->precision == PMG_PRECISION_FP32) // allocations and conversions on the caller's stream, outside the capture
     PMG_TRY(mg_prepare_f32(mg, s));
+  else // ... and so are the product vectors of the smoothers that take the recomputed form in this cycle
+    for (int i = 0; i < mg->L; ++i)
+      if (!mg->mats[i] && wants_recompute(mg->smoothers[i]) && !laplacian_wants_zeroed_output(mg->ops[i])
+          && !local_correction(mg, i))
+        PMG_TRY(recompute_buffers(mg->smoothers[i], s));
+  std::vector<long long> recomputed_before(mg->L);
+  for (int i = 0; i < mg->L; ++i)
+    recomputed_before[i] = mg->smoothers[i]->recomputed;
   if (!mg->capture_stream)
     PMG_HIP(hipStreamCreateWithFlags(&mg->capture_stream, hipStreamNonBlocking));
   PMG_HIP(hipStreamBeginCapture(mg->capture_stream, hipStreamCaptureModeRelaxed));
@@ -1062,7 +1177,9 @@ int mg_apply_graph(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, 
   }
   if (e != hipSuccess || !graph)
     return fail(PMG_ERR_HIP, "capturing the V-cycle failed: %s", hipGetErrorString(e));
-  pmg_multigrid_s::GraphEntry g{rhs, y, y_zero, (uint64_t)cfg, nullptr, mg->counts, mg->fused_count};
+  pmg_multigrid_s::GraphEntry g{rhs, y, y_zero, (uint64_t)cfg, nullptr, mg->counts, mg->fused_count, {}};
+  for (int i = 0; i < mg->L; ++i)
+    g.recomputed.push_back((int)(mg->smoothers[i]->recomputed - recomputed_before[i]));
   const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
   (void)hipGraphDestroy(graph);
   if (ei != hipSuccess)

@@ -235,6 +235,26 @@ __device__ __forceinline__ void st2(double* p, int i, double2 v)
     D2(p)[i] = v;
 }
 
+// The two products of the smoother that a later sum could absorb, with their roundings fixed.  Under the default
+// contraction the compiler fuses a product into whichever sum consumes it, and that differs from kernel to kernel: the
+// stored passes read z back from memory, the recomputed ones (ChebRecomputeF) hold it in registers next to the sums
+// that use it.  Every pass calls these two, so both forms round alike and agree bit for bit:
+//   z_1 = (c0 dinv) r            -- two rounded products, never part of a fused multiply-add;
+//   z_{i+1} = fma(c1, z_i, (c2 dinv) r)  -- two rounded products and one fused multiply-add.
+template <typename T>
+__device__ __forceinline__ T cheb_first_correction(T c0, T d, T r)
+{
+#pragma clang fp contract(off)
+  return c0 * d * r;
+}
+template <typename T>
+__device__ __forceinline__ T cheb_correction(T c1, T z, T c2, T d, T r)
+{
+#pragma clang fp contract(off)
+  const T t = c2 * d * r;
+  return fma(c1, z, t);
+}
+
 template <typename T, bool NT>
 struct ChebInitF
 { // r = b - q ; z = c0 * dinv * r   (src/chebyshev.hpp:57,67-68); q == nullptr: r = b
@@ -255,13 +275,13 @@ struct ChebInitF
       vr.y -= vq.y;
     }
     st2<NT>(r, i, vr);
-    D2(z)[i] = make_double2(c0 * vd.x * vr.x, c0 * vd.y * vr.y);
+    D2(z)[i] = make_double2(cheb_first_correction(c0, vd.x, vr.x), cheb_first_correction(c0, vd.y, vr.y));
   }
   __device__ void one(int i) const
   {
     T vr = b[i] - (q ? q[i] : T(0));
     r[i] = vr;
-    z[i] = c0 * dinv[i] * vr;
+    z[i] = cheb_first_correction(c0, dinv[i], vr);
   }
 };
 // The iterate absorbs every correction z_{i+1} in the kernel that computes it (x is streamed by that
@@ -290,8 +310,8 @@ struct ChebStepF
     }
     vr.x -= vq.x;
     vr.y -= vq.y;
-    vz.x = c1 * vz.x + c2 * vd.x * vr.x;
-    vz.y = c1 * vz.y + c2 * vd.y * vr.y;
+    vz.x = cheb_correction(c1, vz.x, c2, vd.x, vr.x);
+    vz.y = cheb_correction(c1, vz.y, c2, vd.y, vr.y);
     vx.x += vz.x;
     vx.y += vz.y;
     if (x_final)
@@ -310,7 +330,7 @@ struct ChebStepF
     if constexpr (BOTH)
       vx += vz;
     T vr = r[i] - q[i];
-    vz = c1 * vz + c2 * dinv[i] * vr;
+    vz = cheb_correction(c1, vz, c2, dinv[i], vr);
     if (x_final != 2)
     {
       r[i] = vr;
@@ -336,8 +356,8 @@ struct ChebFirstF
     double2 vx = vz;
     vr.x -= vq.x;
     vr.y -= vq.y;
-    vz.x = c1 * vz.x + c2 * vd.x * vr.x;
-    vz.y = c1 * vz.y + c2 * vd.y * vr.y;
+    vz.x = cheb_correction(c1, vz.x, c2, vd.x, vr.x);
+    vz.y = cheb_correction(c1, vz.y, c2, vd.y, vr.y);
     if (x_final)
       D2(x)[i] = make_double2(vx.x + vz.x, vx.y + vz.y);
     else
@@ -353,13 +373,98 @@ struct ChebFirstF
     T vz = z[i];
     const T vx = vz;
     T vr = r[i] - q[i];
-    vz = c1 * vz + c2 * dinv[i] * vr;
+    vz = cheb_correction(c1, vz, c2, dinv[i], vr);
     if (x_final != 2)
     {
       r[i] = vr;
       z[i] = vz;
     }
     x[i] = vx + vz;
+  }
+};
+// The recomputed form of a smooth of two or three steps (cheb_iterate): the residual is never stored and x is touched
+// once.  Every operator product has a buffer of its own (q0 = A x, q1 = A z_1, q2 = A z_2) and each kernel forms what
+// it needs from b, the products and dinv in registers, in the arithmetic of the stored passes above
+// (r = ((b - q0) - q1) - q2 in that order, the two helpers for the corrections):
+//   STAGE 1:  z_out = z_1 = c0 dinv (b - q0)
+//   STAGE 2:  r_1 = (b - q0) - q1;  z_out = z_2 = c1a z_1 + c2a dinv r_1
+//   STAGE 3:  the last kernel, over q1 and (three steps) q2:  r_2 = r_1 - q2;  z_3 = c1b z_2 + c2b dinv r_2;
+//             x = ((x + z_1) + z_2) + z_3, the sums of ChebStepF<BOTH> followed by "x += z_3"; with r_out the last
+//             residual and correction are written as well (the fused restriction reads them).
+// q0 == nullptr: x is 0 on entry, so r_0 = b and x is assigned (ChebInitF without q, ChebFirstF).
+// What the next operator application or transfer gathers (z_out, x) keeps the default cache policy; everything else is
+// streamed, r_out included, as ChebStepF stores r (with a default-policy r both stage 3 and the fused restriction
+// behind it ran slower: profiles/chebyshev_recompute.md).
+template <bool NT, int STAGE>
+struct ChebRecomputeF
+{
+  double* x;
+  double* r_out;
+  double* z_out;
+  const double *b, *q0, *q1, *q2, *dinv;
+  double c0, c1a, c2a, c1b, c2b;
+  // one entry: vx is the iterate (in and out, STAGE 3), vr and vz come back as the last residual and correction
+  __device__ __forceinline__ void entry(double& vx, double& vr, double& vz, double vb, double vd, double v0, double v1,
+                                        double v2) const
+  {
+    vr = q0 ? vb - v0 : vb;
+    vz = cheb_first_correction(c0, vd, vr);
+    if constexpr (STAGE >= 2)
+    {
+      if constexpr (STAGE == 3)
+        vx = q0 ? vx + vz : vz;
+      vr -= v1;
+      vz = cheb_correction(c1a, vz, c2a, vd, vr);
+      if constexpr (STAGE == 3)
+      {
+        vx += vz;
+        if (q2)
+        {
+          vr -= v2;
+          vz = cheb_correction(c1b, vz, c2b, vd, vr);
+          vx += vz;
+        }
+      }
+    }
+  }
+  __device__ void pair(int i) const
+  {
+    const double2 zero = make_double2(0.0, 0.0);
+    const double2 vb = ld2<NT>(b, i), vd = ld2<NT>(dinv, i);
+    const double2 v0 = q0 ? ld2<NT>(q0, i) : zero;
+    const double2 v1 = STAGE >= 2 ? ld2<NT>(q1, i) : zero;
+    const double2 v2 = (STAGE == 3 && q2) ? ld2<NT>(q2, i) : zero;
+    double2 vx = (STAGE == 3 && q0) ? ld2<NT>(x, i) : zero;
+    double2 vr, vz;
+    entry(vx.x, vr.x, vz.x, vb.x, vd.x, v0.x, v1.x, v2.x);
+    entry(vx.y, vr.y, vz.y, vb.y, vd.y, v0.y, v1.y, v2.y);
+    if constexpr (STAGE == 3)
+    {
+      D2(x)[i] = vx;
+      if (r_out)
+      {
+        st2<NT>(r_out, i, vr);
+        D2(z_out)[i] = vz;
+      }
+    }
+    else
+      D2(z_out)[i] = vz;
+  }
+  __device__ void one(int i) const
+  {
+    double vx = (STAGE == 3 && q0) ? x[i] : 0.0, vr, vz;
+    entry(vx, vr, vz, b[i], dinv[i], q0 ? q0[i] : 0.0, STAGE >= 2 ? q1[i] : 0.0, (STAGE == 3 && q2) ? q2[i] : 0.0);
+    if constexpr (STAGE == 3)
+    {
+      x[i] = vx;
+      if (r_out)
+      {
+        r_out[i] = vr;
+        z_out[i] = vz;
+      }
+    }
+    else
+      z_out[i] = vz;
   }
 };
 template <typename T, bool NT>
@@ -665,6 +770,32 @@ void launch_cheb_first(int n, double* x, double* r, double* z, const double* q, 
     ew_launch(n, v, ChebFirstF<double, true>{x, r, z, q, dinv, c1, c2, xf}, s);
   else
     ew_launch(n, v, ChebFirstF<double, false>{x, r, z, q, dinv, c1, c2, xf}, s);
+}
+bool vector_streams(int n) { return streams(n); }
+// One kernel of the recomputed form (ChebRecomputeF): stage 1, 2 write z_out; stage 3 updates x and, with r_out, writes
+// r_out and z_out.  q0 == nullptr: from x = 0; q2 == nullptr in stage 3: a smooth of two steps.
+// c = {c0, c1 and c2 of step 1, c1 and c2 of step 2}.
+void launch_cheb_recompute(int n, int stage, double* x, double* r_out, double* z_out, const double* b,
+                           const double* q0, const double* q1, const double* q2, const double* dinv, const double c[5],
+                           hipStream_t s)
+{
+  bool v = aligned16(b) && aligned16(dinv);
+  for (const void* p : {(const void*)x, (const void*)r_out, (const void*)z_out, (const void*)q0, (const void*)q1,
+                        (const void*)q2})
+    v = v && (!p || aligned16(p));
+  auto go = [&](auto f)
+  {
+    f.x = x, f.r_out = r_out, f.z_out = z_out, f.b = b, f.q0 = q0, f.q1 = q1, f.q2 = q2, f.dinv = dinv;
+    f.c0 = c[0], f.c1a = c[1], f.c2a = c[2], f.c1b = c[3], f.c2b = c[4];
+    ew_launch(n, v, f, s);
+  };
+  const bool nt = streams(n);
+  if (stage == 1)
+    nt ? go(ChebRecomputeF<true, 1>{}) : go(ChebRecomputeF<false, 1>{});
+  else if (stage == 2)
+    nt ? go(ChebRecomputeF<true, 2>{}) : go(ChebRecomputeF<false, 2>{});
+  else
+    nt ? go(ChebRecomputeF<true, 3>{}) : go(ChebRecomputeF<false, 3>{});
 }
 void launch_cheb_last(int n, double* x, double* r, const double* z, const double* q, bool assign,
                       hipStream_t s)

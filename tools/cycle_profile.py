@@ -51,7 +51,7 @@ def run(argv):
 def family(n):
     n = n.replace("(anonymous namespace)::", "").replace("void ", "")
     m = re.match(r"(stiffness_restrict_kernel<\d, \d)|(stiffness_column_kernel<\d)|(restrict_patch_kernel<\d, \d)|"
-                 r"(prolong_patch_kernel<\d, \d)|ew_kernel2<(\w+)|(\w+)", n)
+                 r"(prolong_patch_kernel<\d, \d)|ew_kernel2<(Cheb\w+<[\w, ]+)|ew_kernel2<(\w+)|(\w+)", n)
     return next(g for g in m.groups() if g) if m else n[:40]
 
 
