@@ -634,34 +634,49 @@ int alloc_d(double** p, size_t n)
   return PMG_OK;
 }
 
+// The smooths of the hierarchy: k steps on a plain product (a CSR level, the fine operator), single domain.
+SmoothCall smooth_call(int k, int need_r, bool x_zero)
+{
+  SmoothCall c;
+  c.k = k, c.need_r = need_r, c.x_zero = x_zero;
+  return c;
+}
+SmoothData<double> smooth_data(const ChebWork<double>& w, ApplyFn A, const double* dinv, int n, double lmax, double* x,
+                               const double* b, hipStream_t s)
+{
+  SmoothData<double> d;
+  d.w = w;
+  d.apply[SmoothStep::PLAIN] = std::move(A);
+  d.dinv = dinv, d.n = d.n_total = n, d.lmax = lmax, d.x = x, d.b = b, d.s = s;
+  return d;
+}
+
 // One V(k, k) cycle on level l: x = cycle(b), from a zero initial guess.
 int amg_cycle(pmg_amg amg, int l, double* x, const double* b, hipStream_t s)
 {
   const int L = (int)amg->levels.size();
   AmgLevel& lv = amg->levels[l];
+  if (l == L - 1 && amg->dense_inv)
+  {
+    if (lv.n > 0)
+      dense_apply_kernel<<<(lv.n * 64 + 255) / 256, 256, 0, s>>>(lv.n, amg->dense_inv, b, x);
+    PMG_HIP(hipGetLastError());
+    return PMG_OK;
+  }
+  const SmoothData<double> sd = smooth_data(
+      {lv.r, lv.z, lv.q}, [&lv, s](double* in, double* out) { return csr_product<0>(lv.A, in, nullptr, out, s); },
+      lv.dinv, lv.n, lv.lmax, x, b, s);
   if (l == L - 1)
   {
-    if (amg->dense_inv)
-    {
-      if (lv.n > 0)
-        dense_apply_kernel<<<(lv.n * 64 + 255) / 256, 256, 0, s>>>(lv.n, amg->dense_inv, b, x);
-      PMG_HIP(hipGetLastError());
-      return PMG_OK;
-    }
     // a coarsest level too large to invert: smooth it harder
-    const ChebWork<double> w{lv.r, lv.z, lv.q};
-    return cheb_iterate<double>(
-        w, [&lv, s](double* in, double* out) { return csr_product<0>(lv.A, in, nullptr, out, s); }, lv.dinv, lv.n,
-        lv.lmax, 4 * amg->smoother_its, x, b, ResidualNone, true, s);
+    return cheb_iterate(smooth_call(4 * amg->smoother_its, ResidualNone, true), sd);
   }
-  const ChebWork<double> w{lv.r, lv.z, lv.q};
-  const ApplyFn A = [&lv, s](double* in, double* out) { return csr_product<0>(lv.A, in, nullptr, out, s); };
   AmgLevel& lc = amg->levels[l + 1];
-  PMG_TRY(cheb_iterate(w, A, lv.dinv, lv.n, lv.lmax, amg->smoother_its, x, b, ResidualUpdated, true, s)); // leaves r = b - A x
+  PMG_TRY(cheb_iterate(smooth_call(amg->smoother_its, ResidualUpdated, true), sd)); // leaves r = b - A x
   PMG_TRY(csr_product<0>(lv.R, lv.r, nullptr, lc.b, s));
   PMG_TRY(amg_cycle(amg, l + 1, lc.x, lc.b, s));
   PMG_TRY(csr_product<2>(lv.P, lc.x, nullptr, x, s)); // x += P x_c
-  PMG_TRY(cheb_iterate(w, A, lv.dinv, lv.n, lv.lmax, amg->smoother_its, x, b, ResidualNone, false, s));
+  PMG_TRY(cheb_iterate(smooth_call(amg->smoother_its, ResidualNone, false), sd));
   return PMG_OK;
 }
 } // namespace
@@ -788,18 +803,18 @@ int dist_cycle(pmg_amg amg, double* x, const double* b, hipStream_t s)
   const int n = l->size_local;
   AmgLevel& l0 = amg->levels[0];
   AmgLevel& l1 = amg->levels[1];
-  const ChebWork<double> w{amg->d0_r, amg->d0_z, amg->d0_q};
-  const ApplyFn A = [op, s](double* in, double* out) { return laplacian_apply(op, in, out, s); };
   // The inverse diagonal of the hierarchy's OWN level-0 matrix, restricted to this rank (d0_dinv): the bound l0.lmax
   // was computed for D^-1 A with that diagonal, and the operator's diag_inv may never have been computed or may have
   // been replaced by the caller (pmg_laplacian_set_diag_inverse) -- ADVICE r03.
-  const double* dinv = amg->d0_dinv;
-  PMG_TRY(cheb_iterate(w, A, dinv, n, l0.lmax, amg->smoother_its, x, b, ResidualUpdated, true, s)); // r = b - A x
+  const SmoothData<double> sd = smooth_data(
+      {amg->d0_r, amg->d0_z, amg->d0_q}, [op, s](double* in, double* out) { return laplacian_apply(op, in, out, s); },
+      amg->d0_dinv, n, l0.lmax, x, b, s);
+  PMG_TRY(cheb_iterate(smooth_call(amg->smoother_its, ResidualUpdated, true), sd)); // r = b - A x
   PMG_TRY(csr_product<0>(amg->R0l, amg->d0_r, nullptr, l1.b, s)); // this rank's share of R r
   PMG_TRY(device_allreduce_sum(amg, l1.b, l1.n, s));
   PMG_TRY(amg_cycle(amg, 1, l1.x, l1.b, s));                      // replicated from here down
   PMG_TRY(csr_product<2>(amg->P0l, l1.x, nullptr, x, s));         // x += P x_c, owned rows
-  PMG_TRY(cheb_iterate(w, A, dinv, n, l0.lmax, amg->smoother_its, x, b, ResidualNone, false, s));
+  PMG_TRY(cheb_iterate(smooth_call(amg->smoother_its, ResidualNone, false), sd));
   return PMG_OK;
 }
 

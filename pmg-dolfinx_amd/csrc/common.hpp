@@ -2,6 +2,7 @@
 #pragma once
 
 #include "../../include/pmg_amd.h"
+#include "smooth_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -228,8 +229,7 @@ template <typename T>
 struct ChebWork
 {
   T *r = nullptr, *z = nullptr, *q = nullptr;
-  // given both: the smooth may take the recomputed form, whose three operator products go to q, q1 and q2
-  T *q1 = nullptr, *q2 = nullptr;
+  T *q1 = nullptr, *q2 = nullptr; // the recomputed form's further products: its three go to q, q1 and q2
 };
 template <typename T>
 using ApplyFnT = std::function<int(T* in, T* out)>;
@@ -237,40 +237,26 @@ using ApplyFn = ApplyFnT<double>;
 using PrecondFn = std::function<int(double* z, const double* r)>;
 int cg_iterate(pmg_cg cg, const ApplyFn& A, const double* dinv, const PrecondFn* M, bool flexible, double* x,
                const double* b, int* iterations, hipStream_t s);
-enum : int
-{
-  ResidualNone = 0,    // only x is wanted
-  ResidualUpdated = 1, // w.r = b - A x on return
-  ResidualSplit = 2,   // b - A x = w.r - w.q is left to the consumer when *split comes back true
-  ResidualFused = 3    // the last application is left to the consumer as well when *split comes back true:
-                       // b - A x = w.r - A w.z (a restriction fused into that application); a one-step smoother
-                       // keeps its own path and returns false with w.r = b - A x
-};
-// A_zeroed (optional): the same operator for an output vector that is already zero over [0, n_total) -- given for
-// an operator whose launch accumulates with atomics; the smoother's vector kernels then clear w.q behind themselves
-// and every application after the first goes through A_zeroed (no zero-fill kernels).
-// Ghost bookkeeping of the iterate (several ranks; round 4): every operator application refreshes the ghost entries of
-// its INPUT (src/laplacian.hpp:378,425), so the ghosts of z are current right behind A z.  With track_ghosts the
-// smoother adds them to the ghost entries of x there (a kernel over the ghost range only) -- after a smooth that
-// returns its residual, in which every correction has been applied to, x then has current ghosts without an exchange
-// of its own.  A_first (optional): the operator for the FIRST application, A x, when the caller knows that x's ghosts
-// are current already (no exchange).
-// T = float (the FP32 cycle, single domain): A alone; the scalar coefficients are formed in FP64 and rounded once.
-// The recomputed form (w.q1 and w.q2 given, T = double; ChebRecomputeF in vector.hip): a smooth of two or three steps
-// that returns no residual, or leaves its last application to a fused restriction, never stores r and touches x once
-// -- three passes over the level's vectors less, same applications, same launches, the same arithmetic bit for bit.
-// It needs plain operator outputs and no ghost bookkeeping; everywhere else the stored loop runs.
-inline bool cheb_recompute_applies(int max_iter, int need_r, bool has_split, bool zeroed_output, bool ghosts_tracked,
-                                   bool has_first)
-{
-  return (max_iter == 2 || max_iter == 3) && (need_r == ResidualNone || (need_r == ResidualFused && has_split))
-         && !zeroed_output && !ghosts_tracked && !has_first;
-}
+// The smoother's control flow is not here: smooth_plan.hpp decides once, on the host, which applications and passes a
+// call issues (SmoothCall -> for_each_smooth_step) and what it leaves to its consumer (smooth_outcome).  cheb_iterate
+// is the interpreter: it turns each step into the launch_cheb_* / launch_add / launch_zero / hipMemcpyAsync call below
+// or into an application through apply[step.variant], and returns the visitor's refusal for a call that cannot be
+// scheduled.  The caller fills in the SmoothCall from what it knows (steps, what it can consume of the residual, the
+// operator's output rule, the ghost bookkeeping, the smoother's mode and buffers) and the data the steps work on.
 template <typename T>
-int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int n, double lmax, int max_iter, T* x,
-                 const T* b, int need_r, bool x_zero, hipStream_t s, bool* split = nullptr,
-                 const ApplyFnT<T>* A_zeroed = nullptr, int n_total = 0, bool track_ghosts = false,
-                 const ApplyFnT<T>* A_first = nullptr);
+struct SmoothData
+{
+  ChebWork<T> w;        // r, z, q; q1 and q2 where the call allows the recomputed form
+  ApplyFnT<T> apply[3]; // by SmoothStep::Variant: plain, zeroed-output, ghosts-current -- those the call can ask for
+  const T* dinv = nullptr;
+  int n = 0, n_total = 0; // owned entries; with the ghosts behind them (read only with call.ghosts or zeroed_output)
+  double lmax = 1;
+  T* x = nullptr;
+  const T* b = nullptr;
+  hipStream_t s = nullptr;
+};
+template <typename T>
+int cheb_iterate(const SmoothCall& call, const SmoothData<T>& d);
 
 // vector.hip -- stream-ordered building blocks used by the solvers
 // local dot of the owned entries into the result slot `slot` of the layout (device)
@@ -303,7 +289,7 @@ void launch_cheb_last(int n, double* x, double* r, const double* z, const double
 void launch_zero(int n, double* x, hipStream_t s);
 void launch_mask_bc(int n, double* b, const int8_t* bc, hipStream_t s);
 // The same passes for the FP32 cycle: one element per lane, default cache policy.  They have no zeroed-output form: a
-// non-null clear_q ends the process with a message (cheb_iterate refuses such an operator before it gets here).
+// non-null clear_q ends the process with a message (the smooth's schedule refuses such an operator before it gets here).
 void launch_cheb_init(int n, float* r, float* z, const float* b, const float* q, const float* dinv, float c0,
                       hipStream_t s, float* clear_q = nullptr, int n_total = 0);
 void launch_cheb_step(int n, float* x, float* r, float* z, const float* q, const float* dinv, float c1, float c2,

@@ -97,135 +97,56 @@ struct pmg_multigrid_s
 
 namespace pmg
 {
-// src/chebyshev.hpp:46-91.
-//   x_zero : x is known to be 0 on entry (A 0 = 0, so r = b and x := z)
-//   need_r : ResidualNone    -- only x is wanted: the loop's last apply is skipped;
-//            ResidualUpdated -- w.r = b - A x on return (costs that last apply);
-//            ResidualSplit   -- as ResidualUpdated, but the last "r -= q" is left to the consumer when *split
-//                               comes back true: b - A x = w.r - w.q (a restriction subtracts while it gathers; a
-//                               one-step smoother, whose only kernel updates x and r together, returns false).
-//            ResidualFused   -- the last apply itself is left to the consumer when *split comes back true:
-//                               b - A x = w.r - A w.z, for a restriction that forms A w.z on the fly
-//                               (interp_restrict_residual); a one-step smoother keeps its path and returns false.
-// T = float: the same loop on the float passes (vector.hip); every coefficient is formed in FP64 and rounded once.
-
-// The recomputed form of a smooth of k = 2 or 3 steps (cheb_recompute_applies, common.hpp), per entry the arithmetic
-// of the stored loop below: q0 = A x, q1 = A z_1, q2 = A z_2 each in a buffer of its own, and three (k = 2: two)
-// vector kernels that form the residual ((b - q0) - q1) - q2 in registers.  The last application is never issued:
-// without a residual nobody reads it, and in ResidualFused it is the consumer's (w.r, w.z as the stored loop leaves
-// them).  Launches and applications are those of the stored loop.
-static int cheb_iterate_recomputed(const ChebWork<double>& w, const ApplyFn& A, const double* dinv, int n, double lmax,
-                                   int k, double* x, const double* b, bool fused, bool x_zero, hipStream_t s)
-{
-  auto c1 = [](double i) { return (2.0 * i - 1.0) / (2.0 * i + 3.0); };
-  auto c2 = [lmax](double i) { return (8.0 * i + 4.0) / (2.0 * i + 3.0) / lmax; };
-  const double c[5] = {4.0 / (3.0 * lmax), c1(1), c2(1), c1(2), c2(2)};
-  const double* q0 = x_zero ? nullptr : w.q;
-  if (!x_zero)
-    PMG_TRY(A(x, w.q)); // :56
-  launch_cheb_recompute(n, 1, nullptr, nullptr, w.z, b, q0, nullptr, nullptr, dinv, c, s);
-  PMG_TRY(A(w.z, w.q1)); // :76, step 1
-  if (k == 3)
-  {
-    launch_cheb_recompute(n, 2, nullptr, nullptr, w.z, b, q0, w.q1, nullptr, dinv, c, s);
-    PMG_TRY(A(w.z, w.q2)); // :76, step 2
-  }
-  launch_cheb_recompute(n, 3, x, fused ? w.r : nullptr, fused ? w.z : nullptr, b, q0, w.q1, k == 3 ? w.q2 : nullptr,
-                        dinv, c, s);
-  PMG_HIP(hipGetLastError());
-  return PMG_OK;
-}
-
+// src/chebyshev.hpp:46-91: the steps of smooth_plan.hpp as calls on d.s.  T = float: the same steps on the float passes
+// (vector.hip); every coefficient is formed in FP64 and rounded once.
 template <typename T>
-int cheb_iterate(const ChebWork<T>& w, const ApplyFnT<T>& A, const T* dinv, int n, double lmax, int max_iter, T* x,
-                 const T* b, int need_r, bool x_zero, hipStream_t s, bool* split, const ApplyFnT<T>* A_zeroed,
-                 int n_total, bool track_ghosts, const ApplyFnT<T>* A_first)
+int cheb_iterate(const SmoothCall& call, const SmoothData<T>& d)
 {
-  PMG_REQUIRE(sizeof(T) == 8 || !A_zeroed, "cheb_iterate: the FP32 passes have no zeroed-output form");
-  if (split)
-    *split = false;
-  T* const clear_q = A_zeroed ? w.q : nullptr;      // the vector kernels leave w.q zero for the next application
-  const ApplyFnT<T>& An = A_zeroed ? *A_zeroed : A; // ... which then needs no zero-fill
-  const T c0 = (T)(4.0 / (3.0 * lmax));
-  const int ng = track_ghosts && n_total > n ? n_total - n : 0; // ghost entries of x kept current (see common.hpp)
-  if constexpr (sizeof(T) == 8)
-  {
-    if (w.q1 && w.q2
-        && cheb_recompute_applies(max_iter, need_r, split != nullptr, A_zeroed != nullptr, ng > 0, A_first != nullptr))
+  PMG_REQUIRE(call.fp64 == (sizeof(T) == 8), "cheb_iterate: the call's scalar type is not the data's");
+  const ChebWork<T>& w = d.w;
+  const int n = d.n, ng = call.ghosts;
+  T* const x = d.x;
+  T* const product[3] = {w.q, w.q1, w.q2}; // by SmoothStep::Buffer
+  hipStream_t s = d.s;
+  PMG_TRY(for_each_smooth_step(call, [&](const SmoothStep& st) -> int {
+    T* const clear_q = st.clear_q ? w.q : nullptr;
+    const T c1 = (T)cheb_c1(st.i), c2 = (T)cheb_c2(st.i, d.lmax);
+    switch (st.kind)
     {
-      const bool fused = need_r == ResidualFused;
-      if (fused)
-        *split = true; // x is final; w.r and w.z are what the consumer reads
-      return cheb_iterate_recomputed(w, A, dinv, n, lmax, max_iter, x, b, fused, x_zero, s);
-    }
-  }
-  else // the float loop keeps the stored form: no silent mixing
-    PMG_REQUIRE(!w.q1 && !w.q2, "cheb_iterate: the FP32 passes have no recomputed form");
-  if (x_zero)
-  {
-    launch_cheb_init(n, w.r, w.z, b, nullptr, dinv, c0, s, clear_q, n_total);
-    if (ng > 0)
-      launch_zero(ng, x + n, s);
-  }
-  else
-  {
-    PMG_TRY(A_first ? (*A_first)(x, w.q) : A(x, w.q));                      // :56 (refreshes the ghosts of x)
-    launch_cheb_init(n, w.r, w.z, b, w.q, dinv, c0, s, clear_q, n_total); // :57,67-68
-  }
-  // x absorbs the correction z_{i+1} in the step kernel that computes it (the first step adds z_1 and z_2), so
-  // after the last application only the residual is left to update, and only where it is wanted.
-  for (int i = 1; i <= max_iter; ++i)
-  {
-    const bool last = (i == max_iter);
-    if (last && !need_r)
-    {
-      if (max_iter == 1) // a one-step smoother: z_1 is all there is (:73)
+    case SmoothStep::APPLY: return d.apply[st.variant](st.in_x ? x : w.z, product[st.out]);
+    case SmoothStep::INIT:
+      launch_cheb_init(n, w.r, w.z, d.b, st.with_q ? w.q : nullptr, d.dinv, (T)cheb_c0(d.lmax), s, clear_q, d.n_total);
+      break;
+    case SmoothStep::FIRST:
+      launch_cheb_first(n, x, w.r, w.z, w.q, d.dinv, c1, c2, st.x_final, s, clear_q, d.n_total);
+      break;
+    case SmoothStep::STEP:
+      launch_cheb_step(n, x, w.r, w.z, w.q, d.dinv, c1, c2, st.both, st.x_final, s, clear_q, d.n_total);
+      break;
+    case SmoothStep::LAST: launch_cheb_last(n, x, w.r, w.z, w.q, st.assign, s); break;
+    case SmoothStep::RESIDUAL: launch_cheb_residual(n, w.r, w.q, s); break;
+    case SmoothStep::ADD: launch_add(n, x, w.z, s); break;
+    case SmoothStep::GHOST_ADD: launch_add(ng, x + n, w.z + n, s); break;
+    case SmoothStep::COPY: PMG_HIP(hipMemcpyAsync(x, w.z, sizeof(T) * n, hipMemcpyDeviceToDevice, s)); break;
+    case SmoothStep::ZERO_X: launch_zero(n, x, s); break;
+    case SmoothStep::ZERO_GHOSTS: launch_zero(ng, x + n, s); break;
+    case SmoothStep::RECOMPUTE:
+      if constexpr (sizeof(T) == 8)
       {
-        if (x_zero)
-          PMG_HIP(hipMemcpyAsync(x, w.z, sizeof(T) * n, hipMemcpyDeviceToDevice, s));
-        else
-          launch_add(n, x, w.z, s);
+        const double c[5] = {cheb_c0(d.lmax), cheb_c1(1), cheb_c2(1, d.lmax), cheb_c1(2), cheb_c2(2, d.lmax)};
+        launch_cheb_recompute(n, st.stage, st.stage == 3 ? x : nullptr, st.r_out ? w.r : nullptr,
+                              st.stage < 3 || st.r_out ? w.z : nullptr, d.b, st.with_q ? w.q : nullptr,
+                              st.stage >= 2 ? w.q1 : nullptr, st.with_q2 ? w.q2 : nullptr, d.dinv, c, s);
       }
       break;
     }
-    if (last && need_r == ResidualFused && split && max_iter > 1)
-    {
-      *split = true; // x is final (x_final below); w.r and w.z are what the consumer reads
-      break;
-    }
-    PMG_TRY(An(w.z, w.q)); // :76
-    if (ng > 0)             // the ghosts of z are current now: the iterate's ghosts absorb them
-      launch_add(ng, x + n, w.z + n, s);
-    if (last) // need_r: the new z would not be used, only x and r are (:73,77)
-    {
-      if (max_iter == 1)
-        launch_cheb_last(n, x, w.r, w.z, w.q, x_zero, s);
-      else if (need_r == ResidualSplit && split)
-        *split = true;
-      else
-        launch_cheb_residual(n, w.r, w.q, s);
-      break;
-    }
-    const T c1 = (T)((2.0 * i - 1.0) / (2.0 * i + 3.0));
-    const T c2 = (T)((8.0 * i + 4.0) / (2.0 * i + 3.0) / lmax);
-    // the last correction enters x here (1); when no residual is wanted either, r and z are dead behind this step (2)
-    const int x_final = (i + 1 == max_iter) ? (need_r == ResidualNone ? 2 : 1) : 0;
-    if (x_zero && i == 1)
-      launch_cheb_first(n, x, w.r, w.z, w.q, dinv, c1, c2, x_final, s, clear_q, n_total);
-    else
-      launch_cheb_step(n, x, w.r, w.z, w.q, dinv, c1, c2, i == 1, x_final, s, clear_q, n_total); // :73,77,80-83
-  }
-  if (max_iter == 0 && x_zero)
-    launch_zero(n, x, s);
+    return PMG_OK;
+  }));
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }
-template int cheb_iterate<double>(const ChebWork<double>&, const ApplyFnT<double>&, const double*, int, double, int,
-                                  double*, const double*, int, bool, hipStream_t, bool*, const ApplyFnT<double>*, int,
-                                  bool, const ApplyFnT<double>*);
-template int cheb_iterate<float>(const ChebWork<float>&, const ApplyFnT<float>&, const float*, int, double, int, float*,
-                                 const float*, int, bool, hipStream_t, bool*, const ApplyFnT<float>*, int, bool,
-                                 const ApplyFnT<float>*);
+template int cheb_iterate<double>(const SmoothCall&, const SmoothData<double>&);
+template int cheb_iterate<float>(const SmoothCall&, const SmoothData<float>&);
 } // namespace pmg
 
 namespace
@@ -246,13 +167,12 @@ int alloc_vec(pmg_layout l, T** p)
   return PMG_OK;
 }
 
-// Does this smoother take the recomputed form where a call qualifies?  On request, or by default where the level's
-// vectors are streamed: there a pass costs its bytes and three passes less per smooth show in the cycle
+// Does this smoother's mode ask for the recomputed form?  On request, or by default where the level's vectors are
+// streamed: there a pass costs its bytes and three passes less per smooth show in the cycle
 // (profiles/chebyshev_recompute.md); a resident level's passes are cheap and the form would only add two vectors.
+// Which calls take it is the schedule's business (smooth_plan.hpp).
 bool wants_recompute(pmg_chebyshev sm)
 {
-  if (sm->max_iter != 2 && sm->max_iter != 3)
-    return false;
   return sm->recompute_mode >= 0 ? sm->recompute_mode == 1 : vector_streams(sm->layout->size_local);
 }
 
@@ -272,55 +192,66 @@ int recompute_buffers(pmg_chebyshev sm, hipStream_t s)
   return PMG_OK;
 }
 
-// src/chebyshev.hpp:46-91 on the operator `A` (see cheb_iterate)
-// track_ghosts / x_ghosts_current: the exchange bookkeeping of the V-cycle, see cheb_iterate (common.hpp)
-int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, int need_r,
-               bool x_zero, hipStream_t s, bool* split = nullptr, bool track_ghosts = false,
-               bool x_ghosts_current = false)
+// The call of smoother `sm`: the one place where a SmoothCall is read off the library's objects.  A = the matrix-free
+// operator it runs on, nullptr for a plain product (an assembled matrix, the float apply): single domain, no output
+// rule, no recomputed form.  track_ghosts / ghosts_current: the exchange bookkeeping of the V-cycle (local_correction).
+SmoothCall smoother_call(pmg_chebyshev sm, pmg_laplacian A, int need_r, bool x_zero, bool track_ghosts = false,
+                         bool ghosts_current = false)
+{
+  SmoothCall c;
+  c.k = sm->max_iter;
+  c.need_r = need_r;
+  c.x_zero = x_zero;
+  c.zeroed_output = A && laplacian_wants_zeroed_output(A);
+  c.ghosts = A && track_ghosts ? sm->layout->num_ghosts : 0;
+  c.ghosts_current = A && ghosts_current;
+  c.allow_recompute = A && wants_recompute(sm);
+  return c;
+}
+
+// src/chebyshev.hpp:46-91 on the operator `A`: the call as smoother_call made it
+int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, SmoothCall call, hipStream_t s)
 {
   pmg_layout l = sm->layout;
   PMG_REQUIRE(laplacian_layout(A) == l, "Chebyshev: operator and smoother layouts differ");
-  ChebWork<double> w{sm->r, sm->z, sm->q};
-  const bool zeroed = laplacian_wants_zeroed_output(A);
-  // the recomputed form, where the smoother's mode asks for it and this call qualifies (the test cheb_iterate makes)
-  bool recompute = wants_recompute(sm)
-                   && cheb_recompute_applies(sm->max_iter, need_r, split != nullptr, zeroed,
-                                             track_ghosts && l->total() > l->size_local, x_ghosts_current);
-  if (recompute)
-  {
+  if (call.allow_recompute && smooth_outcome(call).recomputed)
     PMG_TRY(recompute_buffers(sm, s));
-    recompute = sm->q1 && sm->q2;
-    w.q1 = sm->q1;
-    w.q2 = sm->q2;
-  }
+  call.allow_recompute = call.allow_recompute && sm->q1 && sm->q2;
   // eig_range[0] is unused (src/chebyshev.hpp:51); no per-call D2D copy of the diagonal (:53)
-  const ApplyFn apply = [A, s](double* in, double* out) { return laplacian_apply(A, in, out, s); };
-  const ApplyFn apply_zeroed = [A, s](double* in, double* out) { return laplacian_apply_zeroed(A, in, out, s); };
-  const ApplyFn apply_local = [A, s](double* in, double* out) { return laplacian_apply_ghosts_current(A, in, out, s); };
-  PMG_TRY(cheb_iterate(w, apply, laplacian_diag_inv(A), l->size_local, sm->eig_max, sm->max_iter, x, b, need_r, x_zero,
-                       s, split, zeroed ? &apply_zeroed : nullptr, l->total(), track_ghosts,
-                       x_ghosts_current ? &apply_local : nullptr));
-  if (recompute)
+  SmoothData<double> d;
+  d.w = {sm->r, sm->z, sm->q, sm->q1, sm->q2};
+  d.apply[SmoothStep::PLAIN] = [A, s](double* in, double* out) { return laplacian_apply(A, in, out, s); };
+  d.apply[SmoothStep::ZEROED_OUTPUT] = [A, s](double* in, double* out) { return laplacian_apply_zeroed(A, in, out, s); };
+  d.apply[SmoothStep::GHOSTS_CURRENT] = [A, s](double* in, double* out)
+  { return laplacian_apply_ghosts_current(A, in, out, s); };
+  d.dinv = laplacian_diag_inv(A);
+  d.n = l->size_local, d.n_total = l->total();
+  d.lmax = sm->eig_max;
+  d.x = x, d.b = b, d.s = s;
+  PMG_TRY(cheb_iterate(call, d));
+  if (smooth_outcome(call).recomputed)
     sm->recomputed++;
   return PMG_OK;
 }
 
 // the same smoother on the assembled operator `M`: its product, its own inverse diagonal (single domain: no ghosts);
 // *applies (optional) counts the products issued
-int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b, int need_r, bool x_zero,
-                      hipStream_t s, bool* split = nullptr, long long* applies = nullptr)
+int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b, const SmoothCall& call, hipStream_t s,
+                      long long* applies = nullptr)
 {
   pmg_layout l = sm->layout;
   PMG_REQUIRE(matrix_layout(M) == l, "Chebyshev: matrix and smoother layouts differ");
-  const ChebWork<double> w{sm->r, sm->z, sm->q};
-  const ApplyFn apply = [M, s, applies](double* in, double* out)
-  {
-    if (applies)
-      ++*applies;
-    return matrix_apply(M, in, out, s);
-  };
-  return cheb_iterate(w, apply, matrix_diag_inv(M), l->size_local, sm->eig_max, sm->max_iter, x, b, need_r, x_zero, s,
-                      split);
+  SmoothData<double> d;
+  d.w = {sm->r, sm->z, sm->q};
+  d.apply[SmoothStep::PLAIN] = [M, s](double* in, double* out) { return matrix_apply(M, in, out, s); };
+  d.dinv = matrix_diag_inv(M);
+  d.n = l->size_local, d.n_total = l->total();
+  d.lmax = sm->eig_max;
+  d.x = x, d.b = b, d.s = s;
+  PMG_TRY(cheb_iterate(call, d));
+  if (applies)
+    *applies += smooth_outcome(call).applications;
+  return PMG_OK;
 }
 
 // Does level i's pre-smooth hand its last application to the restriction (stiffness_restrict_kernel)?  The level has
@@ -340,15 +271,6 @@ bool fuses_restriction(pmg_multigrid mg, int i)
     return false;
   }
   return true;
-}
-
-// the smoother of level i on whichever form of the operator the level has (pmg_multigrid_set_level_matrix)
-int level_smooth(pmg_multigrid mg, int i, double* x, const double* b, int need_r, bool x_zero, hipStream_t s,
-                 bool* split = nullptr, bool track_ghosts = false, bool x_ghosts_current = false)
-{
-  if (mg->mats[i])
-    return cheb_solve_matrix(mg->smoothers[i], mg->mats[i], x, b, need_r, x_zero, s, split, &mg->mat_applies[i]);
-  return cheb_solve(mg->smoothers[i], mg->ops[i], x, b, need_r, x_zero, s, split, track_ghosts, x_ghosts_current);
 }
 
 // applications of level i's operator so far, in either form
@@ -436,18 +358,70 @@ int mg_prepare_f32(pmg_multigrid mg, hipStream_t s)
   return PMG_OK;
 }
 
-// the smoother of level i in FP32: cheb_iterate on the operator's float form (no ghosts: no exchange bookkeeping)
-int level_smooth_f32(pmg_multigrid mg, int i, int need_r, bool x_zero, hipStream_t s, bool* split)
+// The smooths of a cycle: before the restriction (levels > 0), in place of a coarse solver (level 0), behind the
+// prolongation (levels > 0).
+enum SmoothRole
+{
+  PreSmooth,
+  CoarseSmooth,
+  PostSmooth
+};
+bool has_coarse_solver(pmg_multigrid mg) { return mg->coarse_amg || mg->coarse || mg->coarse_fn; }
+bool cycle_smooths(pmg_multigrid mg, int i, SmoothRole role)
+{
+  return role == CoarseSmooth ? i == 0 && !(has_coarse_solver(mg) && mg->L > 1) : i > 0; // src/pmg.hpp:106-109
+}
+// The call of level i's smoother in that role, for a cycle whose finest iterate is zero on entry or not: what mg_apply
+// issues, and what mg_apply_graph asks before it captures.
+//   x_zero   u[i < L-1] = 0 (src/pmg.hpp:63-64) is folded into the smoothers' x_zero path; the FP32 cycle starts every
+//            level from zero (defect correction at the finest)
+//   need_r   the pre-smooth leaves the residual to the restriction in the form that restriction consumes
+//   ghosts   several ranks: the iterate leaves the pre-smooth with current ghosts and, with local_correction, still has
+//            them in front of the post-smooth, whose first application then runs without an exchange
+SmoothCall level_call(pmg_multigrid mg, int i, SmoothRole role, bool y_zero)
+{
+  pmg_chebyshev sm = mg->smoothers[i];
+  if (mg->precision == PMG_PRECISION_FP32) // the float apply: a plain product, single domain
+  {
+    SmoothCall c = smoother_call(sm, nullptr, role == PreSmooth ? ResidualSplit : ResidualNone, role != PostSmooth);
+    c.fp64 = false;
+    return c;
+  }
+  int need_r = ResidualNone;
+  if (role == PreSmooth)
+    need_r = fuses_restriction(mg, i)                          ? ResidualFused
+             : interp_restricts_difference(mg->interps[i - 1]) ? ResidualSplit
+                                                               : ResidualUpdated;
+  const bool x_zero = role != PostSmooth && (i == mg->L - 1 ? y_zero : true);
+  const bool local = local_correction(mg, i);
+  return smoother_call(sm, mg->mats[i] ? nullptr : mg->ops[i], need_r, x_zero, local && role == PreSmooth,
+                       local && role == PostSmooth);
+}
+
+// the smoother of level i on whichever form of the operator the level has (pmg_multigrid_set_level_matrix)
+int level_smooth(pmg_multigrid mg, int i, double* x, const double* b, const SmoothCall& call, hipStream_t s)
+{
+  if (mg->mats[i])
+    return cheb_solve_matrix(mg->smoothers[i], mg->mats[i], x, b, call, s, &mg->mat_applies[i]);
+  return cheb_solve(mg->smoothers[i], mg->ops[i], x, b, call, s);
+}
+
+// the smoother of level i in FP32: the same steps on the operator's float form
+int level_smooth_f32(pmg_multigrid mg, int i, const SmoothCall& call, hipStream_t s)
 {
   pmg_laplacian op = mg->ops[i];
-  const ApplyFnT<float> apply = [op, s](float* in, float* out) { return laplacian_apply_f32(op, in, out, s); };
-  return cheb_iterate(mg->w32[i], apply, mg->dinv32[i], mg->layouts[i]->size_local, mg->smoothers[i]->eig_max,
-                      mg->smoothers[i]->max_iter, mg->u32[i], mg->b32[i], need_r, x_zero, s, split);
+  SmoothData<float> d;
+  d.w = mg->w32[i];
+  d.apply[SmoothStep::PLAIN] = [op, s](float* in, float* out) { return laplacian_apply_f32(op, in, out, s); };
+  d.dinv = mg->dinv32[i];
+  d.n = mg->layouts[i]->size_local, d.n_total = mg->layouts[i]->total();
+  d.lmax = mg->smoothers[i]->eig_max;
+  d.x = mg->u32[i], d.b = mg->b32[i], d.s = s;
+  return cheb_iterate(call, d);
 }
 
 // u[0] = the coarse solver's answer to b[0], in FP64 (src/pmg.hpp:106-107): the library's own AMG (amg.hip), or,
 // KSP-style from a zero initial guess, the library's CG or the caller's callback
-bool has_coarse_solver(pmg_multigrid mg) { return mg->coarse_amg || mg->coarse || mg->coarse_fn; }
 int coarse_solve(pmg_multigrid mg, hipStream_t s)
 {
   if (mg->coarse_amg)
@@ -490,12 +464,13 @@ int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hi
   }
   for (int i = L - 1; i > 0; --i)
   {
-    bool split = false;
+    const SmoothCall pre = level_call(mg, i, PreSmooth, y_zero);
     {
       Range rg("pmg:pre_smooth");
-      PMG_TRY(level_smooth_f32(mg, i, ResidualSplit, true, s, &split));
+      PMG_TRY(level_smooth_f32(mg, i, pre, s));
     }
     Range rg("pmg:restrict");
+    const bool split = smooth_outcome(pre).left_to_consumer == SmoothOutcome::LeftSplit;
     PMG_TRY(restrict_f32(mg->interps[i - 1], mg->M1_32[i - 1], mg->w32[i].r, split ? mg->w32[i].q : nullptr,
                          mg->b32[i - 1], s));
   }
@@ -504,14 +479,14 @@ int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hi
     launch_mask_bc(n0, mg->b32[0], mg->bc0, s);
   {
     Range rg("pmg:coarse_solve");
-    if (has_coarse_solver(mg) && L > 1) // FP64 on the existing objects
+    if (!cycle_smooths(mg, 0, CoarseSmooth)) // FP64 on the existing objects
     {
       launch_from_f32(n0, mg->b32[0], mg->b[0], false, s);
       PMG_TRY(coarse_solve(mg, s));
       launch_to_f32(n0, mg->u[0], nullptr, mg->u32[0], s);
     }
     else
-      PMG_TRY(level_smooth_f32(mg, 0, ResidualNone, true, s, nullptr));
+      PMG_TRY(level_smooth_f32(mg, 0, level_call(mg, 0, CoarseSmooth, y_zero), s));
   }
   for (int i = 0; i < L - 1; ++i)
   {
@@ -520,7 +495,7 @@ int mg_apply_f32(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hi
       PMG_TRY(prolong_add_f32(mg->interps[i], mg->M1_32[i], mg->u32[i], mg->u32[i + 1], s));
     }
     Range rg("pmg:post_smooth");
-    PMG_TRY(level_smooth_f32(mg, i + 1, ResidualNone, false, s, nullptr));
+    PMG_TRY(level_smooth_f32(mg, i + 1, level_call(mg, i + 1, PostSmooth, y_zero), s));
   }
   launch_from_f32(nf, mg->u32[L - 1], y, !y_zero, s);
   for (int i = 0; i < L; ++i)
@@ -541,49 +516,43 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
   std::vector<long long> before(L);
   for (int i = 0; i < L; ++i)
     before[i] = level_applies(mg, i);
-  // u[L-1] = y, b[L-1] = rhs (:65,68) -- used in place; u[i<L-1] = 0 (:63-64) is
-  // folded into the smoothers' x_zero path.
+  // u[L-1] = y, b[L-1] = rhs (:65,68) -- used in place; every smooth's call comes from level_call
   Range cycle("pmg:vcycle");
   mg->u[L - 1] = y;
   mg->fused_count = 0;
   for (int i = L - 1; i > 0; --i)
   {
     const double* bi = (i == L - 1) ? rhs : mg->b[i];
-    const bool zero = (i == L - 1) ? y_zero : true;
-    const bool fuse = fuses_restriction(mg, i);
-    bool split = false;
+    const SmoothCall pre = level_call(mg, i, PreSmooth, y_zero);
     {
       Range rg("pmg:pre_smooth");
-      // (several ranks: the iterate leaves the pre-smooth with current ghosts, see `local_correction` below)
-      PMG_TRY(level_smooth(mg, i, mg->u[i], bi,
-                           fuse                                              ? ResidualFused
-                           : interp_restricts_difference(mg->interps[i - 1]) ? ResidualSplit
-                                                                             : ResidualUpdated,
-                           zero, s, &split, local_correction(mg, i))); // :83-87
+      PMG_TRY(level_smooth(mg, i, mg->u[i], bi, pre, s)); // :83-87
     }
     Range rg("pmg:restrict");
-    if (split && fuse) // the smoother's last application and the restriction of r - A z in one kernel
+    switch (smooth_outcome(pre).left_to_consumer)
     {
+    case SmoothOutcome::LeftFused: // the smoother's last application and the restriction of r - A z in one kernel
       PMG_TRY(interp_restrict_residual(mg->interps[i - 1], mg->ops[i], mg->smoothers[i]->z, mg->smoothers[i]->r,
                                        mg->b[i - 1], s));
       mg->fused_count++;
-    }
-    else if (split) // the residual r - q is formed by the restriction's gather
+      break;
+    case SmoothOutcome::LeftSplit: // the residual r - q is formed by the restriction's gather
       PMG_TRY(interp_restrict_difference(mg->interps[i - 1], mg->smoothers[i]->r, mg->smoothers[i]->q,
                                          mg->b[i - 1], s));
-    else
+      break;
+    case SmoothOutcome::LeftNone:
       PMG_TRY(interp_restrict(mg->interps[i - 1], mg->smoothers[i]->r, mg->b[i - 1], s)); // :92
+    }
   }
   if (L > 1)
     launch_mask_bc(mg->layouts[0]->size_local, mg->b[0], mg->bc0, s); // :100-103
   {
     Range rg("pmg:coarse_solve");
     const double* b0 = (L == 1) ? rhs : mg->b[0];
-    const bool zero = (L == 1) ? y_zero : true;
-    if (has_coarse_solver(mg) && L > 1) // :106-107
+    if (!cycle_smooths(mg, 0, CoarseSmooth)) // :106-107
       PMG_TRY(coarse_solve(mg, s));
     else
-      PMG_TRY(level_smooth(mg, 0, mg->u[0], b0, ResidualNone, zero, s)); // :109
+      PMG_TRY(level_smooth(mg, 0, mg->u[0], b0, level_call(mg, 0, CoarseSmooth, y_zero), s)); // :109
   }
   for (int i = 0; i < L - 1; ++i)
   {
@@ -600,9 +569,7 @@ int mg_apply(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, hipStr
     }
     Range rg("pmg:post_smooth");
     const double* bi = (i + 1 == L - 1) ? rhs : mg->b[i + 1];
-    // with local_correction the ghosts of u are current here: the post-smooth's first application needs no exchange
-    PMG_TRY(level_smooth(mg, i + 1, mg->u[i + 1], bi, ResidualNone, false, s, nullptr, false,
-                         local_correction(mg, i + 1))); // :138
+    PMG_TRY(level_smooth(mg, i + 1, mg->u[i + 1], bi, level_call(mg, i + 1, PostSmooth, y_zero), s)); // :138
   }
   for (int i = 0; i < L; ++i)
     mg->counts[i] = (int)(level_applies(mg, i) - before[i]);
@@ -667,14 +634,14 @@ extern "C" int pmg_chebyshev_solve(pmg_chebyshev sm, pmg_laplacian A, double* x,
                                    pmg_stream stream)
 {
   PMG_REQUIRE(sm && A && x && b, "pmg_chebyshev_solve: NULL argument");
-  return cheb_solve(sm, A, x, b, ResidualNone, false, S(stream));
+  return cheb_solve(sm, A, x, b, smoother_call(sm, A, ResidualNone, false), S(stream));
 }
 
 extern "C" int pmg_chebyshev_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b,
                                           pmg_stream stream)
 {
   PMG_REQUIRE(sm && M && x && b, "pmg_chebyshev_solve_matrix: NULL argument");
-  return cheb_solve_matrix(sm, M, x, b, ResidualNone, false, S(stream));
+  return cheb_solve_matrix(sm, M, x, b, smoother_call(sm, nullptr, ResidualNone, false), S(stream));
 }
 
 // -------------------------------------------------------------------- CG --
@@ -1155,11 +1122,11 @@ int mg_apply_graph(pmg_multigrid mg, const double* rhs, double* y, bool y_zero, 
     }
   if (mg->precision == PMG_PRECISION_FP32) // allocations and conversions on the caller's stream, outside the capture
     PMG_TRY(mg_prepare_f32(mg, s));
-  else // ... and so are the product vectors of the smoothers that take the recomputed form in this cycle
+  else // ... and so are the product vectors of the smoothers of which a call of this cycle takes the recomputed form
     for (int i = 0; i < mg->L; ++i)
-      if (!mg->mats[i] && wants_recompute(mg->smoothers[i]) && !laplacian_wants_zeroed_output(mg->ops[i])
-          && !local_correction(mg, i))
-        PMG_TRY(recompute_buffers(mg->smoothers[i], s));
+      for (SmoothRole role : {PreSmooth, CoarseSmooth, PostSmooth})
+        if (cycle_smooths(mg, i, role) && smooth_outcome(level_call(mg, i, role, y_zero)).recomputed)
+          PMG_TRY(recompute_buffers(mg->smoothers[i], s));
   std::vector<long long> recomputed_before(mg->L);
   for (int i = 0; i < mg->L; ++i)
     recomputed_before[i] = mg->smoothers[i]->recomputed;
