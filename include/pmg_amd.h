@@ -286,7 +286,14 @@ int pmg_vec_norm(pmg_layout l, const double* a, int norm_type, double* result, p
  * tied to the cell, not to its position in the launched list -- SURVEY.md quirks
  * Q1, Q2) and groups the cells into coloured patches (its own copy of the
  * dofmap in patch form); it reads dofmap, bc_marker, xgeom and geom_dofmap back
- * to the host once for that.  Degrees 1..PMG_MAX_DEGREE are supported (the
+ * to the host once for that.
+ * Cell orientation is free: the local axes of a cell (the i, j, l of geom_dofmap, the a, b, c of dofmap -- the same
+ * three axes in both) may run along any of the cell's edge directions, either way, in any order, and differently from
+ * cell to cell, as in an imported mesh; a left-handed cell (det J < 0) is as good as a right-handed one.  Every
+ * volume measure is |det J| (the reference's assembled path, src/precompute.hpp:96,230; its matrix-free kernel takes
+ * the signed value): "detJ" below -- in G, in the load vector and in the reaction vector -- stands for |det J_q|.
+ * adj(J) keeps its sign: it enters G twice and the facet measure through a norm.  For a right-handed cell nothing
+ * changes, bit for bit.  A cell whose determinant changes sign inside the cell is not a valid cell.  Degrees 1..PMG_MAX_DEGREE are supported (the
  * reference stops at 5, :335-346). */
 int pmg_laplacian_create(pmg_laplacian* out, pmg_layout layout, int degree, int32_t ncells,
                          const double* kappa, const int32_t* dofmap, const double* xgeom,
@@ -365,7 +372,7 @@ int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream strea
 int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const double* kq, pmg_stream stream);
 int pmg_laplacian_has_coefficient_field(pmg_laplacian op);
 /* Full-tensor diffusion: -div(K grad u) with K symmetric positive definite and constant per cell (not in the
- * reference).  The stored tensor G_q = adj(J) adj(J)^T w_q / detJ enters the form linearly, and with a tensor K_c it
+ * reference).  The stored tensor G_q = adj(J) adj(J)^T w_q / detJ (detJ = |det J_q|) enters the form linearly, and with a tensor K_c it
  * becomes G_q = adj(J) K_c adj(J)^T w_q / detJ: still six symmetric entries per point, so every form of the apply
  * streams the same bytes as without one, and the diagonal, the assembled matrix (pmg_matrix_*) and the AMG set-up read
  * that one tensor.  The effective coefficient is kappa[cell] * kq[dof(cell, q)] * K[cell]: the per-cell array and the
@@ -396,7 +403,7 @@ int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op);
  * step of the heat equation (M / dt + K), a screened Poisson problem, a Robin-type penalty.  With GLL collocation the
  * quadrature points are the nodes, so the mass matrix is diagonal and the term is one vector over the dofs,
  *   d[dof] = sum over the listed cells c that hold the dof, at the cell's point q on it, of sigma[c] * w_q * detJ_q
- * (the weights of pmg_laplacian_assemble_rhs with sigma in place of kappa and f = 1; 0 on marked dofs).  The operator
+ * (detJ_q = |det J_q|; the weights of pmg_laplacian_assemble_rhs with sigma in place of kappa and f = 1; 0 on marked dofs).  The operator
  * becomes y = A x + d .* x on unmarked rows; Dirichlet rows stay y = x.  d does not depend on the stored tensor, so
  * the call combines freely with kappa, the nodal field, the coefficient tensor, both geometry modes and batched
  * geometry.  No apply form takes a further pass over the vectors: in the FP64 and FP32 patch kernels the first patch
@@ -429,7 +436,7 @@ int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op);
  * leaves the vector equal to that component, and "d" above reads d_sigma + d_R. */
 int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma, pmg_stream stream);
 int pmg_laplacian_has_reaction(pmg_laplacian op);
-/* GLL-collocated load vector b_i = sum_cells kappa * w_q * detJ_q * f_i at q = i
+/* GLL-collocated load vector b_i = sum_cells kappa * w_q * detJ_q * f_i at q = i, detJ_q = |det J_q|
  * (what dolfinx assemble_vector does for L = inner(f, v)*dx with the GLL rule,
  * examples/pmg/poisson.py:40; examples/pmg/main.cpp:289-295), then set_bc:
  * b[bc] = 0.  `f` holds the nodal values of the source term.  The scaling is by the per-cell kappa only (the

@@ -101,7 +101,8 @@ void orc_geometry(int ncells, int nq, const double* xgeom, const int32_t* geom_d
               -J[0][0] * J[1][2] + J[0][2] * J[1][0]},
              {J[1][0] * J[2][1] - J[1][1] * J[2][0], -J[0][0] * J[2][1] + J[0][1] * J[2][0],
               J[0][0] * J[1][1] - J[0][1] * J[1][0]}};
-      double detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
+      /* |det J|: a left-handed local frame (a reflected vertex order) does not change the measure */
+      double detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]);
       double s = w[q] / detJ;
       double* g = G + ((size_t)c * nq + q) * 6;
       g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;

@@ -249,7 +249,9 @@ def geometry_G(xgeom, geom_dofmap, dphi_geom, weights, cells=None):
     K[..., 2, 0] = J[..., 1, 0] * J[..., 2, 1] - J[..., 1, 1] * J[..., 2, 0]
     K[..., 2, 1] = -J[..., 0, 0] * J[..., 2, 1] + J[..., 0, 1] * J[..., 2, 0]
     K[..., 2, 2] = J[..., 0, 0] * J[..., 1, 1] - J[..., 0, 1] * J[..., 1, 0]
-    detJ = J[..., 0, 0] * K[..., 0, 0] + J[..., 0, 1] * K[..., 1, 0] + J[..., 0, 2] * K[..., 2, 0]
+    # |det J|, as the reference's assembled path (src/precompute.hpp:96,230): a cell whose local frame is left-handed
+    # (a reflected vertex order) has the same measure, G and load as in any other frame
+    detJ = np.abs(J[..., 0, 0] * K[..., 0, 0] + J[..., 0, 1] * K[..., 1, 0] + J[..., 0, 2] * K[..., 2, 0])
     KKt = np.einsum("cqik,cqjk->cqij", K, K)
     s = weights[None, :] / detJ
     G = np.stack(

@@ -126,7 +126,7 @@ __global__ void affine_geometry_kernel(long long nslots, const int32_t* __restri
     K[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
     K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
     K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    const double detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
+    const double detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]); // as jacobian(): |det J|
     const double s = 1.0 / detJ;
     if (ktensor)
     {

@@ -175,7 +175,7 @@ int walk_launches(pmg_laplacian op, int l0, int l1, ApplyForm form, hipStream_t 
   return PMG_OK;
 }
 
-// ---- geometry: J, adj(J), det at one quadrature point (src/laplacian.hpp:72-97) ----
+// ---- geometry: J, adj(J), |det| at one quadrature point (src/laplacian.hpp:72-97) ----
 __device__ inline void jacobian(const double* __restrict__ xgeom,
                                 const int32_t* __restrict__ gdofs, const double* __restrict__ dphi,
                                 int nq, int q, double K[3][3], double& detJ)
@@ -207,8 +207,10 @@ __device__ inline void jacobian(const double* __restrict__ xgeom,
   K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
   K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
   // full cofactor expansion along the first row (the reference's :97 drops to
-  // the diagonal-J special case)
-  detJ = J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0];
+  // the diagonal-J special case).  |det J|: a cell's local frame may be left-handed (vertex order of an imported
+  // mesh); the volume measure, G, the load and the reaction weights do not depend on it.  K keeps its sign: it enters
+  // G twice and the facet measure through a norm.  (fabs changes no bit of a positive determinant.)
+  detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]);
 }
 
 // ---- the six entries of adj(J) T adj(J)^T * s for a symmetric T = (xx, xy, xz, yy, yz, zz) in physical coordinates:

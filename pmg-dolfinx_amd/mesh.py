@@ -105,6 +105,42 @@ def facet_nodes(P: int, local_facet: int) -> np.ndarray:
     return ((a * nd + b) * nd + c).ravel().astype(np.int32)
 
 
+def cell_symmetries():
+    """The 48 symmetries of the reference cube as ``(perm, flips, sign)``: the local frames a hexahedral cell of an
+    imported mesh can come in.  New local axis ``m`` runs along old axis ``perm[m]``, reversed if ``flips[m]``;
+    ``sign = sgn(perm) * (-1)^sum(flips)`` is the sign det J takes (-1: a left-handed cell).
+
+    Order (fixed): index ``s = 8 * p + 4 * flips[0] + 2 * flips[1] + flips[2]`` with ``p`` the position of ``perm`` in
+    the lexicographic list (0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0).  Index 0 is the identity."""
+    from itertools import permutations
+
+    out = []
+    for perm in permutations((0, 1, 2)):
+        inversions = sum(perm[i] > perm[j] for i in range(3) for j in range(i + 1, 3))
+        for f in range(8):
+            flips = ((f >> 2) & 1, (f >> 1) & 1, f & 1)
+            out.append((perm, flips, (-1) ** (inversions + sum(flips))))
+    return out
+
+
+def frame_node_map(P: int, perm, flips) -> np.ndarray:
+    """int32 ``[nd^3]``: the old-frame node of every new-frame node ``t' = (i0*nd + i1)*nd + i2`` of a cell re-framed
+    by ``(perm, flips)`` -- the node whose index along old axis ``perm[m]`` is ``P - i_m`` if ``flips[m]``, else
+    ``i_m`` (the GLL nodes are symmetric about the midpoint, so nodes map to nodes).  ``P = 1``: the vertex map."""
+    nd = P + 1
+    idx = np.meshgrid(*([np.arange(nd)] * 3), indexing="ij")
+    old = [None] * 3
+    for m in range(3):
+        old[perm[m]] = (P - idx[m]) if flips[m] else idx[m]
+    return ((old[0] * nd + old[1]) * nd + old[2]).ravel().astype(np.int32)
+
+
+def frame_facet_map(perm, flips) -> np.ndarray:
+    """int32 ``[6]``: the old local facet ``2 * perm[m] + (side ^ flips[m])`` of every new local facet
+    ``2 * m + side``."""
+    return np.array([2 * perm[m] + (side ^ flips[m]) for m in range(3) for side in range(2)], dtype=np.int32)
+
+
 @dataclass
 class LevelData:
     """Everything one p-level needs on one rank (host arrays)."""
@@ -131,9 +167,17 @@ class LevelData:
 
 
 class BoxPartition:
-    """One rank's share of an n_x x n_y x n_z hex mesh of the box [lo, hi]."""
+    """One rank's share of an n_x x n_y x n_z hex mesh of the box [lo, hi].
 
-    def __init__(self, n, proc_dims=(1, 1, 1), rank=0, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), warp=None):
+    ``cell_frames`` (optional): an int array of shape ``n`` (the GLOBAL cell grid, so every rank gives a shared or
+    ghost cell the same frame) with values 0..47, the index into ``cell_symmetries()`` of each cell's local frame.
+    The rows of ``geom_dofmap`` and of every level's ``dofmap`` are then listed in that frame (``frame_node_map``) and
+    ``exterior_facets()`` reports that frame's facet numbers -- what an imported mesh looks like, left-handed cells
+    included.  The mesh, the dof numbering, ownership, halo lists, cell lists and markers are those of the default
+    (frame 0 everywhere: local axes = global axes)."""
+
+    def __init__(self, n, proc_dims=(1, 1, 1), rank=0, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), warp=None,
+                 cell_frames=None):
         if np.isscalar(n):
             n = (int(n),) * 3
         self.n = tuple(int(v) for v in n)
@@ -177,8 +221,22 @@ class BoxPartition:
             for j in range(2):
                 for k in range(2):
                     gd[:, i * 4 + j * 2 + k] = ((lc[:, 0] + i) * vshape[1] + (lc[:, 1] + j)) * vshape[2] + lc[:, 2] + k
+        # local frames: one symmetry index per local cell, looked up by global cell coordinates
+        self.cell_frames = None
+        if cell_frames is not None:
+            fr = np.asarray(cell_frames)
+            if fr.shape != self.n or not np.issubdtype(fr.dtype, np.integer) or fr.min() < 0 or fr.max() > 47:
+                raise ValueError("cell_frames: an integer array of shape n with values 0..47")
+            cc = self.cell_coords
+            self.cell_frames = fr[cc[:, 0], cc[:, 1], cc[:, 2]].astype(np.int64)
+            gd = self._reframe(gd, 1)
         self.geom_dofmap = gd
         self._levels = {}
+
+    def _reframe(self, rows, P):
+        """Rows [ncells, (P+1)^3] of cell-local node data, listed in every cell's own frame."""
+        table = np.stack([frame_node_map(P, perm, flips) for perm, flips, _ in cell_symmetries()])
+        return np.ascontiguousarray(np.take_along_axis(rows, table[self.cell_frames].astype(np.int64), axis=1))
 
     # ---- brick geometry (cells) ----
     def _own_cells(self, coords):
@@ -273,6 +331,8 @@ class BoxPartition:
         mark = ghost_cell | touches_ghost  # src/mesh.hpp:119-128
         lcells = np.nonzero(~mark)[0].astype(np.int32)
         bcells = np.nonzero(mark)[0].astype(np.int32)
+        if self.cell_frames is not None:  # (after the cell lists: they depend on a row's set of dofs only)
+            dofmap = self._reframe(dofmap, P)
 
         lv = LevelData(
             P=P,
@@ -295,7 +355,8 @@ class BoxPartition:
 
     def exterior_facets(self):
         """(cells int32, local_facets int8) of every face of a local cell -- ghost cells included -- that lies on the
-        boundary of the whole box; local facet = 2 * axis + side (``facet_nodes``).  Ordered by cell, then facet."""
+        boundary of the whole box; local facet = 2 * axis + side (``facet_nodes``) in the cell's own frame
+        (``cell_frames``).  Ordered by cell, then facet."""
         cc = self.cell_coords
         cells, facets = [], []
         for axis in range(3):
@@ -304,6 +365,9 @@ class BoxPartition:
                 cells.append(on)
                 facets.append(np.full(on.size, 2 * axis + side))
         cells, facets = np.concatenate(cells), np.concatenate(facets)
+        if self.cell_frames is not None:  # global-frame facet -> the cell's own number of it
+            new_of_old = np.stack([np.argsort(frame_facet_map(perm, flips)) for perm, flips, _ in cell_symmetries()])
+            facets = new_of_old[self.cell_frames[cells], facets]
         order = np.lexsort((facets, cells))
         return cells[order].astype(np.int32), facets[order].astype(np.int8)
 

@@ -26,7 +26,7 @@ class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
                  node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None,
-                 kappa_tensor=None, reaction=None, robin=None):
+                 kappa_tensor=None, reaction=None, robin=None, cell_frames=None):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
@@ -53,14 +53,17 @@ class PoissonHierarchy:
         ``dirichlet`` (optional): a callable mapping dof coordinates ``[n, 3]`` to a boolean array; on every level
         the Dirichlet marker becomes the exterior dofs for which it is true (default: the whole boundary).  The rest
         of the boundary is natural; non-zero data enter through ``MatFreeLaplacian.apply_lifting`` / ``set_bc`` /
-        ``assemble_neumann`` on the caller's right-hand side."""
+        ``assemble_neumann`` on the caller's right-hand side.
+
+        ``cell_frames`` (optional): every cell's local frame, an int array over the global cell grid
+        (``BoxPartition``); the problem and its solution do not depend on it."""
         import torch
 
         self.orders = tuple(int(p) for p in orders)
         if list(self.orders) != sorted(set(self.orders)):
             raise ValueError("orders must be strictly ascending (coarse -> fine)")
         dims = tuple(proc_dims) if proc_dims is not None else default_proc_dims(size)
-        self.part = BoxPartition(n, dims, rank, warp=warp)
+        self.part = BoxPartition(n, dims, rank, warp=warp, cell_frames=cell_frames)
         part = self.part
         self.levels, self.layouts, self.operators, self.smoothers, self.eig_ranges = [], [], [], [], []
         self.rhs = []

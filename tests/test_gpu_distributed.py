@@ -87,16 +87,17 @@ def _reporting(fn):
     return wrapped
 
 
-def _rank_checks(pm, rank, world, n, dims, orders, comm=None):
+def _rank_checks(pm, rank, world, n, dims, orders, comm=None, cell_frames=None):
     """What every rank checks against the single-domain oracle: operator apply on every level (with
-    stale ghosts on input), distributed reductions, eigenvalue estimates, two V-cycles."""
+    stale ghosts on input), distributed reductions, eigenvalue estimates, two V-cycles.  ``cell_frames`` (optional,
+    tests/test_gpu_cell_frames.py): the local frame of every cell of the global grid; the oracle stays frame-free."""
     import torch
 
     from oracle import pmg_oracle as po
 
     k = 3
     H = pm.PoissonHierarchy(n, orders, kappa=2.0, cheb_its=k, proc_dims=dims, rank=rank, size=world, warp=warp,
-                            comm=comm)
+                            comm=comm, cell_frames=cell_frames)
     out = {"eig": H.eig_ranges, "ghosts": [lv.num_ghosts for lv in H.levels],
            "neighbors": [len(lv.neighbors) for lv in H.levels]}
     # operator apply on every level against the global oracle
@@ -246,7 +247,7 @@ def _assert_rank_results(res):
     assert all(out["dis_levels"][1:] == res[0]["dis_levels"][1:] for out in res)
 
 
-def _worker_body(rank, world, port, n, dims, orders, halo="exchange"):
+def _worker_body(rank, world, port, n, dims, orders, halo="exchange", cell_frames=None):
     import torch
     import torch.distributed as dist
 
@@ -265,7 +266,7 @@ def _worker_body(rank, world, port, n, dims, orders, halo="exchange"):
         comm = {"windows": lambda: pm.TorchComm(halo="windows"),       # halo windows, reductions on the gloo callbacks
                 "window-comm": lambda: pm.WindowComm.from_torch(),     # halo AND reductions through windows
                 "exchange": lambda: None}[halo]()
-        out = _rank_checks(pm, rank, world, n, dims, orders, comm=comm)
+        out = _rank_checks(pm, rank, world, n, dims, orders, comm=comm, cell_frames=cell_frames)
         if halo == "window-comm":
             # collectives longer than one exchange of the window (16 384 doubles per rank): chunked all-reduce and gather
             import ctypes as C
