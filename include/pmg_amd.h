@@ -293,8 +293,18 @@ int pmg_vec_norm(pmg_layout l, const double* a, int norm_type, double* result, p
  * volume measure is |det J| (the reference's assembled path, src/precompute.hpp:96,230; its matrix-free kernel takes
  * the signed value): "detJ" below -- in G, in the load vector and in the reaction vector -- stands for |det J_q|.
  * adj(J) keeps its sign: it enters G twice and the facet measure through a norm.  For a right-handed cell nothing
- * changes, bit for bit.  A cell whose determinant changes sign inside the cell is not a valid cell.  Degrees 1..PMG_MAX_DEGREE are supported (the
- * reference stops at 5, :335-346). */
+ * changes, bit for bit.  A cell whose determinant changes sign inside the cell is not a valid cell.
+ * What the library requires of a mesh: hexahedra with trilinear geometry, and a CONFORMING dofmap -- two cells hold the
+ * same dof exactly where they share the vertex, edge or face that carries it.  Nothing about structure or valence: an
+ * edge may be shared by any number of cells (3 and 5 are tested), a vertex likewise (3 to 10), blocks may meet with
+ * local axes that do not line up, the domain may have re-entrant corners and cavities, a partition interface need not
+ * be a plane.  The patches are formed from cell centroids and dof sets alone; a group of cells with more distinct dofs
+ * than a patch holds is halved until it fits.  The optional forms are taken only where the mesh allows them and are
+ * refused before anything is launched otherwise: the two-stream split (PMG_APPLY_STREAMS) needs patch colours that
+ * separate the two halves, the chain form (PMG_CHAIN) a tensor grid of patches; a mesh that has neither runs the
+ * plain patch form.  The one hard limit: a patch colouring of more than 64 colours is refused with PMG_ERR_INVALID by
+ * the constructor (no mesh of the suite needs more than 16).
+ * Degrees 1..PMG_MAX_DEGREE are supported (the reference stops at 5, :335-346). */
 int pmg_laplacian_create(pmg_laplacian* out, pmg_layout layout, int degree, int32_t ncells,
                          const double* kappa, const int32_t* dofmap, const double* xgeom,
                          int32_t npoints, const int32_t* geom_dofmap, const int32_t* lcells,

@@ -665,8 +665,10 @@ class MultigridPreconditioner:
 # --------------------------------------------------------------------------
 
 
-def build_hierarchy(n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, warp=None):
-    mesh = BoxMesh(n, warp=warp)
+def build_hierarchy(n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, warp=None, mesh=None):
+    """``mesh`` (optional): any object with ``BoxMesh``'s members, used instead of the box of ``n`` cells."""
+    if mesh is None:
+        mesh = BoxMesh(n, warp=warp)
     ops, smoothers, eigs = [], [], []
     for P in orders:
         A = Laplacian(P, kappa, mesh.dofmap(P), mesh.xgeom, mesh.geom_dofmap, mesh.boundary_marker(P))

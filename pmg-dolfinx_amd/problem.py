@@ -26,7 +26,7 @@ class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
                  node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None,
-                 kappa_tensor=None, reaction=None, robin=None, cell_frames=None):
+                 kappa_tensor=None, reaction=None, robin=None, cell_frames=None, part=None):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
@@ -56,14 +56,19 @@ class PoissonHierarchy:
         ``assemble_neumann`` on the caller's right-hand side.
 
         ``cell_frames`` (optional): every cell's local frame, an int array over the global cell grid
-        (``BoxPartition``); the problem and its solution do not depend on it."""
+        (``BoxPartition``); the problem and its solution do not depend on it.
+
+        ``part`` (optional): this rank's share of any conforming hexahedral mesh, an object with ``BoxPartition``'s
+        members (``xgeom``, ``geom_dofmap``, ``ncells``, ``level(P)``, ``dof_coordinates(P)``, ``exterior_facets()``,
+        ``facet_point_coordinates(P, cells, facets)``), used instead of constructing one; ``n``, ``proc_dims``,
+        ``rank``, ``size``, ``warp`` and ``cell_frames`` are then ignored."""
         import torch
 
         self.orders = tuple(int(p) for p in orders)
         if list(self.orders) != sorted(set(self.orders)):
             raise ValueError("orders must be strictly ascending (coarse -> fine)")
         dims = tuple(proc_dims) if proc_dims is not None else default_proc_dims(size)
-        self.part = BoxPartition(n, dims, rank, warp=warp, cell_frames=cell_frames)
+        self.part = part if part is not None else BoxPartition(n, dims, rank, warp=warp, cell_frames=cell_frames)
         part = self.part
         self.levels, self.layouts, self.operators, self.smoothers, self.eig_ranges = [], [], [], [], []
         self.rhs = []

@@ -91,11 +91,13 @@ void cover(const char* f) { g_cov.insert(f); }
 struct Geo
 {
   int n[3] = {0, 0, 0};
-  std::vector<std::array<int, 3>> cc; // cell coordinates on the n[0] x n[1] x n[2] grid
+  std::vector<std::array<int, 3>> cc; // cell coordinates on the n[0] x n[1] x n[2] grid (empty on a multi-block mesh)
+  std::vector<std::array<int32_t, 8>> verts; // multi-block meshes: the cells' vertices, order i*4 + j*2 + k
+  int32_t nverts = 0;
   std::vector<float> cen;             // [ncells*3]
   std::vector<int32_t> lcells, bcells;
   bool expect_morton = false;
-  int32_t ncells() const { return (int32_t)cc.size(); }
+  int32_t ncells() const { return (int32_t)(verts.empty() ? cc.size() : verts.size()); }
 };
 struct Space
 {
@@ -245,6 +247,278 @@ void brick(int n, std::array<int, 3> dims, int rank, int P, Geo& g, Space& s)
       mark = lv.dofmap[(size_t)c * N + k] >= lv.size_local;
     (mark ? g.bcells : g.lcells).push_back(c);
   }
+}
+
+// ---- multi-block meshes ---------------------------------------------------------------------------------------------
+// Blocks of mx x my x mz cells each, given by the numbers of their eight corners (order i*4 + j*2 + k) in a list of
+// points; blocks that name the same corners meet there, with whatever local axes each of them has.  Everything is
+// identified topologically and exactly: a lattice point of a block, and a node of a cell, by its integer trilinear
+// weights on the corners it depends on -- the same point seen from two blocks or two cells has the same weights on the
+// same corners, whichever way their axes run.
+using WeightKey = std::vector<std::pair<int32_t, int32_t>>;
+WeightKey weight_key(const int32_t (&corner)[8], int n0, int i0, int n1, int i1, int n2, int i2)
+{
+  WeightKey key;
+  const int w0[2] = {n0 - i0, i0}, w1[2] = {n1 - i1, i1}, w2[2] = {n2 - i2, i2};
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b)
+      for (int e = 0; e < 2; ++e)
+        if (w0[a] * w1[b] * w2[e] != 0)
+          key.push_back({corner[a * 4 + b * 2 + e], w0[a] * w1[b] * w2[e]});
+  std::sort(key.begin(), key.end());
+  return key;
+}
+
+struct BlockMesh
+{
+  std::vector<std::array<int32_t, 8>> corner; // per block
+  std::vector<std::array<double, 3>> x;       // the points the corners name
+  int m[3] = {1, 1, 1};
+};
+enum Map
+{
+  MAP_NONE,
+  MAP_BEND, // x += 0.3 z y: every centroid gets an x of its own
+  MAP_TWIST
+};
+
+// lists: ALL_L / ALL_B / NONE as for a box; SLAB: the cells of block 0 are "boundary" cells (a partition between blocks)
+Geo block_geo(const BlockMesh& bm, Map map, Lists lists, bool shuffle = false, uint32_t seed = 1)
+{
+  Geo g;
+  g.expect_morton = true;
+  std::map<WeightKey, int32_t> vertex;
+  std::vector<int> block_of;
+  std::vector<std::array<double, 3>> centre;
+  for (size_t b = 0; b < bm.corner.size(); ++b)
+  {
+    int32_t cn[8];
+    std::copy(bm.corner[b].begin(), bm.corner[b].end(), cn);
+    for (int i = 0; i < bm.m[0]; ++i)
+      for (int j = 0; j < bm.m[1]; ++j)
+        for (int k = 0; k < bm.m[2]; ++k)
+        {
+          std::array<int32_t, 8> v;
+          for (int a = 0; a < 2; ++a)
+            for (int e = 0; e < 2; ++e)
+              for (int f = 0; f < 2; ++f)
+              {
+                const WeightKey key = weight_key(cn, bm.m[0], i + a, bm.m[1], j + e, bm.m[2], k + f);
+                v[a * 4 + e * 2 + f] = vertex.emplace(key, (int32_t)vertex.size()).first->second;
+              }
+          g.verts.push_back(v);
+          block_of.push_back((int)b);
+          const double t[3] = {(i + 0.5) / bm.m[0], (j + 0.5) / bm.m[1], (k + 0.5) / bm.m[2]};
+          std::array<double, 3> c = {0, 0, 0};
+          for (int a = 0; a < 2; ++a)
+            for (int e = 0; e < 2; ++e)
+              for (int f = 0; f < 2; ++f)
+                for (int d = 0; d < 3; ++d)
+                  c[d] += (a ? t[0] : 1 - t[0]) * (e ? t[1] : 1 - t[1]) * (f ? t[2] : 1 - t[2]) * bm.x[cn[a * 4 + e * 2 + f]][d];
+          if (map == MAP_BEND)
+            c[0] += 0.3 * c[2] * c[1];
+          if (map == MAP_TWIST)
+            c = {c[0] + 0.12 * c[1] * c[2], c[1] + 0.10 * c[0] * c[2], c[2] + 0.08 * c[0] * c[1]};
+          centre.push_back(c);
+        }
+  }
+  g.nverts = (int32_t)vertex.size();
+  std::vector<int32_t> order(g.verts.size());
+  std::iota(order.begin(), order.end(), 0);
+  std::mt19937 rng(seed * 7919u + 13u);
+  if (shuffle)
+    std::shuffle(order.begin(), order.end(), rng);
+  std::vector<std::array<int32_t, 8>> verts(order.size());
+  g.cen.resize(3 * order.size());
+  for (size_t c = 0; c < order.size(); ++c)
+  {
+    verts[c] = g.verts[order[c]];
+    for (int d = 0; d < 3; ++d)
+      g.cen[3 * c + d] = (float)centre[order[c]][d];
+    const bool boundary = lists == ALL_B || (lists == SLAB && block_of[order[c]] == 0);
+    if (lists != NONE)
+      (boundary ? g.bcells : g.lcells).push_back((int32_t)c);
+  }
+  g.verts.swap(verts);
+  if (shuffle)
+  {
+    std::shuffle(g.lcells.begin(), g.lcells.end(), rng);
+    std::shuffle(g.bcells.begin(), g.bcells.end(), rng);
+  }
+  return g;
+}
+
+// k rhombic sectors (0, a_s, a_s + a_{s+1}, a_{s+1}) around the z axis: an edge shared by k cells, vertices of valence 2k
+BlockMesh star_blocks(int k, int m, int nz)
+{
+  BlockMesh bm;
+  bm.m[0] = bm.m[1] = m, bm.m[2] = nz;
+  const double pi = 3.14159265358979323846;
+  // points: 2 on the axis, then per sector a_s and a_s + a_{s+1}, each at z = 0 and z = 1
+  bm.x.push_back({0, 0, 0});
+  bm.x.push_back({0, 0, 1});
+  for (int s = 0; s < k; ++s)
+    for (int far = 0; far < 2; ++far)
+      for (int z = 0; z < 2; ++z)
+      {
+        const double a0 = 2 * pi * s / k, a1 = 2 * pi * (s + 1) / k;
+        bm.x.push_back({std::cos(a0) + far * std::cos(a1), std::sin(a0) + far * std::sin(a1), (double)z});
+      }
+  auto ray = [&](int s, int far, int z) { return 2 + ((s % k) * 2 + far) * 2 + z; };
+  for (int s = 0; s < k; ++s)
+    bm.corner.push_back({0, 1, ray(s + 1, 0, 0), ray(s + 1, 0, 1), ray(s, 0, 0), ray(s, 0, 1), ray(s, 1, 0), ray(s, 1, 1)});
+  return bm;
+}
+
+// an inner cube and six frusta whose local axis 0 is radial; three of them are left-handed
+BlockMesh ogrid_blocks(int m)
+{
+  BlockMesh bm;
+  bm.m[0] = bm.m[1] = bm.m[2] = m;
+  for (int shell = 0; shell < 2; ++shell)
+    for (int v = 0; v < 8; ++v)
+    {
+      const double s = shell ? 1.0 : 0.4;
+      bm.x.push_back({(2 * ((v >> 2) & 1) - 1) * s, (2 * ((v >> 1) & 1) - 1) * s, (2 * (v & 1) - 1) * s});
+    }
+  bm.corner.push_back({0, 1, 2, 3, 4, 5, 6, 7});
+  for (int axis = 0; axis < 3; ++axis)
+    for (int side = 0; side < 2; ++side)
+    {
+      const int b = axis == 0 ? 1 : 0, c = axis == 2 ? 1 : 2;
+      std::array<int32_t, 8> cn;
+      for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
+          for (int e = 0; e < 2; ++e)
+          {
+            int bit[3];
+            bit[axis] = side, bit[b] = j, bit[c] = e;
+            cn[i * 4 + j * 2 + e] = 8 * i + bit[0] * 4 + bit[1] * 2 + bit[2];
+          }
+      bm.corner.push_back(cn);
+    }
+  return bm;
+}
+
+// a box grid with a re-entrant notch along one vertical edge and one interior cell removed: a tensor grid of centroids
+// with gaps, columns of cells that stop and resume
+Geo notched_geo(int nx, int ny, int nz, Lists lists, bool shuffle = false, uint32_t seed = 1)
+{
+  Geo g;
+  g.n[0] = nx, g.n[1] = ny, g.n[2] = nz;
+  for (int i = 0; i < nx; ++i)
+    for (int j = 0; j < ny; ++j)
+      for (int k = 0; k < nz; ++k)
+      {
+        const bool notch = i >= (nx + 1) / 2 && j >= (ny + 1) / 2 && k >= nz / 4 && k < nz / 2;
+        const bool hole = i == 1 && j == 1 && k == (3 * nz) / 4;
+        if (!notch && !hole)
+          g.cc.push_back({i, j, k});
+      }
+  std::mt19937 rng(seed * 7919u + 13u);
+  if (shuffle)
+    std::shuffle(g.cc.begin(), g.cc.end(), rng);
+  set_centroids(g, 0.0, false, seed);
+  for (int32_t c = 0; c < g.ncells(); ++c)
+  {
+    if (lists == ALL_L || (lists == SLAB && g.cc[c][0] > 0))
+      g.lcells.push_back(c);
+    else if (lists == ALL_B || lists == SLAB)
+      g.bcells.push_back(c);
+  }
+  return g;
+}
+
+// continuous space of degree P on a multi-block mesh; BC_SURFACE: the dofs of the faces that belong to one cell only
+Space mesh_space(const Geo& g, int P, Bc bcmode, uint32_t perm_seed = 0)
+{
+  Space s;
+  s.P = P;
+  const int nd = P + 1, N = nd * nd * nd;
+  std::map<WeightKey, int32_t> dof;
+  s.dofmap.resize((size_t)g.ncells() * N);
+  for (int32_t c = 0; c < g.ncells(); ++c)
+  {
+    int32_t v[8];
+    std::copy(g.verts[c].begin(), g.verts[c].end(), v);
+    for (int a = 0; a < nd; ++a)
+      for (int b = 0; b < nd; ++b)
+        for (int e = 0; e < nd; ++e)
+          s.dofmap[(size_t)c * N + (a * nd + b) * nd + e]
+              = dof.emplace(weight_key(v, P, a, P, b, P, e), (int32_t)dof.size()).first->second;
+  }
+  s.ndofs = (int32_t)dof.size();
+  // the count by topology: V + E (P-1) + F (P-1)^2 + C (P-1)^3
+  std::set<std::array<int32_t, 2>> edges;
+  std::map<std::array<int32_t, 4>, int> faces;
+  for (int32_t c = 0; c < g.ncells(); ++c)
+    for (int axis = 0; axis < 3; ++axis)
+    {
+      const int bit = 4 >> axis;
+      for (int v = 0; v < 8; ++v)
+        if (!(v & bit))
+        {
+          std::array<int32_t, 2> e = {g.verts[c][v], g.verts[c][v | bit]};
+          std::sort(e.begin(), e.end());
+          edges.insert(e);
+        }
+      for (int side = 0; side < 2; ++side)
+      {
+        std::array<int32_t, 4> f;
+        int k = 0;
+        for (int v = 0; v < 8; ++v)
+          if (((v & bit) != 0) == (side != 0))
+            f[k++] = g.verts[c][v];
+        std::sort(f.begin(), f.end());
+        faces[f]++;
+      }
+    }
+  const long long want = g.nverts + (long long)edges.size() * (P - 1) + (long long)faces.size() * (P - 1) * (P - 1)
+                         + (long long)g.ncells() * (P - 1) * (P - 1) * (P - 1);
+  CHECK(s.ndofs == want, "mesh generator", "degree %d: %d dofs by identification, %lld by counting", P, s.ndofs, want);
+  std::vector<int32_t> perm(s.ndofs);
+  std::iota(perm.begin(), perm.end(), 0);
+  if (perm_seed)
+  {
+    std::mt19937 rng(perm_seed);
+    std::shuffle(perm.begin(), perm.end(), rng);
+  }
+  for (int32_t& d : s.dofmap)
+    d = perm[d];
+  s.bc.assign(s.ndofs, 0);
+  if (bcmode == BC_RANDOM)
+  {
+    std::mt19937 rng(perm_seed + 77u);
+    for (int32_t d = 0; d < s.ndofs; ++d)
+      s.bc[d] = rng() % 10u == 0;
+  }
+  else if (bcmode == BC_SURFACE)
+    for (int32_t c = 0; c < g.ncells(); ++c)
+      for (int axis = 0; axis < 3; ++axis)
+        for (int side = 0; side < 2; ++side)
+        {
+          const int bit = 4 >> axis;
+          std::array<int32_t, 4> f;
+          int k = 0;
+          for (int v = 0; v < 8; ++v)
+            if (((v & bit) != 0) == (side != 0))
+              f[k++] = g.verts[c][v];
+          std::sort(f.begin(), f.end());
+          if (faces[f] != 1)
+            continue;
+          for (int t = 0; t < N; ++t)
+          {
+            const int idx[3] = {t / (nd * nd), (t / nd) % nd, t % nd};
+            if (idx[axis] == (side ? P : 0))
+              s.bc[s.dofmap[(size_t)c * N + t]] = 1;
+          }
+        }
+  return s;
+}
+
+Space space_of(const Geo& g, int P, Bc bcmode, uint32_t perm_seed = 0)
+{
+  return g.verts.empty() ? box_space(g, P, bcmode, perm_seed) : mesh_space(g, P, bcmode, perm_seed);
 }
 
 // ---- the settings a plan is built under -----------------------------------------------------------------------------
@@ -1108,7 +1382,8 @@ enum ChainExpect
   CH_REFUSE_SPLIT,
   CH_REFUSE_GRID,
   CH_REFUSE_COLOURS,
-  CH_REFUSE_FEW
+  CH_REFUSE_FEW,
+  CH_ANY // accepted or refused: whichever it is, it is classified, checked as that and reported
 };
 constexpr int PRODUCTION_MIN_CHAINS = (256 * 3) / 4; // laplacian.hip: three quarters of the compute units
 
@@ -1121,6 +1396,29 @@ void run_chain(const Geo& g, const Space& s, const PatchPlan& pl, const Referenc
   int npi = 0;
   for (int l = 0; l < pl.n_launch_l; ++l)
     npi += pl.launch_count[l];
+  if (expect == CH_ANY)
+  {
+    const bool col = pl.n_plain > 1 && pl.n_plain == pl.n_launch_l;
+    if (cp.ok)
+      expect = CH_OK;
+    else if (!pl.launch_stream.empty())
+      expect = CH_REFUSE_SPLIT;
+    else if (!col)
+      expect = CH_REFUSE_MERGED;
+    else if (!interior_is_patch_grid(g, pl, npi))
+      expect = CH_REFUSE_GRID;
+    else
+    {
+      // as many positions as patches, and still refused: two patches at one position, patches of a chain that share
+      // dofs without being neighbours, or too many chain colours -- the builder keeps the patch form in each case
+      std::printf("     chain plan: refused on a patch grid\n");
+      return;
+    }
+    static const char* const what[] = {"", "accepted", "refused: merged level", "refused: split plan",
+                                       "refused: no patch grid"};
+    std::printf("     chain plan: %s (%zu chain launches for %d patch colours)\n", what[expect], cp.launch_first.size(),
+                pl.n_plain);
+  }
   CHECK(cp.ok == (expect == CH_OK), "chain plan: accepted or refused as expected", "ok = %d, expectation %d "
         "(n_plain %d, n_launch_l %d, split %d, %d interior patches, min_chains %d)", cp.ok, expect, pl.n_plain,
         pl.n_launch_l, !pl.launch_stream.empty(), npi, min_chains);
@@ -1316,6 +1614,7 @@ struct Case
   std::vector<int> coarse_degrees; // transfers from these degrees to s.P
   uint32_t coarse_perm = 0;
   bool expect_split = false, expect_split_refused = false, expect_split_refused_colours = false;
+  bool observe = false; // no expectation about the split: what the builder decides is checked and reported
 };
 
 void note_coverage(const Case& c, const PatchPlan& pl)
@@ -1326,7 +1625,7 @@ void note_coverage(const Case& c, const PatchPlan& pl)
   for (int p = 0; p < pl.npatch; ++p)
   {
     int lo[3] = {1 << 30, 1 << 30, 1 << 30}, hi[3] = {-1, -1, -1};
-    for (int sl = 0; sl < pl.pncell[p]; ++sl)
+    for (int sl = 0; sl < (c.g.cc.empty() ? 0 : pl.pncell[p]); ++sl)
       for (int a = 0; a < 3; ++a)
       {
         lo[a] = std::min(lo[a], c.g.cc[pl.pcell[(size_t)p * K + sl]][a]);
@@ -1399,6 +1698,8 @@ void run_case(const Case& c)
     const bool attempted = npi >= 16 && std::max(npos[0], std::max(npos[1], npos[2])) >= 4;
     if (attempted)
       cover("split_refused_colours");
+    else if (c.observe)
+      cover("split_refused");
     if (c.expect_split_refused_colours)
       CHECK(attempted, "case", "the split was expected to be attempted: %d interior patches, %d x %d x %d positions",
             npi, npos[0], npos[1], npos[2]);
@@ -1409,7 +1710,7 @@ void run_case(const Case& c)
     run_chain(c.g, c.s, pl, ref, c.chain, c.min_chains);
   for (int pc : c.coarse_degrees)
   {
-    const Space coarse = box_space(c.g, pc, BC_NONE, c.coarse_perm);
+    const Space coarse = space_of(c.g, pc, BC_NONE, c.coarse_perm);
     CoarsePlan cp;
     CHECK(build_coarse(cp, c.g, coarse, pl) == PMG_OK, "build_coarse_plan", "degrees %d -> %d: %s", pc, c.s.P,
           g_last_error.c_str());
@@ -1449,7 +1750,7 @@ Geo patches_geo(int P, int px, int py, int pz, Lists lists, bool shuffle = false
 }
 
 const char* const GROUPS[] = {"boxes", "permuted", "irregular", "lists", "coloured", "split", "chains", "transfers",
-                              "chains_production"};
+                              "chains_production", "multiblock"};
 
 std::vector<Case> cases_of(const std::string& group)
 {
@@ -1697,6 +1998,73 @@ std::vector<Case> cases_of(const std::string& group)
         v.push_back(b);
       }
     }
+  }
+  else if (group == "multiblock")
+  {
+    // Meshes that are no boxes: stars of 3 and 5 sectors (an edge shared by 3 / 5 cells, vertices of valence 6 / 10, a
+    // Jacobian per sector; bent: every centroid with an x of its own), the O-grid (edges of 3 cells, vertices of 4 and
+    // 6, left-handed blocks; twisted) and the notched grid (re-entrant edges, a cavity, columns of cells that stop and
+    // resume).  Sizes per degree: a handful of patches at least.  Nothing is expected of the split and the chains but
+    // that the builder's decision is consistent and the resulting schedule exact.
+    struct Size
+    {
+      int P, star_m, star_nz, ogrid_m, nx, ny, nz;
+      std::vector<int> coarse;
+    };
+    const Size sizes[] = {{1, 4, 16, 6, 8, 8, 32, {}},    {2, 4, 16, 6, 8, 8, 32, {1}}, {4, 4, 8, 4, 4, 4, 32, {1, 2}},
+                          {5, 2, 7, 2, 3, 3, 14, {2}}, {8, 2, 3, 2, 3, 3, 6, {4}}};
+    int i = 0;
+    for (const Size& z : sizes)
+      for (int mesh = 0; mesh < 4; ++mesh)
+        for (int form = 0; form < 2; ++form)
+        {
+          // form 0: one cell list, coloured, the exterior marked; form 1: two lists (a partition between blocks / a
+          // slab), cells shuffled, dofs permuted, random markers, merged or the default threshold
+          const Lists lists = form ? SLAB : ALL_L;
+          const bool bent = form == 0;
+          Geo g;
+          const char* name = "";
+          switch (mesh)
+          {
+          case 0: g = block_geo(star_blocks(3, z.star_m, z.star_nz), bent ? MAP_BEND : MAP_NONE, lists, form, 70 + i); name = "star3"; break;
+          case 1: g = block_geo(star_blocks(5, z.star_m, z.star_nz), bent ? MAP_BEND : MAP_NONE, lists, form, 70 + i); name = "star5"; break;
+          case 2: g = block_geo(ogrid_blocks(z.ogrid_m), bent ? MAP_TWIST : MAP_NONE, lists, form, 70 + i); name = "ogrid"; break;
+          default: g = notched_geo(z.nx, z.ny, z.nz, lists, form, 70 + i); name = "notched"; break;
+          }
+          const long long thr = form == 0 ? THR_COLOURED : (i % 2 ? THR_MERGED : THR_DEFAULT);
+          Case c = mk(nm("%s%s P%d %s%s", name, bent && mesh < 3 ? (mesh == 2 ? " twisted" : " bent") : "", z.P,
+                         form ? (i % 2 ? "merged" : "default") : "coloured", form ? ", two lists, shuffled" : ""),
+                      g, Space(), thr);
+          c.s = space_of(c.g, z.P, form ? BC_RANDOM : BC_SURFACE, form ? 600 + i : 0);
+          c.chain = CH_ANY;
+          c.coarse_degrees = z.coarse;
+          c.coarse_perm = form ? 700 + i : 0;
+          c.observe = true;
+          v.push_back(c);
+          ++i;
+        }
+    // the two-stream split and the chains, asked of levels that are large enough to get them
+    for (int P : {1, 4})
+      for (int mesh = 0; mesh < 4; ++mesh)
+      {
+        Geo g;
+        const char* name = "";
+        switch (mesh)
+        {
+        case 0: g = block_geo(star_blocks(5, 4, P == 1 ? 64 : 8), MAP_NONE, ALL_L); name = "star5"; break;
+        case 1: g = block_geo(star_blocks(3, 4, P == 1 ? 96 : 12), MAP_BEND, ALL_L); name = "star3 bent"; break;
+        case 2: g = block_geo(ogrid_blocks(P == 1 ? 9 : 4), MAP_TWIST, ALL_L); name = "ogrid twisted"; break;
+        default: g = P == 1 ? notched_geo(8, 8, 96, ALL_L) : notched_geo(4, 4, 48, ALL_L); name = "notched"; break;
+        }
+        for (int streams : {2, 0})
+        {
+          Case c = mk(nm("%s P%d, %s", name, P, streams ? "split asked" : "chains asked"), g, Space(), THR_COLOURED, streams);
+          c.s = space_of(c.g, P, BC_SURFACE);
+          c.chain = CH_ANY;
+          c.observe = true;
+          v.push_back(c);
+        }
+      }
   }
   return v;
 }

@@ -31,7 +31,8 @@ def tensor_G(P, xgeom, geom_dofmap, T):
     J = np.einsum("ckd,rqk->cqdr", xc, dphi)
     det = np.linalg.det(J)
     adj = det[..., None, None] * np.linalg.inv(J)  # [nc, nq, r, d]
-    M = np.einsum("cqad,cde,cqbe->cqab", adj, full(T), adj) * (w3[None, :] / det)[..., None, None]
+    # |det J|: a left-handed cell (det J < 0) has the same positive-definite tensor as in any other frame
+    M = np.einsum("cqad,cde,cqbe->cqab", adj, full(T), adj) * (w3[None, :] / np.abs(det))[..., None, None]
     return packed(M)
 
 

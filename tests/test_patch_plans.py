@@ -43,6 +43,16 @@ GROUPS = {
                 "chain_refused_colours", "chain_refused_few_chains", "form_chains"] + WALKS, 10),
     "chains_production": (["chain_ok", "form_chains"] + WALKS, 20),
     "transfers": (["coarse_coloured", "coarse_merged", "coarse_refused", "coalesced_step"] + WALKS, 10),
+    # Meshes that are no boxes (stars of 3 and 5 sectors, the O-grid, the notched grid; 6.5 s).  The grouping flags are
+    # required; the split, chain and coarse flags are what the builder yields there: the notched grid (a tensor grid of
+    # centroids with gaps: tensor_grouping, ragged_blocks) is split over two streams, a star or an O-grid is not (the
+    # colours of Morton patches do not separate the halves); no such mesh gets chains (its patches form no tensor
+    # grid, or the level is merged or split) and each then runs, and is checked, in the patch form; every coarse plan
+    # is accepted, coloured and merged.
+    "multiblock": (["morton_grouping", "halved_group", "halved_group_high_degree", "coloured_interior",
+                    "merged_interior", "coalesced_step", "tensor_grouping", "ragged_blocks", "split_plan",
+                    "split_refused_colours", "fp32_unsplit", "chain_refused_grid", "chain_refused_merged",
+                    "chain_refused_split", "coarse_coloured", "coarse_merged"] + WALKS, 40),
 }
 
 
