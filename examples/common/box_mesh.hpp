@@ -46,6 +46,54 @@ struct BoxMesh
   }
 };
 
+/// The drivers' --curved G: the box bent by a fixed smooth map and described by a coordinate element of degree G
+/// (pmg_amd.h "curved cells").  From the vertices and the 8-node dofmap of any box mesh of this directory (BoxMesh,
+/// BrickPartition) it makes the degree-G node grid of every cell -- the GLL nodes `gll` of degree G at the trilinear
+/// positions between the cell's own corners, k = (i (G+1) + j)(G+1) + l, one node set per cell (a shared node may be
+/// stored once per cell) -- and maps every node.  G = 1: the straight-sided mesh through the mapped vertices.
+inline void curved_map(double* x)
+{
+  const double a = x[0], b = x[1], c = x[2];
+  x[0] = a + 0.05 * std::sin(2.0 * b + c);
+  x[1] = b + 0.05 * std::sin(2.0 * c + a);
+  x[2] = c + 0.05 * std::sin(2.0 * a + b);
+}
+struct CurvedGeometry
+{
+  int degree;
+  std::vector<double> xgeom;             // [ncells * (G+1)^3][3]
+  std::vector<std::int32_t> geom_dofmap; // [ncells][(G+1)^3]
+
+  CurvedGeometry(const std::vector<double>& vertices, const std::vector<std::int32_t>& corner_dofmap, int G,
+                 const std::vector<double>& gll)
+      : degree(G)
+  {
+    const int m = G + 1, ng = m * m * m;
+    const std::size_t ncells = corner_dofmap.size() / 8;
+    xgeom.resize(3 * ncells * ng);
+    geom_dofmap.resize(ncells * ng);
+    for (std::size_t c = 0; c < ncells; ++c)
+      for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j)
+          for (int l = 0; l < m; ++l)
+          {
+            const std::size_t node = c * ng + (std::size_t)(i * m + j) * m + l;
+            double x[3] = {0, 0, 0};
+            for (int k = 0; k < 8; ++k)
+            {
+              const double wgt = ((k & 4) ? gll[i] : 1.0 - gll[i]) * ((k & 2) ? gll[j] : 1.0 - gll[j])
+                                 * ((k & 1) ? gll[l] : 1.0 - gll[l]);
+              for (int d = 0; d < 3; ++d)
+                x[d] += wgt * vertices[3 * (std::size_t)corner_dofmap[8 * c + k] + d];
+            }
+            curved_map(x);
+            for (int d = 0; d < 3; ++d)
+              xgeom[3 * node + d] = x[d];
+            geom_dofmap[node] = (std::int32_t)node;
+          }
+  }
+};
+
 /// Degree-P space on the mesh: dofmap, Dirichlet marker on the whole boundary
 /// (examples/mat_free/main.cpp:163-165,236-240), dof coordinates.
 struct FunctionSpace

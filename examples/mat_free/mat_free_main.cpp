@@ -15,6 +15,10 @@
 // --robin A keeps the Dirichlet marker on the face x = 0 only and puts a Robin term with alpha = A (1 + y) at the facet
 // points of the other five faces (not in the reference; pmg_laplacian_set_robin); it combines with the three above,
 // and the stencil comparison is left out as well.
+// --curved G (1..4) bends the box by a fixed smooth map (examples/common/box_mesh.hpp: curved_map) and hands the library
+// a coordinate element of degree G (pmg_laplacian_create_curved through the adapter, which infers G from the geometry
+// dofmap's width); G = 1 is the straight-sided mesh through the mapped vertices.  It combines with every flag above
+// (their data stay functions of the box coordinates); the stencil comparison is left out as well.
 // --lift restates the right-hand side the reference's driver has commented out (:252-255): u = the assembled load of
 // f = 0 (:133,143: the interpolation of f is commented out as well), lifted with the boundary value 1.3 (:165) and
 // set_bc -- pmg_laplacian_assemble_rhs, _apply_lifting, _set_bc on the one operator -- instead of u = 1.
@@ -41,6 +45,7 @@ int main(int argc, char** argv)
   bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false;
   double reaction = 0.0; // S of --reaction; 0 = no term
   double robin = 0.0;    // A of --robin; 0 = no term
+  int curved = 0;        // G of --curved; 0 = the unit box, trilinear
   std::size_t batch_size = 0; // :38,46-50: cells whose geometry tensor is held at a time (0 = all, resident)
   for (int i = 1; i < argc; ++i)
   {
@@ -63,6 +68,8 @@ int main(int argc, char** argv)
       reaction = std::atof(next());
     else if (!std::strcmp(argv[i], "--robin"))
       robin = std::atof(next());
+    else if (!std::strcmp(argv[i], "--curved"))
+      curved = std::atoi(next());
     else if (!std::strcmp(argv[i], "--lift"))
       lift = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
@@ -70,7 +77,7 @@ int main(int argc, char** argv)
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--lift]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -93,8 +100,17 @@ int main(int argc, char** argv)
 
     auto map = std::make_shared<const IndexMap>(V.ndofs, 0);
     device_array<double> kappa(std::vector<double>(mesh.ncells(), 2.0)); // :132
-    device_array<std::int32_t> dofmap(V.dofmap), xdofmap(mesh.geom_dofmap);
-    device_array<double> xgeom(mesh.xgeom);
+    if (curved < 0 || curved > PMG_MAX_GEOM_DEGREE)
+      throw std::runtime_error("--curved takes a geometry degree 1..4");
+    std::vector<double> gll_g(curved + 1), w_g(curved + 1);
+    if (curved)
+      check(pmg_gll_table(curved + 1, gll_g.data(), w_g.data()));
+    const examples::CurvedGeometry bent(mesh.xgeom, mesh.geom_dofmap, curved ? curved : 1,
+                                        curved ? gll_g : std::vector<double>{0.0, 1.0});
+    if (curved)
+      std::cout << "Curved cells: coordinate element of degree " << curved << "\n";
+    device_array<std::int32_t> dofmap(V.dofmap), xdofmap(curved ? bent.geom_dofmap : mesh.geom_dofmap);
+    device_array<double> xgeom(curved ? bent.xgeom : mesh.xgeom);
     device_array<std::int8_t> bc(V.bc_marker);
     // one rank: no ghost dofs, so every cell comes out local (src/mesh.hpp:105-143)
     auto [lcells, bcells] = compute_boundary_cells(V.dofmap, mesh.ncells(), mesh.ncells(), nd * nd * nd, V.ndofs);
@@ -193,7 +209,7 @@ int main(int argc, char** argv)
       std::printf("CSR Matvec: %d reps, %.3f us per apply\n", nreps, ms * 1e3 / nreps);
       std::printf("CSR nnz = %zu\n", mat.nnz());
       acc::axpy(ec, -1.0, y, zc);
-      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0)
+      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0 || curved)
       {
         std::printf("Norm of z = %.15e\n", acc::norm(zc));
         std::printf("Norm of error = %.3e\n", acc::norm(ec));

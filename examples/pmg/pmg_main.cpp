@@ -33,6 +33,10 @@
 //   --reaction S     the reaction term sigma u on every level, sigma_c = S (1 + x_c) at the cell centre
 //                    (pmg_laplacian_set_reaction); combines with --kappa-field, --kappa-tensor, --amg, --pcg,
 //                    --fp32-cycle, --csr
+//   --curved G       the box bent by a fixed smooth map (examples/common/box_mesh.hpp: curved_map) with a coordinate
+//                    element of degree G = 1..4 (pmg_laplacian_create_curved); G = 1: the straight-sided mesh through
+//                    the mapped vertices.  The data of the other flags stay functions of the box coordinates;
+//                    combines with --kappa-field, --kappa-tensor, --reaction, --robin, --fp32-cycle, --csr, --amg, --pcg
 //   --check-partition px,py,pz   host-only consistency check of the brick partition (no GPU)
 //   --node-order basix   the dofmaps handed over in basix's cell-local node order (endpoints first), as dolfinx
 //                    gives them to the reference (examples/pmg/main.cpp:83-87); same numbers as without
@@ -95,6 +99,7 @@ struct Options : examples::RankOptions
   bool kappa_tensor = false;   // --kappa-tensor: per-cell tensor, eigenvalues (1, 2 + x, 4) rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z)
   double reaction = 0.0;       // --reaction S: sigma_c = S (1 + x_c); 0 = no term
   double robin = 0.0;          // --robin A: Dirichlet on x = 0 only, alpha = A (1 + y) on the other five faces; 0 = no term
+  int curved = 0;              // --curved G: the box bent by examples::curved_map, coordinate element of degree G; 0 = the unit box
   bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
   std::vector<int> csr_levels; // empty with --csr: every level
 };
@@ -112,8 +117,16 @@ void solve(const Options& o)
 
   examples::BrickPartition mesh(o.n, o.ranks, o.rank);
   device_array<T> constants(std::vector<T>(mesh.ncells, kappa));
-  device_array<T> geom_x_d(mesh.xgeom);
-  device_array<std::int32_t> geom_x_dofmap_d(mesh.geom_dofmap);
+  // --curved G: the degree-G node grid of every local cell, mapped (the adapter infers G from the dofmap's width)
+  std::vector<double> gll_g(o.curved + 1), w_g(o.curved + 1);
+  if (o.curved)
+    check(pmg_gll_table(o.curved + 1, gll_g.data(), w_g.data()));
+  const examples::CurvedGeometry bent(mesh.xgeom, mesh.geom_dofmap, o.curved ? o.curved : 1,
+                                      o.curved ? gll_g : std::vector<double>{0.0, 1.0});
+  if (o.curved && root)
+    std::printf("Curved cells: coordinate element of degree %d\n", o.curved);
+  device_array<T> geom_x_d(o.curved ? bent.xgeom : mesh.xgeom);
+  device_array<std::int32_t> geom_x_dofmap_d(o.curved ? bent.geom_dofmap : mesh.geom_dofmap);
   std::span<const T> device_constants = constants.span(), geom_x = geom_x_d.span();
   std::span<const std::int32_t> geom_x_dofmap = geom_x_dofmap_d.span();
 
@@ -452,6 +465,12 @@ int main(int argc, char** argv)
         o.reaction = std::atof(argv[++i]);
       else if (!std::strcmp(argv[i], "--robin") && i + 1 < argc)
         o.robin = std::atof(argv[++i]);
+      else if (!std::strcmp(argv[i], "--curved") && i + 1 < argc)
+      {
+        o.curved = std::atoi(argv[++i]);
+        if (o.curved < 1 || o.curved > PMG_MAX_GEOM_DEGREE)
+          throw std::runtime_error("--curved takes a geometry degree 1..4");
+      }
       else if (!std::strcmp(argv[i], "--csr"))
       {
         o.csr = true;
@@ -518,7 +537,7 @@ int main(int argc, char** argv)
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
                      "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
-                     "           [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A]\n"
+                     "           [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"

@@ -294,7 +294,8 @@ int pmg_vec_norm(pmg_layout l, const double* a, int norm_type, double* result, p
  * the signed value): "detJ" below -- in G, in the load vector and in the reaction vector -- stands for |det J_q|.
  * adj(J) keeps its sign: it enters G twice and the facet measure through a norm.  For a right-handed cell nothing
  * changes, bit for bit.  A cell whose determinant changes sign inside the cell is not a valid cell.
- * What the library requires of a mesh: hexahedra with trilinear geometry, and a CONFORMING dofmap -- two cells hold the
+ * What the library requires of a mesh: hexahedra with trilinear geometry (or, through pmg_laplacian_create_curved
+ * below, with a tensor-product coordinate element of degree up to 4), and a CONFORMING dofmap -- two cells hold the
  * same dof exactly where they share the vertex, edge or face that carries it.  Nothing about structure or valence: an
  * edge may be shared by any number of cells (3 and 5 are tested), a vertex likewise (3 to 10), blocks may meet with
  * local axes that do not line up, the domain may have re-entrant corners and cavities, a partition interface need not
@@ -329,6 +330,40 @@ int pmg_laplacian_create_ordered(pmg_laplacian* out, pmg_layout layout, int degr
                                  const int8_t* bc_marker, int node_order, const int32_t* custom_perm1d,
                                  pmg_stream stream);
 int pmg_laplacian_node_order(pmg_laplacian op); /* PMG_NODES_* the operator was created with */
+/* ---- curved cells: a coordinate element of degree 1..PMG_MAX_GEOM_DEGREE
+ * The mesh requirement above ("trilinear geometry") is the geom_degree = 1 case of this constructor, which all the
+ * others call.  Conventions:
+ *   coordinate element  the tensor-product Lagrange element of degree g = geom_degree on the hexahedron.  Its 1-D nodes
+ *                  are the GLL points of degree g on [0, 1] (pmg_gll_table(g + 1)); for g <= 2 these are the
+ *                  equispaced points.  A caller with another node family passes its own tabulation (last entry).
+ *   geom_dofmap    [ncells * (g+1)^3]  the cell's nodes, k = (i*(g+1) + j)*(g+1) + l with i, j, l the node numbers
+ *                  along the cell's axes x, y, z by ASCENDING coordinate -- for g = 1 the k = i*4+j*2+l above.  The
+ *                  axes are the same three as those of `dofmap`.  `node_order` applies to `dofmap`, to the rows (q) of
+ *                  dphi_geometry and to G_weights only: the geometry nodes are always in ascending tensor order (a
+ *                  geometry dofmap in another order, e.g. a dolfinx hex27 one, is permuted by the caller).
+ *   xgeom          [3 * npoints] as before.  A node shared by two cells may be stored once or once per cell; the
+ *                  library relies on neither.
+ *   frames         cell frames and left-handed cells work as for g = 1: measures are |det J|, adj(J) keeps its sign.
+ *   caller tables  dphi_geometry [3][nq][(g+1)^3] and G_weights [nq], both given or both NULL, override the library's
+ *                  tabulation: q in the caller's node_order, k in ascending tensor order.
+ * Every entry of geom_dofmap must lie in [0, npoints); a geom_degree outside 1..PMG_MAX_GEOM_DEGREE is refused with
+ * PMG_ERR_INVALID.  On any refusal *out is NULL.  With the library's own tabulation the tensor of a g >= 2 operator is
+ * built by a cell-cooperative, sum-factorised kernel; with caller tables, which need not be a tensor product, by a
+ * thread per point over the dense table.  The stored tensor is per quadrature point already, so the apply kernels, the
+ * diagonal, the assembled matrix, the transfers and the smoothers are those of a trilinear mesh.  A cell is affine
+ * (pmg_laplacian_is_affine) only if every one of its (g+1)^3 nodes sits where the affine map of its corners puts it. */
+#define PMG_MAX_GEOM_DEGREE 4
+int pmg_laplacian_create_curved(pmg_laplacian* out, pmg_layout layout, int degree, int32_t ncells, const double* kappa,
+                                const int32_t* dofmap, const double* xgeom, int32_t npoints, int geom_degree,
+                                const int32_t* geom_dofmap, const double* dphi_geometry, const double* G_weights,
+                                const int32_t* lcells, int32_t n_lcells, const int32_t* bcells, int32_t n_bcells,
+                                const int8_t* bc_marker, int node_order, const int32_t* custom_perm1d,
+                                pmg_stream stream);
+int pmg_laplacian_geometry_degree(pmg_laplacian op); /* 1..PMG_MAX_GEOM_DEGREE; -1 for NULL */
+/* Host, no GPU: what the coordinate element's tabulate(1, GLL points of `degree`) returns, dphi[3][nq][(g+1)^3] with
+ * q in node_order and k in ascending tensor order -- the table the library builds for itself. */
+int pmg_coordinate_element_table(int degree, int geom_degree, int node_order, const int32_t* custom_perm1d,
+                                 double* dphi);
 int pmg_laplacian_destroy(pmg_laplacian op);
 /* operator()(in, out), :462-482: zeroes `out` (ghosts included), updates the
  * ghosts of `in` (side effect, as in the reference), interior cells overlap

@@ -614,9 +614,20 @@ public:
     if (degree < 1 || degree > PMG_MAX_DEGREE)
       throw std::runtime_error("Unsupported degree [mat-free operator]"); // :346
     const std::size_t N = (std::size_t)(degree + 1) * (degree + 1) * (degree + 1);
-    if (dofmap.size() % N != 0 || dofmap.size() / N != coefficients.size()
-        || geometry_dofmap.size() != 8 * coefficients.size())
+    if (dofmap.size() % N != 0 || dofmap.size() / N != coefficients.size())
       throw std::runtime_error("MatFreeLaplacian: array sizes do not match the cell count");
+    // the coordinate element's degree g follows from the geometry dofmap's width (g+1)^3 in {8, 27, 64, 125}
+    // (pmg_amd.h "curved cells"), and dphi_geometry, when given, is [3][N][(g+1)^3]
+    for (int g = 1; g <= PMG_MAX_GEOM_DEGREE && _geom_degree == 0; ++g)
+      if (geometry_dofmap.size() == (std::size_t)(g + 1) * (g + 1) * (g + 1) * coefficients.size())
+        _geom_degree = g;
+    if (coefficients.empty())
+      _geom_degree = 1;
+    if (_geom_degree == 0)
+      throw std::runtime_error("MatFreeLaplacian: array sizes do not match the cell count");
+    const std::size_t ng = (std::size_t)(_geom_degree + 1) * (_geom_degree + 1) * (_geom_degree + 1);
+    if (!dphi_geometry.empty() && !G_weights.empty() && _geom_degree > 1 && dphi_geometry.size() != 3 * N * ng)
+      throw std::runtime_error("MatFreeLaplacian: dphi_geometry does not match the geometry dofmap's width");
   }
   MatFreeLaplacian(const MatFreeLaplacian&) = delete;
   MatFreeLaplacian& operator=(const MatFreeLaplacian&) = delete;
@@ -778,6 +789,7 @@ public:
   }
   bool has_robin() const { return _op && pmg_laplacian_has_robin(_op) == 1; }
   int degree() const { return _degree; }
+  int geometry_degree() const { return _geom_degree; }
 
   pmg_laplacian handle(const std::shared_ptr<const IndexMap>& map)
   {
@@ -788,9 +800,9 @@ public:
       // dofmap, dphi_geometry and G_weights are indexed in the caller's cell-local node order (the library keeps
       // an ascending copy of the dofmap); without the two tables the library builds its own
       const bool tables = !_dphi.empty() && !_gw.empty();
-      check(pmg_laplacian_create_ordered(
+      check(pmg_laplacian_create_curved(
           &_op, map->layout(), _degree, (std::int32_t)_kappa.size(), _kappa.data(), _dofmap.data(), _xgeom.data(),
-          (std::int32_t)(_xgeom.size() / 3), _geom_dofmap.data(), tables ? _dphi.data() : nullptr,
+          (std::int32_t)(_xgeom.size() / 3), _geom_degree, _geom_dofmap.data(), tables ? _dphi.data() : nullptr,
           tables ? _gw.data() : nullptr, _lcells.data(), (std::int32_t)_lcells.size(), _bcells.data(),
           (std::int32_t)_bcells.size(), _bc.data(), static_cast<int>(_node_order), nullptr, nullptr));
       if (_batch_size != 0) // :383-396: the geometry tensor is not kept, it is recomputed batch by batch
@@ -804,6 +816,7 @@ public:
 
 private:
   int _degree;
+  int _geom_degree = 0;
   std::span<const T> _kappa;
   std::span<const std::int32_t> _dofmap;
   std::span<const T> _xgeom;

@@ -12,7 +12,7 @@ from .interpolate import Interpolator  # noqa: F401
 from .laplacian import MatFreeLaplacian, node_permutation, set_merge_threshold  # noqa: F401
 from .matrix import MatrixOperator  # noqa: F401
 from .mesh import (BoxPartition, basix_node_permutation, cell_permutation, cell_symmetries,  # noqa: F401
-                   default_proc_dims, dofmap_in_node_order, facet_nodes, frame_facet_map, frame_node_map)
+                   coordinate_element_table, default_proc_dims, dofmap_in_node_order, facet_nodes, frame_facet_map, frame_node_map)
 from .pmg import MultigridPreconditioner  # noqa: F401
 from .problem import PoissonHierarchy, make_layout  # noqa: F401
 from .vector import (Layout, RcclComm, TorchComm, Vector, WindowComm, axpy, copy, inner_product, norm, pointwise_mult, scale,  # noqa: F401

@@ -90,6 +90,13 @@ _SIGS = {
         [C.POINTER(vp), vp, C.c_int, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, c_ip, C.c_int32, c_ip,
          C.c_int32, vp, C.c_int, c_ip, vp],
     ),
+    "pmg_laplacian_create_curved": (
+        C.c_int,
+        [C.POINTER(vp), vp, C.c_int, C.c_int32, vp, vp, vp, C.c_int32, C.c_int, vp, vp, vp, c_ip, C.c_int32, c_ip,
+         C.c_int32, vp, C.c_int, c_ip, vp],
+    ),
+    "pmg_laplacian_geometry_degree": (C.c_int, [vp]),
+    "pmg_coordinate_element_table": (C.c_int, [C.c_int, C.c_int, C.c_int, c_ip, c_dp]),
     "pmg_laplacian_node_order": (C.c_int, [vp]),
     "pmg_node_permutation": (C.c_int, [C.c_int, C.c_int, c_ip, c_ip]),
     "pmg_gll_table_ordered": (C.c_int, [C.c_int, C.c_int, c_ip, c_dp, c_dp]),
@@ -215,7 +222,7 @@ _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplac
                 "pmg_laplacian_degree", "pmg_multigrid_precision", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine",
                 "pmg_laplacian_has_coefficient_field", "pmg_laplacian_has_coefficient_tensor", "pmg_laplacian_has_reaction", "pmg_laplacian_has_robin", "pmg_laplacian_lift_cell_count",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
-                "pmg_laplacian_node_order", "pmg_layout_forward_scatters",
+                "pmg_laplacian_node_order", "pmg_laplacian_geometry_degree", "pmg_layout_forward_scatters",
                 "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions",
                 "pmg_chebyshev_recomputed"}
 

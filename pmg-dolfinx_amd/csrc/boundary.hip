@@ -36,7 +36,7 @@ template <int ND>
 __global__ void __launch_bounds__(LiftShape<ND>::THREADS)
     lifting_kernel(int nlift, const int32_t* __restrict__ lift_cells, const int32_t* __restrict__ dofmap,
                    const int8_t* __restrict__ bc, int32_t size_local, const double* __restrict__ xgeom,
-                   const int32_t* __restrict__ geom_dofmap, const double* __restrict__ dphi,
+                   const int32_t* __restrict__ geom_dofmap, int ng, const double* __restrict__ dphi,
                    const double* __restrict__ w, const double* __restrict__ D, const double* __restrict__ kfield,
                    const double* __restrict__ ktensor, const double* __restrict__ kappa, const double* __restrict__ g,
                    const double* __restrict__ x0, double alpha, double* __restrict__ b)
@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(LiftShape<ND>::THREADS)
       d2 += Ds[c * ND + i] * ue[(a * ND + bb) * ND + i];
     }
     double K[3][3], detJ;
-    jacobian(xgeom, geom_dofmap + (size_t)cell * 8, dphi, N, t, K, detJ);
+    jacobian(xgeom, geom_dofmap + (size_t)cell * ng, dphi, N, t, ng, K, detJ);
     double s = w[t] / detJ;
     if (kfield)
       s *= kfield[dof];
@@ -141,7 +141,7 @@ __global__ void set_bc_kernel(int n, const int8_t* __restrict__ bc, const double
 __device__ __forceinline__ bool facet_point(long long gid, int nd, const int32_t* __restrict__ fcells,
                                             const int8_t* __restrict__ flocal, const int32_t* __restrict__ dofmap,
                                             const int8_t* __restrict__ bc, int32_t ndofs,
-                                            const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                                            const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap, int ng,
                                             const double* __restrict__ dphi, const double* __restrict__ w1,
                                             int32_t& dof, double& wdS)
 {
@@ -154,7 +154,7 @@ __device__ __forceinline__ bool facet_point(long long gid, int nd, const int32_t
   if (bc[dof] || dof >= ndofs)
     return false;
   double K[3][3], detJ;
-  jacobian(xgeom, geom_dofmap + (size_t)cell * 8, dphi, N, t, K, detJ);
+  jacobian(xgeom, geom_dofmap + (size_t)cell * ng, dphi, N, t, ng, K, detJ);
   const double* r = K[axis];
   const double dS = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
   wdS = w1[i] * w1[j] * dS;
@@ -165,7 +165,7 @@ __device__ __forceinline__ bool facet_point(long long gid, int nd, const int32_t
 __global__ void neumann_kernel(long long npoints, int nd, const int32_t* __restrict__ fcells,
                                const int8_t* __restrict__ flocal, const double* __restrict__ h,
                                const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc, int32_t size_local,
-                               const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                               const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap, int ng,
                                const double* __restrict__ dphi, const double* __restrict__ w1,
                                double* __restrict__ b)
 {
@@ -174,7 +174,7 @@ __global__ void neumann_kernel(long long npoints, int nd, const int32_t* __restr
     return;
   int32_t dof;
   double wdS;
-  if (facet_point(gid, nd, fcells, flocal, dofmap, bc, size_local, xgeom, geom_dofmap, dphi, w1, dof, wdS))
+  if (facet_point(gid, nd, fcells, flocal, dofmap, bc, size_local, xgeom, geom_dofmap, ng, dphi, w1, dof, wdS))
     atomicAdd(&b[dof], wdS * h[gid]);
 }
 
@@ -183,7 +183,7 @@ __global__ void neumann_kernel(long long npoints, int nd, const int32_t* __restr
 __global__ void robin_kernel(long long npoints, int nd, const int32_t* __restrict__ fcells,
                              const int8_t* __restrict__ flocal, const double* __restrict__ alpha,
                              const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc, int32_t total,
-                             const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                             const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap, int ng,
                              const double* __restrict__ dphi, const double* __restrict__ w1, double* __restrict__ d)
 {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -191,7 +191,7 @@ __global__ void robin_kernel(long long npoints, int nd, const int32_t* __restric
     return;
   int32_t dof;
   double wdS;
-  if (facet_point(gid, nd, fcells, flocal, dofmap, bc, total, xgeom, geom_dofmap, dphi, w1, dof, wdS))
+  if (facet_point(gid, nd, fcells, flocal, dofmap, bc, total, xgeom, geom_dofmap, ng, dphi, w1, dof, wdS))
     atomicAdd(&d[dof], wdS * alpha[gid]);
 }
 
@@ -285,7 +285,7 @@ void launch_lifting(pmg_laplacian op, const double* g, const double* x0, double 
   using Sh = LiftShape<ND>;
   const unsigned blocks = (unsigned)((op->n_lift + Sh::CPW - 1) / Sh::CPW);
   lifting_kernel<ND><<<blocks, Sh::THREADS, 0, s>>>(op->n_lift, op->lift_cells, op->dofmap, op->bc,
-                                                   op->layout->size_local, op->xgeom, op->geom_dofmap, op->dphi_geom,
+                                                   op->layout->size_local, op->xgeom, op->geom_dofmap, op->ng, op->dphi_geom,
                                                    op->gweights, op->D, op->kfield, op->ktensor, op->kappa, g, x0, alpha,
                                                    b);
 }
@@ -357,7 +357,7 @@ extern "C" int pmg_laplacian_assemble_neumann(pmg_laplacian op, int32_t nfacets,
   {
     const long long np = (long long)nfacets * (long long)nf;
     neumann_kernel<<<(unsigned)((np + 255) / 256), 256, 0, s>>>(np, op->nd, d_cells, d_local, h, op->dofmap, op->bc,
-                                                              op->layout->size_local, op->xgeom, op->geom_dofmap,
+                                                              op->layout->size_local, op->xgeom, op->geom_dofmap, op->ng,
                                                               op->dphi_geom, op->W1, b);
     e = hipGetLastError();
   }
@@ -427,7 +427,7 @@ extern "C" int pmg_laplacian_set_robin(pmg_laplacian op, int32_t nfacets, const 
   if (e == hipSuccess)
   {
     robin_kernel<<<(unsigned)((np + 255) / 256), 256, 0, s>>>(np, op->nd, d_cells, d_local, alpha, op->dofmap, op->bc,
-                                                            total, op->xgeom, op->geom_dofmap, op->dphi_geom, op->W1,
+                                                            total, op->xgeom, op->geom_dofmap, op->ng, op->dphi_geom, op->W1,
                                                             op->robin_buf);
     e = hipGetLastError();
   }

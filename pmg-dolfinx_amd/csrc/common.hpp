@@ -80,6 +80,10 @@ static_assert(PMG_MAX_DEGREE == 8, "with_degree lists the degrees");
 void gll_table(int n, double* x, double* w);
 void lagrange_derivative_table(int n, const double* x, double* D);
 void lagrange_eval_table(int nc, const double* xc, int nf, const double* xf, double* M);
+// coordinate element of degree g: its 1-D basis / derivative at the n points x, L / Lp [n][g+1], and the dense
+// tabulation dphi[3][nd^3][m^3] they give (tables.hip)
+void coordinate_element_tables_1d(int n, const double* x, int g, double* L, double* Lp);
+void coordinate_element_table_3d(int nd, int m, const double* L, const double* Lp, double* dphi);
 
 // Cell-local node order (pmg_amd.h "cell-local node order"; tables.hip).  perm1d[j] = ascending position of the
 // caller's 1-D node j; node_permutation validates / builds it, cell_permutation expands it to the nd^3 cell-local

@@ -91,8 +91,9 @@ __global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K
 
 // Constant geometry tensor of an affine cell: K K^T / detJ at the cell centre
 // (q-independent when the cell is a parallelepiped); G_q = w_q * this.  ktensor (optional): the per-cell diffusion
-// tensor, constant over the cell like the rest: K Kc K^T / detJ.
-__global__ void affine_geometry_kernel(long long nslots, const int32_t* __restrict__ pcell,
+// tensor, constant over the cell like the rest: K Kc K^T / detJ.  g: the coordinate element's degree; the four corners
+// that span the cell sit at the tensor positions (0,0,0), (0,0,g), (0,g,0), (g,0,0) of its (g+1)^3 nodes.
+__global__ void affine_geometry_kernel(long long nslots, int gdeg, const int32_t* __restrict__ pcell,
                                        const double* __restrict__ xgeom,
                                        const int32_t* __restrict__ geom_dofmap,
                                        const double* __restrict__ ktensor, double* __restrict__ Gaff)
@@ -104,11 +105,12 @@ __global__ void affine_geometry_kernel(long long nslots, const int32_t* __restri
   double g[6] = {0, 0, 0, 0, 0, 0};
   if (c >= 0)
   {
-    const int32_t* gd = geom_dofmap + (size_t)c * 8;
+    const int m = gdeg + 1;
+    const int32_t* gd = geom_dofmap + (size_t)c * m * m * m;
     const double* x0 = xgeom + 3 * (size_t)gd[0];
-    const double* xz = xgeom + 3 * (size_t)gd[1]; // (0,0,1)
-    const double* xy = xgeom + 3 * (size_t)gd[2]; // (0,1,0)
-    const double* xx = xgeom + 3 * (size_t)gd[4]; // (1,0,0)
+    const double* xz = xgeom + 3 * (size_t)gd[gdeg];         // (0,0,g)
+    const double* xy = xgeom + 3 * (size_t)gd[gdeg * m];     // (0,g,0)
+    const double* xx = xgeom + 3 * (size_t)gd[gdeg * m * m]; // (g,0,0)
     double J[3][3];
     for (int i = 0; i < 3; ++i)
     {
@@ -228,7 +230,7 @@ __global__ void diag_invert_kernel(int n, const int8_t* __restrict__ bc, const d
 }
 
 // ---- GLL-collocated load vector ----
-__global__ void rhs_kernel(long long nslots, int nq, const int32_t* __restrict__ pcell,
+__global__ void rhs_kernel(long long nslots, int nq, int ng, const int32_t* __restrict__ pcell,
                            const double* __restrict__ xgeom,
                            const int32_t* __restrict__ geom_dofmap,
                            const double* __restrict__ dphi, const double* __restrict__ w,
@@ -248,13 +250,13 @@ __global__ void rhs_kernel(long long nslots, int nq, const int32_t* __restrict__
   if (bc[dof])
     return; // set_bc: b[bc] = 0 (b is zeroed first)
   double K[3][3], detJ;
-  jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
+  jacobian(xgeom, geom_dofmap + (size_t)c * ng, dphi, nq, q, ng, K, detJ);
   atomicAdd(&b[dof], kappa[c] * w[q] * detJ * f[dof]);
 }
 
 // ---- reaction vector: d[dof] = sum over the listed cells' points on the dof of sigma_c w_q detJ_q, the weights of
 // rhs_kernel with sigma in place of kappa and f = 1 (d is zeroed first; marked dofs stay 0: their rows are y = x) ----
-__global__ void reaction_kernel(long long nslots, int nq, const int32_t* __restrict__ pcell,
+__global__ void reaction_kernel(long long nslots, int nq, int ng, const int32_t* __restrict__ pcell,
                                 const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
                                 const double* __restrict__ dphi, const double* __restrict__ w,
                                 const int32_t* __restrict__ dofmap, const int8_t* __restrict__ bc,
@@ -272,6 +274,6 @@ __global__ void reaction_kernel(long long nslots, int nq, const int32_t* __restr
   if (bc[dof])
     return;
   double K[3][3], detJ;
-  jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
+  jacobian(xgeom, geom_dofmap + (size_t)c * ng, dphi, nq, q, ng, K, detJ);
   atomicAdd(&d[dof], sigma[c] * w[q] * detJ);
 }

@@ -43,6 +43,7 @@
 //   stiffness_restrict.hpp  stiffness_restrict_kernel: the apply fused with the restriction of r - A z
 //   laplacian.hip         the host side: launch plan, run_launches, the C ABI
 #include "laplacian.hpp"
+#include "curved_geometry.hpp"
 #include "stiffness_layer.hpp"
 
 #include <algorithm>
@@ -60,6 +61,19 @@ namespace
 #include "stiffness_chain.hpp"
 #include "stiffness_restrict.hpp"
 
+// where the degree-g geometry kernels (curved_geometry.hpp) put a point's six values: the stored tensor's layout
+struct TensorOut64
+{
+  double2* G; // absolute slot positions (batch_geometry)
+  int nd, K;
+  __device__ __forceinline__ void operator()(long long slot, int q, const double g[6]) const
+  {
+    G[gpos(nd, K, slot, q, 0)] = make_double2(g[0], g[1]);
+    G[gpos(nd, K, slot, q, 1)] = make_double2(g[2], g[3]);
+    G[gpos(nd, K, slot, q, 2)] = make_double2(g[4], g[5]);
+  }
+};
+
 __global__ void zero_list_kernel(int n, const int32_t* __restrict__ idx, double* __restrict__ y)
 {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
@@ -72,7 +86,9 @@ const double2* batch_geometry(pmg_laplacian op, int first, int count, hipStream_
 {
   double2* base = op->G - (size_t)first * gpatch(op->nd, op->K);
   const long long nslots = (long long)count * op->K, n = nslots * op->N;
-  if (n > 0)
+  if (op->ng != 8) // a coordinate element of degree >= 2 (curved_geometry.hpp)
+    launch_curved_geometry(op, (long long)first * op->K, nslots, TensorOut64{base, op->nd, op->K}, s);
+  else if (n > 0)
     geometry_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)first * op->K, nslots, op->nd, op->K,
                                                               op->pcell, op->xgeom, op->geom_dofmap,
                                                               op->dphi_geom, op->gweights, op->kfield, op->dofmap,
@@ -374,16 +390,24 @@ int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_
 }
 } // namespace pmg
 
-extern "C" int pmg_laplacian_create_ordered(
+// The one constructor: every pmg_laplacian_create_* ends here (the trilinear ones with geom_degree = 1)
+extern "C" int pmg_laplacian_create_curved(
     pmg_laplacian* out, pmg_layout layout, int degree, int32_t ncells, const double* kappa,
-    const int32_t* dofmap, const double* xgeom, int32_t npoints, const int32_t* geom_dofmap,
+    const int32_t* dofmap, const double* xgeom, int32_t npoints, int geom_degree, const int32_t* geom_dofmap,
     const double* dphi_geometry, const double* G_weights, const int32_t* lcells, int32_t n_lcells,
     const int32_t* bcells, int32_t n_bcells, const int8_t* bc_marker, int node_order, const int32_t* custom_perm1d,
     pmg_stream stream)
 {
-  PMG_REQUIRE(out && layout, "pmg_laplacian_create: NULL handle");
+  PMG_REQUIRE(out, "pmg_laplacian_create: NULL handle");
+  *out = nullptr;
+  PMG_REQUIRE(layout, "pmg_laplacian_create: NULL handle");
   if (degree < 1 || degree > PMG_MAX_DEGREE)
     return fail(PMG_ERR_INVALID, "Unsupported degree"); // src/laplacian.hpp:346
+  PMG_REQUIRE(geom_degree >= 1 && geom_degree <= PMG_MAX_GEOM_DEGREE,
+              "pmg_laplacian_create: geometry degree %d outside 1..%d", geom_degree, PMG_MAX_GEOM_DEGREE);
+  PMG_REQUIRE((dphi_geometry != nullptr) == (G_weights != nullptr) || geom_degree == 1,
+              "pmg_laplacian_create: dphi_geometry and G_weights are both given or both NULL");
+  const int g = geom_degree, gm = g + 1, ng = gm * gm * gm;
   PMG_REQUIRE(ncells >= 0 && n_lcells >= 0 && n_bcells >= 0 && n_lcells + n_bcells <= ncells,
               "pmg_laplacian_create: cell lists (%d + %d) exceed ncells (%d)", n_lcells, n_bcells,
               ncells);
@@ -452,47 +476,45 @@ extern "C" int pmg_laplacian_create_ordered(
   lagrange_derivative_table(nd, pts.data(), D.data());
   PMG_TRY(upload(&op->D, D.data(), D.size(), s));
 
-  // trilinear coordinate-element derivatives at the GLL points, [3][N][8], and
+  // coordinate-element derivatives at the GLL points, [3][N][ng] (ng = 8: the trilinear element), and
   // the 3-D weights (examples/pmg/main.cpp:216-238)
+  op->geom_degree = g;
+  op->ng = ng;
   if (dphi_geometry && G_weights)
   {
-    PMG_HIP(hipMalloc(&op->dphi_geom, sizeof(double) * 24 * N));
+    PMG_HIP(hipMalloc(&op->dphi_geom, sizeof(double) * 3 * ng * N));
     PMG_HIP(hipMalloc(&op->gweights, sizeof(double) * N));
     if (op->qperm) // the caller's tables are indexed by ITS quadrature-point numbers
     {
-      PMG_TRY(permute_rows_f64(3, N, 8, op->qperm, dphi_geometry, op->dphi_geom, s));
+      PMG_TRY(permute_rows_f64(3, N, ng, op->qperm, dphi_geometry, op->dphi_geom, s));
       PMG_TRY(permute_rows_f64(1, N, 1, op->qperm, G_weights, op->gweights, s));
     }
     else
     {
-      PMG_HIP(hipMemcpyAsync(op->dphi_geom, dphi_geometry, sizeof(double) * 24 * N,
+      PMG_HIP(hipMemcpyAsync(op->dphi_geom, dphi_geometry, sizeof(double) * 3 * ng * N,
                              hipMemcpyDeviceToDevice, s));
       PMG_HIP(hipMemcpyAsync(op->gweights, G_weights, sizeof(double) * N, hipMemcpyDeviceToDevice, s));
     }
   }
   else
   {
-    std::vector<double> dphi(24 * (size_t)N), w3(N);
+    // the element's 1-D basis and derivative at the GLL points, L / Lp [nd][g + 1]; the dense table is their product
+    std::vector<double> L((size_t)nd * gm), Lp((size_t)nd * gm), dphi((size_t)3 * ng * N), w3(N);
+    coordinate_element_tables_1d(nd, pts.data(), g, L.data(), Lp.data());
+    coordinate_element_table_3d(nd, gm, L.data(), Lp.data(), dphi.data());
     for (int a = 0; a < nd; ++a)
       for (int b = 0; b < nd; ++b)
         for (int c = 0; c < nd; ++c)
-        {
-          int q = (a * nd + b) * nd + c;
-          w3[q] = wts[a] * wts[b] * wts[c];
-          double ph[3][2] = {{1.0 - pts[a], pts[a]}, {1.0 - pts[b], pts[b]}, {1.0 - pts[c], pts[c]}};
-          const double dp[2] = {-1.0, 1.0};
-          for (int i = 0; i < 2; ++i)
-            for (int j = 0; j < 2; ++j)
-              for (int k = 0; k < 2; ++k)
-              {
-                int v = i * 4 + j * 2 + k;
-                dphi[((size_t)0 * N + q) * 8 + v] = dp[i] * ph[1][j] * ph[2][k];
-                dphi[((size_t)1 * N + q) * 8 + v] = ph[0][i] * dp[j] * ph[2][k];
-                dphi[((size_t)2 * N + q) * 8 + v] = ph[0][i] * ph[1][j] * dp[k];
-              }
-        }
+          w3[(a * nd + b) * nd + c] = wts[a] * wts[b] * wts[c];
     PMG_TRY(upload(&op->dphi_geom, dphi.data(), dphi.size(), s));
     PMG_TRY(upload(&op->gweights, w3.data(), w3.size(), s));
+    if (g >= 2) // the cell-cooperative geometry kernel contracts with the 1-D tables (curved_geometry.hpp)
+    {
+      PMG_REQUIRE(curved_lds_bytes(nd, gm) <= 64 * 1024, "internal: the curved geometry kernel needs %zu bytes of LDS",
+                  curved_lds_bytes(nd, gm));
+      PMG_TRY(upload(&op->geom_L, L.data(), L.size(), s));
+      PMG_TRY(upload(&op->geom_Lp, Lp.data(), Lp.size(), s));
+    }
     PMG_HIP(hipStreamSynchronize(s)); // host vectors go out of scope
   }
 
@@ -500,7 +522,7 @@ extern "C" int pmg_laplacian_create_ordered(
   PatchPlan plan;
   ChainPlan cplan;
   {
-    std::vector<int32_t> h_dofmap((size_t)ncells * N), h_gd((size_t)ncells * 8);
+    std::vector<int32_t> h_dofmap((size_t)ncells * N), h_gd((size_t)ncells * ng);
     std::vector<int8_t> h_bc(total);
     std::vector<double> h_x((size_t)npoints * 3);
     PMG_HIP(hipMemcpyAsync(h_dofmap.data(), dofmap, sizeof(int32_t) * h_dofmap.size(),
@@ -511,22 +533,29 @@ extern "C" int pmg_laplacian_create_ordered(
                            hipMemcpyDeviceToHost, s));
     PMG_HIP(hipMemcpyAsync(h_x.data(), xgeom, sizeof(double) * h_x.size(), hipMemcpyDeviceToHost, s));
     PMG_HIP(hipStreamSynchronize(s));
-    std::vector<float> centroid((size_t)ncells * 3);
+    for (size_t i = 0; i < h_gd.size(); ++i) // all (g+1)^3 nodes of every cell
+      PMG_REQUIRE(h_gd[i] >= 0 && h_gd[i] < npoints, "pmg_laplacian_create: geometry dofmap entry %d out of range",
+                  h_gd[i]);
+    // the 8 corner nodes of a cell, k = i*4 + j*2 + l, at their tensor positions among the (g+1)^3
+    int corner[8];
+    for (int k = 0; k < 8; ++k)
+      corner[k] = (((k >> 2) & 1) * g * gm + ((k >> 1) & 1) * g) * gm + (k & 1) * g;
+    std::vector<float> centroid((size_t)ncells * 3); // mean of the corners
     for (int32_t c = 0; c < ncells; ++c)
       for (int a = 0; a < 3; ++a)
       {
         double v = 0;
         for (int k = 0; k < 8; ++k)
-        {
-          int32_t g = h_gd[(size_t)c * 8 + k];
-          PMG_REQUIRE(g >= 0 && g < npoints, "pmg_laplacian_create: geometry dofmap entry %d out of range", g);
-          v += h_x[3 * (size_t)g + a];
-        }
+          v += h_x[3 * (size_t)h_gd[(size_t)c * ng + corner[k]] + a];
         centroid[(size_t)c * 3 + a] = (float)(v * 0.125);
       }
     PMG_TRY(build_patch_plan(plan, degree, ncells, h_dofmap.data(), h_bc.data(), total,
                              centroid.data(), lcells, n_lcells, bcells, n_bcells));
-    // affine (parallelepiped) cells: vertex (i,j,l) = x0 + i e1 + j e2 + l e3
+    // affine (parallelepiped) cells: node (i,j,l) = x0 + xi_i e1 + xi_j e2 + xi_l e3 with the edges e1, e2, e3 from the
+    // corner x0 and xi the element's 1-D nodes -- every one of the (g+1)^3 nodes, so a cell with parallelepiped corners
+    // and a displaced mid-edge node is not affine
+    std::vector<double> xi(gm), xiw(gm);
+    gll_table(gm, xi.data(), xiw.data());
     op->all_affine = (n_lcells + n_bcells) > 0;
     for (int set = 0; set < 2 && op->all_affine; ++set)
     {
@@ -534,17 +563,24 @@ extern "C" int pmg_laplacian_create_ordered(
       const int n = set ? n_bcells : n_lcells;
       for (int i = 0; i < n && op->all_affine; ++i)
       {
-        const int32_t* gd = h_gd.data() + (size_t)list[i] * 8;
+        const int32_t* gd = h_gd.data() + (size_t)list[i] * ng;
         const double* v[8];
         for (int k = 0; k < 8; ++k)
-          v[k] = h_x.data() + 3 * (size_t)gd[k];
+          v[k] = h_x.data() + 3 * (size_t)gd[corner[k]];
         double diam = 0, dev = 0;
         for (int a = 0; a < 3; ++a)
         {
           const double e1 = v[4][a] - v[0][a], e2 = v[2][a] - v[0][a], e3 = v[1][a] - v[0][a];
           diam += std::fabs(e1) + std::fabs(e2) + std::fabs(e3);
-          dev += std::fabs(v[3][a] - (v[0][a] + e2 + e3)) + std::fabs(v[5][a] - (v[0][a] + e1 + e3))
-                 + std::fabs(v[6][a] - (v[0][a] + e1 + e2)) + std::fabs(v[7][a] - (v[0][a] + e1 + e2 + e3));
+          if (g == 1)
+            dev += std::fabs(v[3][a] - (v[0][a] + e2 + e3)) + std::fabs(v[5][a] - (v[0][a] + e1 + e3))
+                   + std::fabs(v[6][a] - (v[0][a] + e1 + e2)) + std::fabs(v[7][a] - (v[0][a] + e1 + e2 + e3));
+          else
+            for (int ni = 0; ni < gm; ++ni)
+              for (int nj = 0; nj < gm; ++nj)
+                for (int nl = 0; nl < gm; ++nl)
+                  dev += std::fabs(h_x[3 * (size_t)gd[(ni * gm + nj) * gm + nl] + a]
+                                   - (v[0][a] + xi[ni] * e1 + xi[nj] * e2 + xi[nl] * e3));
         }
         if (dev > 1e-12 * diam)
           op->all_affine = false;
@@ -614,7 +650,7 @@ extern "C" int pmg_laplacian_create_ordered(
   PMG_TRY(upload(&op->W1, wts.data(), wts.size(), s));
   PMG_HIP(hipMalloc(&op->Gaff, sizeof(double) * 6 * (nslots ? nslots : 1)));
   if (nslots > 0)
-    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->pcell, xgeom,
+    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, g, op->pcell, xgeom,
                                                                            geom_dofmap, nullptr, op->Gaff);
   {
     const size_t gsize = (size_t)op->npatch * gpatch(nd, op->K);
@@ -634,6 +670,20 @@ extern "C" int pmg_laplacian_create_ordered(
   *out = guard.release();
   return PMG_OK;
 }
+
+extern "C" int pmg_laplacian_create_ordered(
+    pmg_laplacian* out, pmg_layout layout, int degree, int32_t ncells, const double* kappa,
+    const int32_t* dofmap, const double* xgeom, int32_t npoints, const int32_t* geom_dofmap,
+    const double* dphi_geometry, const double* G_weights, const int32_t* lcells, int32_t n_lcells,
+    const int32_t* bcells, int32_t n_bcells, const int8_t* bc_marker, int node_order, const int32_t* custom_perm1d,
+    pmg_stream stream)
+{
+  return pmg_laplacian_create_curved(out, layout, degree, ncells, kappa, dofmap, xgeom, npoints, 1, geom_dofmap,
+                                     dphi_geometry, G_weights, lcells, n_lcells, bcells, n_bcells, bc_marker,
+                                     node_order, custom_perm1d, stream);
+}
+
+extern "C" int pmg_laplacian_geometry_degree(pmg_laplacian op) { return op ? op->geom_degree : -1; }
 
 extern "C" int pmg_laplacian_create_with_tables(
     pmg_laplacian* out, pmg_layout layout, int degree, int32_t ncells, const double* kappa,
@@ -677,6 +727,8 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->react32_buf);
   (void)hipFree(op->W1);
   (void)hipFree(op->dphi_geom);
+  (void)hipFree(op->geom_L);
+  (void)hipFree(op->geom_Lp);
   (void)hipFree(op->gweights);
   (void)hipFree(op->pcell);
   (void)hipFree(op->pncell);
@@ -934,8 +986,9 @@ extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const doub
     batch_geometry(op, 0, op->npatch, s);
   const long long nslots = (long long)op->npatch * op->K;
   if (nslots > 0)
-    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->pcell, op->xgeom,
-                                                                           op->geom_dofmap, op->ktensor, op->Gaff);
+    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->geom_degree, op->pcell,
+                                                                           op->xgeom, op->geom_dofmap, op->ktensor,
+                                                                           op->Gaff);
   PMG_HIP(hipGetLastError());
   PMG_TRY(laplacian_f32_refresh(op, s));
   if (op->have_diag && op->diag_computed)
@@ -1049,7 +1102,7 @@ extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma,
     PMG_HIP(hipMemsetAsync(op->sigma_buf, 0, sizeof(double) * (total ? total : 1), s));
     const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
     if (n > 0)
-      reaction_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->N, op->pcell, op->xgeom, op->geom_dofmap,
+      reaction_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->N, op->ng, op->pcell, op->xgeom, op->geom_dofmap,
                                                                  op->dphi_geom, op->gweights, op->dofmap, op->bc,
                                                                  sigma, op->sigma_buf);
     PMG_HIP(hipGetLastError());
@@ -1097,7 +1150,7 @@ extern "C" int pmg_laplacian_assemble_rhs(pmg_laplacian op, const double* f, dou
   const long long nslots = (long long)op->npatch * op->K;
   const long long n = nslots * op->N;
   if (n > 0)
-    rhs_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->N, op->pcell, op->xgeom,
+    rhs_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->N, op->ng, op->pcell, op->xgeom,
                                                           op->geom_dofmap, op->dphi_geom,
                                                           op->gweights, op->dofmap, op->bc,
                                                           op->kappa, f, b);

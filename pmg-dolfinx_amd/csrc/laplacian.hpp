@@ -56,7 +56,14 @@ struct pmg_laplacian_s
   bool all_affine = false;     // every listed cell is a parallelepiped
   int geometry_mode = 0;       // 0 = stored G (reference data structure), 1 = affine cells
   double* D = nullptr;         // [nd*nd]
-  double* dphi_geom = nullptr; // [3][N][8]
+  double* dphi_geom = nullptr; // [3][N][ng]
+  // coordinate element (pmg_laplacian_create_curved): tensor-product Lagrange of degree geom_degree, ng = (g + 1)^3
+  // nodes per cell in ascending tensor order.  geom_L / geom_Lp [nd][g + 1]: its 1-D basis and derivative at the
+  // operator's GLL points, present when the library built the tabulation itself and g >= 2 -- the cell-cooperative
+  // geometry kernel contracts with them (curved_geometry.hpp); nullptr with caller tables (per-point dense path).
+  int geom_degree = 1, ng = 8;
+  double* geom_L = nullptr;
+  double* geom_Lp = nullptr;
   double* gweights = nullptr;  // [N]
   int32_t* pcell = nullptr;    // [npatch*K]
   int32_t* pncell = nullptr;   // [npatch]
@@ -175,6 +182,21 @@ int walk_launches(pmg_laplacian op, int l0, int l1, ApplyForm form, hipStream_t 
   return PMG_OK;
 }
 
+// adj(J) and |det J| of a Jacobian formed elsewhere (the degree-g paths), as jacobian() below forms them
+__device__ __forceinline__ void adjugate(const double J[3][3], double K[3][3], double& detJ)
+{
+  K[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+  K[0][1] = -J[0][1] * J[2][2] + J[0][2] * J[2][1];
+  K[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+  K[1][0] = -J[1][0] * J[2][2] + J[1][2] * J[2][0];
+  K[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+  K[1][2] = -J[0][0] * J[1][2] + J[0][2] * J[1][0];
+  K[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+  K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
+  K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+  detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]);
+}
+
 // ---- geometry: J, adj(J), |det| at one quadrature point (src/laplacian.hpp:72-97) ----
 __device__ inline void jacobian(const double* __restrict__ xgeom,
                                 const int32_t* __restrict__ gdofs, const double* __restrict__ dphi,
@@ -211,6 +233,33 @@ __device__ inline void jacobian(const double* __restrict__ xgeom,
   // mesh); the volume measure, G, the load and the reaction weights do not depend on it.  K keeps its sign: it enters
   // G twice and the facet measure through a norm.  (fabs changes no bit of a positive determinant.)
   detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]);
+}
+
+// The same for a coordinate element of `ng` nodes per cell (dense table [3][nq][ng], gdofs = the cell's ng nodes).  The
+// trilinear element keeps its own code above: ng == 8 goes there, so a degree-1 operator computes what it always did.
+__device__ inline void jacobian(const double* __restrict__ xgeom, const int32_t* __restrict__ gdofs,
+                                const double* __restrict__ dphi, int nq, int q, int ng, double K[3][3], double& detJ)
+{
+  if (ng == 8)
+    return jacobian(xgeom, gdofs, dphi, nq, q, K, detJ);
+  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  const double *t0 = dphi + (size_t)q * ng, *t1 = t0 + (size_t)nq * ng, *t2 = t1 + (size_t)nq * ng;
+  for (int k = 0; k < ng; ++k)
+  {
+    const double* xk = xgeom + 3 * (size_t)gdofs[k];
+    const double x0 = xk[0], x1 = xk[1], x2 = xk[2];
+    const double d0 = t0[k], d1 = t1[k], d2 = t2[k];
+    J[0][0] += x0 * d0;
+    J[0][1] += x0 * d1;
+    J[0][2] += x0 * d2;
+    J[1][0] += x1 * d0;
+    J[1][1] += x1 * d1;
+    J[1][2] += x1 * d2;
+    J[2][0] += x2 * d0;
+    J[2][1] += x2 * d1;
+    J[2][2] += x2 * d2;
+  }
+  adjugate(J, K, detJ);
 }
 
 // ---- the six entries of adj(J) T adj(J)^T * s for a symmetric T = (xx, xy, xz, yy, yz, zz) in physical coordinates:

@@ -20,6 +20,7 @@
 // every degree run eight wavefronts per workgroup where it has the items (P = 6: 49 of 64 lanes, P = 7: 64 of 64),
 // and P = 5 / P = 8 share one item of 7 / 3 cells between four wavefronts as the FP64 kernel does.
 #include "laplacian.hpp"
+#include "curved_geometry.hpp"
 #include "stiffness_layer.hpp"
 
 #include <algorithm>
@@ -99,6 +100,22 @@ __global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __r
   o[nsq] = make_float2((float)g[2], (float)g[3]);
   o[2 * nsq] = make_float2((float)g[4], (float)g[5]);
 }
+
+// the float tensor's layout for the degree-g geometry kernels (curved_geometry.hpp): the one rounding
+struct TensorOut32
+{
+  float2* G;
+  int nd;
+  __device__ __forceinline__ void operator()(long long slot, int q, const double g[6]) const
+  {
+    const int nsq = nd * nd, nq = nsq * nd;
+    const int a = q / nsq, b = (q - a * nsq) / nd, cc = q - a * nsq - b * nd;
+    float2* o = G + (size_t)slot * 3 * nq + (size_t)cc * 3 * nsq + a * nd + b;
+    o[0] = make_float2((float)g[0], (float)g[1]);
+    o[nsq] = make_float2((float)g[2], (float)g[3]);
+    o[2 * nsq] = make_float2((float)g[4], (float)g[5]);
+  }
+};
 
 template <int P, bool NT>
 __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
@@ -317,7 +334,9 @@ int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s)
   if (!op->G32)
     return PMG_OK;
   const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
-  if (n > 0)
+  if (op->ng != 8) // a coordinate element of degree >= 2: the FP64 tensor's routine, rounded at the end
+    launch_curved_geometry(op, 0, nslots, TensorOut32{op->G32, op->nd}, s);
+  else if (n > 0)
     geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
                                                                     op->geom_dofmap, op->dphi_geom, op->gweights,
                                                                     op->kfield, op->dofmap, op->ktensor,

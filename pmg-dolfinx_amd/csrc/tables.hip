@@ -158,6 +158,68 @@ void lagrange_eval_table(int nc, const double* xc, int nf, const double* xf, dou
     }
 }
 
+// ---- coordinate element (pmg_amd.h "coordinate element"): tensor-product Lagrange of degree g on the GLL nodes of
+// degree g.  L[q*(g+1) + i] = l_i(x_q), Lp = l_i'(x_q) at the n points x.  g = 1 is written out, 1 - x, x and -1, 1:
+// the trilinear tables the library has always built, to the bit. ----
+void coordinate_element_tables_1d(int n, const double* x, int g, double* L, double* Lp)
+{
+  const int m = g + 1;
+  if (g == 1)
+  {
+    for (int q = 0; q < n; ++q)
+    {
+      L[2 * q] = 1.0 - x[q];
+      L[2 * q + 1] = x[q];
+      Lp[2 * q] = -1.0;
+      Lp[2 * q + 1] = 1.0;
+    }
+    return;
+  }
+  std::vector<double> xi(m), wi(m);
+  gll_table(m, xi.data(), wi.data());
+  for (int q = 0; q < n; ++q)
+    for (int i = 0; i < m; ++i)
+    {
+      long double v = 1.0L, d = 0.0L;
+      for (int k = 0; k < m; ++k)
+        if (k != i)
+          v *= ((long double)x[q] - (long double)xi[k]) / ((long double)xi[i] - (long double)xi[k]);
+      for (int j = 0; j < m; ++j) // l_i' = sum_j 1 / (xi_i - xi_j) prod_{k != i, j} (x - xi_k) / (xi_i - xi_k)
+      {
+        if (j == i)
+          continue;
+        long double t = 1.0L / ((long double)xi[i] - (long double)xi[j]);
+        for (int k = 0; k < m; ++k)
+          if (k != i && k != j)
+            t *= ((long double)x[q] - (long double)xi[k]) / ((long double)xi[i] - (long double)xi[k]);
+        d += t;
+      }
+      L[q * m + i] = (double)v;
+      Lp[q * m + i] = (double)d;
+    }
+}
+
+// dphi[3][nd^3][m^3] from the 1-D tables: q = (a nd + b) nd + c, k = (i m + j) m + l, both ascending
+void coordinate_element_table_3d(int nd, int m, const double* L, const double* Lp, double* dphi)
+{
+  const size_t N = (size_t)nd * nd * nd, ng = (size_t)m * m * m;
+  for (int a = 0; a < nd; ++a)
+    for (int b = 0; b < nd; ++b)
+      for (int c = 0; c < nd; ++c)
+      {
+        const size_t q = ((size_t)a * nd + b) * nd + c;
+        for (int i = 0; i < m; ++i)
+          for (int j = 0; j < m; ++j)
+            for (int l = 0; l < m; ++l)
+            {
+              const size_t k = ((size_t)i * m + j) * m + l;
+              dphi[(0 * N + q) * ng + k] = Lp[a * m + i] * L[b * m + j] * L[c * m + l];
+              dphi[(1 * N + q) * ng + k] = L[a * m + i] * Lp[b * m + j] * L[c * m + l];
+              dphi[(2 * N + q) * ng + k] = L[a * m + i] * L[b * m + j] * Lp[c * m + l];
+            }
+      }
+}
+
 // ---- cell-local node order (pmg_amd.h) ----
 int node_permutation(int node_order, int degree, const int32_t* custom, std::vector<int32_t>& perm1d)
 {
@@ -331,6 +393,30 @@ extern "C" int pmg_interpolation_table_ordered(int p_coarse, int p_fine, int nod
   for (int j = 0; j < nf; ++j)
     for (int k = 0; k < nc; ++k)
       M[j * nc + k] = Ma[(size_t)pf[j] * nc + pc[k]];
+  return PMG_OK;
+}
+
+extern "C" int pmg_coordinate_element_table(int degree, int geom_degree, int node_order, const int32_t* custom_perm1d,
+                                            double* dphi)
+{
+  PMG_REQUIRE(dphi, "pmg_coordinate_element_table: NULL output");
+  PMG_REQUIRE(degree >= 1 && degree <= PMG_MAX_DEGREE, "pmg_coordinate_element_table: degree %d outside 1..%d", degree,
+              PMG_MAX_DEGREE);
+  PMG_REQUIRE(geom_degree >= 1 && geom_degree <= PMG_MAX_GEOM_DEGREE,
+              "pmg_coordinate_element_table: geometry degree %d outside 1..%d", geom_degree, PMG_MAX_GEOM_DEGREE);
+  std::vector<int32_t> p;
+  PMG_TRY(node_permutation(node_order, degree, custom_perm1d, p));
+  const int nd = degree + 1, m = geom_degree + 1;
+  const size_t N = (size_t)nd * nd * nd, ng = (size_t)m * m * m;
+  std::vector<double> x(nd), w(nd), L((size_t)nd * m), Lp((size_t)nd * m), asc(3 * N * ng);
+  gll_table(nd, x.data(), w.data());
+  coordinate_element_tables_1d(nd, x.data(), geom_degree, L.data(), Lp.data());
+  coordinate_element_table_3d(nd, m, L.data(), Lp.data(), asc.data());
+  const std::vector<int32_t> p3 = cell_permutation(nd, p); // the caller's point number -> ascending
+  for (int d = 0; d < 3; ++d)
+    for (size_t qc = 0; qc < N; ++qc)
+      for (size_t k = 0; k < ng; ++k)
+        dphi[(d * N + qc) * ng + k] = asc[(d * N + (size_t)p3[qc]) * ng + k];
   return PMG_OK;
 }
 

@@ -81,7 +81,10 @@ class MatFreeLaplacian:
 
     def __init__(self, degree, coefficients, dofmap, xgeom, geometry_dofmap, lcells, bcells, bc_marker,
                  layout: Layout, batch_size: int = 0, node_order="ascending", perm1d=None, dphi_geometry=None,
-                 G_weights=None):
+                 G_weights=None, geometry_degree: int = 1):
+        """``geometry_degree`` g (1..4): the coordinate element is the tensor-product Lagrange element of degree g on
+        the GLL nodes; ``geometry_dofmap`` is ``[ncells, (g+1)^3]`` in ascending tensor order (``include/pmg_amd.h``,
+        "curved cells") and ``dphi_geometry``, when given, ``[3, nq, (g+1)^3]``."""
         if batch_size != 0:
             # src/laplacian.hpp:391-396 recomputes G per batch to save memory; with
             # 288 GB of HBM the tensor is always resident.
@@ -95,7 +98,18 @@ class MatFreeLaplacian:
         self.kappa = _dev_f64(np.broadcast_to(np.asarray(coefficients, dtype=np.float64), (self.ncells,)).copy()
                               if not hasattr(coefficients, "data_ptr") else coefficients, dev)
         self.xgeom = _dev_f64(xgeom, dev)
+        self.geom_degree = int(geometry_degree)
+        if not 1 <= self.geom_degree <= 4:
+            raise ValueError(f"geometry_degree {geometry_degree} outside 1..4")
+        ng = (self.geom_degree + 1) ** 3
         self.geom_dofmap = _dev_i32(geometry_dofmap, dev)
+        supported = 1 <= self.degree <= 8  # (any other degree is the library's to refuse: "Unsupported degree")
+        if supported and self.geom_dofmap.numel() != self.ncells * ng:
+            raise ValueError(f"geometry_dofmap has {self.geom_dofmap.numel()} entries, {self.ncells} cells of geometry "
+                             f"degree {self.geom_degree} need {self.ncells * ng}")
+        if supported and dphi_geometry is not None and int(np.prod(tuple(dphi_geometry.shape))) != 3 * N * ng:
+            raise ValueError(f"dphi_geometry has {int(np.prod(tuple(dphi_geometry.shape)))} entries, degree "
+                             f"{self.degree} with geometry degree {self.geom_degree} needs {3 * N * ng}")
         self.bc_marker = _dev_i8(bc_marker, dev)
         if self.bc_marker.numel() != layout.total:
             raise ValueError("bc_marker must have size_local + num_ghosts entries")
@@ -109,8 +123,8 @@ class MatFreeLaplacian:
         self.G_weights = _dev_f64(G_weights, dev) if G_weights is not None else None
         if (self.dphi_geometry is None) != (self.G_weights is None):
             raise ValueError("dphi_geometry and G_weights come together (src/laplacian.hpp:293-294)")
-        call("pmg_laplacian_create_ordered", C.byref(h), layout.handle, self.degree, self.ncells, ptr(self.kappa),
-             ptr(self.dofmap), ptr(self.xgeom), int(self.xgeom.numel() // 3), ptr(self.geom_dofmap),
+        call("pmg_laplacian_create_curved", C.byref(h), layout.handle, self.degree, self.ncells, ptr(self.kappa),
+             ptr(self.dofmap), ptr(self.xgeom), int(self.xgeom.numel() // 3), self.geom_degree, ptr(self.geom_dofmap),
              ptr(self.dphi_geometry), ptr(self.G_weights),
              lc.ctypes.data_as(_lib.c_ip), lc.size, bc_.ctypes.data_as(_lib.c_ip), bc_.size, ptr(self.bc_marker),
              self.node_order, perm.ctypes.data_as(_lib.c_ip) if perm is not None else None, current_stream())
@@ -119,6 +133,10 @@ class MatFreeLaplacian:
     @property
     def handle(self):
         return self._handle
+
+    def geometry_degree(self) -> int:
+        """Degree of the coordinate element the operator was created with (``pmg_laplacian_geometry_degree``)."""
+        return int(call("pmg_laplacian_geometry_degree", self._handle))
 
     def __call__(self, x: Vector, y: Vector):  # operator()(in, out), :462-482
         call("pmg_laplacian_apply", self._handle, ptr(x.data), ptr(y.data), current_stream())

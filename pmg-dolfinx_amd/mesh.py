@@ -91,6 +91,22 @@ def dofmap_in_node_order(dofmap: np.ndarray, perm1d) -> np.ndarray:
     return np.ascontiguousarray(dofmap[:, cell_permutation(perm1d)])
 
 
+def coordinate_element_table(P: int, g: int, node_order="ascending", perm1d=None) -> np.ndarray:
+    """``dphi_geometry`` [3, (P+1)^3, (g+1)^3] of the degree-g coordinate element at the GLL points of degree ``P``
+    (``pmg_coordinate_element_table``: host arithmetic, no GPU): rows q in ``node_order``, nodes k in ascending tensor
+    order -- the table the library builds for itself."""
+    from . import _lib
+    from .laplacian import node_order_args
+
+    if not (1 <= int(P) <= 8 and 1 <= int(g) <= 4):
+        raise ValueError("coordinate_element_table: degree outside 1..8 or geometry degree outside 1..4")
+    code, perm = node_order_args(node_order, int(P), perm1d)
+    out = np.empty((3, (P + 1) ** 3, (g + 1) ** 3))
+    _lib.call("pmg_coordinate_element_table", int(P), int(g), code,
+              perm.ctypes.data_as(_lib.c_ip) if perm is not None else None, out.ctypes.data_as(_lib.c_dp))
+    return out
+
+
 def facet_nodes(P: int, local_facet: int) -> np.ndarray:
     """The nd*nd ascending cell-local node numbers t = a*nd^2 + b*nd + c of the face ``local_facet`` = 2 * axis + side
     (side 0: xi_axis = 0, side 1: xi_axis = 1), in the order of the facet points of ``assemble_neumann``:
@@ -177,7 +193,10 @@ class BoxPartition:
     (frame 0 everywhere: local axes = global axes)."""
 
     def __init__(self, n, proc_dims=(1, 1, 1), rank=0, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), warp=None,
-                 cell_frames=None):
+                 cell_frames=None, geom_degree=1):
+        self.geom_degree = int(geom_degree)
+        if not 1 <= self.geom_degree <= 4:
+            raise ValueError("geom_degree outside 1..4")
         if np.isscalar(n):
             n = (int(n),) * 3
         self.n = tuple(int(v) for v in n)
@@ -207,20 +226,23 @@ class BoxPartition:
         self.ncells_owned = int(owned.sum())
         self.ncells = int(order.size)
 
-        # geometry: vertices of the extended brick, lexicographic
-        vshape = [h - l + 1 for l, h in self.ext]
-        g = [np.linspace(lo[a], hi[a], self.n[a] + 1)[self.ext[a][0]: self.ext[a][1] + 1] for a in range(3)]
+        # geometry: the coordinate element's nodes of the extended brick, lexicographic, shared nodes stored once
+        # (degree 1: the vertices); `warp` is evaluated at them
+        gdeg, gm = self.geom_degree, self.geom_degree + 1
+        vshape = [(h - l) * gdeg + 1 for l, h in self.ext]
+        g = [self._node_line(a)[self.ext[a][0] * gdeg: self.ext[a][1] * gdeg + 1] for a in range(3)]
         X, Y, Z = np.meshgrid(*g, indexing="ij")
         x = np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1)
         if warp is not None:
             x = warp(x)
         self.xgeom = np.ascontiguousarray(x, dtype=np.float64)
-        lc = self.cell_coords - np.array([self.ext[a][0] for a in range(3)])
-        gd = np.empty((self.ncells, 8), dtype=np.int32)
-        for i in range(2):
-            for j in range(2):
-                for k in range(2):
-                    gd[:, i * 4 + j * 2 + k] = ((lc[:, 0] + i) * vshape[1] + (lc[:, 1] + j)) * vshape[2] + lc[:, 2] + k
+        lc = (self.cell_coords - np.array([self.ext[a][0] for a in range(3)])) * gdeg
+        gd = np.empty((self.ncells, gm**3), dtype=np.int32)
+        for i in range(gm):
+            for j in range(gm):
+                for k in range(gm):
+                    gd[:, (i * gm + j) * gm + k] = (((lc[:, 0] + i) * vshape[1] + (lc[:, 1] + j)) * vshape[2]
+                                                   + lc[:, 2] + k)
         # local frames: one symmetry index per local cell, looked up by global cell coordinates
         self.cell_frames = None
         if cell_frames is not None:
@@ -229,9 +251,39 @@ class BoxPartition:
                 raise ValueError("cell_frames: an integer array of shape n with values 0..47")
             cc = self.cell_coords
             self.cell_frames = fr[cc[:, 0], cc[:, 1], cc[:, 2]].astype(np.int64)
-            gd = self._reframe(gd, 1)
+            gd = self._reframe(gd, gdeg)
         self.geom_dofmap = gd
         self._levels = {}
+
+    def _node_line(self, axis):
+        """Reference-box coordinates of the GLOBAL geometry nodes along one axis: the degree-g GLL nodes of every
+        cell, n * g + 1 values (degree 1: the vertices)."""
+        v = np.linspace(self.lo[axis], self.hi[axis], self.n[axis] + 1)
+        if self.geom_degree == 1:
+            return v
+        from ._tables import gll_points
+
+        xi = gll_points(self.geom_degree + 1)[:-1]
+        line = (v[:-1, None] + xi[None, :] * (v[1:, None] - v[:-1, None])).ravel()
+        return np.concatenate([line, v[-1:]])
+
+    def _cell_basis(self, P):
+        """[nd^3, (g+1)^3]: the coordinate element's basis at the GLL points of degree P, both in ascending tensor
+        order."""
+        from ._tables import gll_points
+
+        nd = P + 1
+        xi = gll_points(nd)
+        if self.geom_degree == 1:
+            phi = np.stack([1.0 - xi, xi], axis=1)
+        else:
+            nodes = gll_points(self.geom_degree + 1)
+            phi = np.ones((nd, nodes.size))
+            for k in range(nodes.size):
+                for m in range(nodes.size):
+                    if m != k:
+                        phi[:, k] *= (xi - nodes[m]) / (nodes[k] - nodes[m])
+        return np.einsum("ai,bj,cl->abcijl", phi, phi, phi).reshape(nd**3, phi.shape[1] ** 3)
 
     def _reframe(self, rows, P):
         """Rows [ncells, (P+1)^3] of cell-local node data, listed in every cell's own frame."""
@@ -384,17 +436,14 @@ class BoxPartition:
         return coords[dm[cells[:, None], nodes[local_facets]]]
 
     def dof_coordinates(self, P: int) -> np.ndarray:
-        """Physical coordinates of the local dofs [ndofs_local, 3]: trilinear image
-        of the reference GLL nodes of each cell."""
-        from ._tables import gll_points
-
+        """Physical coordinates of the local dofs [ndofs_local, 3]: image of the reference GLL nodes of each cell under
+        the cell's degree-g map (trilinear for ``geom_degree`` 1).  ``warp`` itself is not evaluated, so manufactured
+        data sits on the discrete geometry."""
         lv = self.level(P)
         if lv.dof_coords is not None:
             return lv.dof_coords
         nd = P + 1
-        xi = gll_points(nd)
-        phi = np.stack([1.0 - xi, xi], axis=1)
-        N = np.einsum("ai,bj,cl->abcijl", phi, phi, phi).reshape(nd**3, 8)
+        N = self._cell_basis(P)  # (a re-framed cell lists its geometry nodes and its dofs in the same frame)
         out = np.zeros((lv.ndofs, 3))
         step = max(1, 4_000_000 // (nd**3))
         for s in range(0, self.ncells, step):

@@ -26,7 +26,7 @@ class PoissonHierarchy:
     def __init__(self, n, orders=(1, 2, 4), kappa=2.0, cheb_its=3, proc_dims=None, rank=0, size=1, group=None,
                  warp=None, eig_cg_its=20, eig_cg_rtol=1e-6, freq=(2, 3, 4), device="cuda", comm=None,
                  node_order="ascending", level_hook=None, assembled_levels=(), kappa_field=None, dirichlet=None,
-                 kappa_tensor=None, reaction=None, robin=None, cell_frames=None, part=None):
+                 kappa_tensor=None, reaction=None, robin=None, cell_frames=None, part=None, geom_degree=1):
         """``kappa_field`` (optional): a callable mapping dof coordinates ``[n, 3]`` to positive nodal values of a
         variable coefficient; it is evaluated on every level at that level's dof coordinates and set on the level's
         operator (``MatFreeLaplacian.set_coefficient_field``) before the diagonal and the eigenvalue estimate.  The
@@ -61,15 +61,24 @@ class PoissonHierarchy:
         ``part`` (optional): this rank's share of any conforming hexahedral mesh, an object with ``BoxPartition``'s
         members (``xgeom``, ``geom_dofmap``, ``ncells``, ``level(P)``, ``dof_coordinates(P)``, ``exterior_facets()``,
         ``facet_point_coordinates(P, cells, facets)``), used instead of constructing one; ``n``, ``proc_dims``,
-        ``rank``, ``size``, ``warp`` and ``cell_frames`` are then ignored."""
+        ``rank``, ``size``, ``warp``, ``cell_frames`` and ``geom_degree`` are then ignored.  Such a mesh announces the
+        degree of its coordinate element through an attribute ``geom_degree`` (1 when absent).
+
+        ``geom_degree`` (1..4): the degree g of the coordinate element (``BoxPartition``); ``warp`` is evaluated at the
+        degree-g nodes of every cell."""
         import torch
 
         self.orders = tuple(int(p) for p in orders)
         if list(self.orders) != sorted(set(self.orders)):
             raise ValueError("orders must be strictly ascending (coarse -> fine)")
         dims = tuple(proc_dims) if proc_dims is not None else default_proc_dims(size)
-        self.part = part if part is not None else BoxPartition(n, dims, rank, warp=warp, cell_frames=cell_frames)
+        self.part = part if part is not None else BoxPartition(n, dims, rank, warp=warp, cell_frames=cell_frames,
+                                                                   geom_degree=geom_degree)
         part = self.part
+        self.geom_degree = gdeg = int(getattr(part, "geom_degree", 1))
+        # the 8 corners among a cell's (g+1)^3 geometry nodes (cell centres: their mean)
+        corners = [((i * gdeg * (gdeg + 1)) + j * gdeg) * (gdeg + 1) + k * gdeg
+                   for i in (0, 1) for j in (0, 1) for k in (0, 1)]
         self.levels, self.layouts, self.operators, self.smoothers, self.eig_ranges = [], [], [], [], []
         self.rhs = []
         dev = torch.device(device)
@@ -81,11 +90,11 @@ class PoissonHierarchy:
         self.node_order = node_order
         ktensor = None
         if kappa_tensor is not None:  # the cells are the same on every level
-            centres = part.xgeom[part.geom_dofmap].mean(axis=1)
+            centres = part.xgeom[part.geom_dofmap[:, corners]].mean(axis=1)
             ktensor = torch.from_numpy(np.ascontiguousarray(kappa_tensor(centres), dtype=np.float64)).to(dev)
         sigma = None
         if reaction is not None:
-            centres = part.xgeom[part.geom_dofmap].mean(axis=1)
+            centres = part.xgeom[part.geom_dofmap[:, corners]].mean(axis=1)
             sigma = torch.from_numpy(np.ascontiguousarray(reaction(centres), dtype=np.float64).reshape(-1)).to(dev)
         for P in self.orders:
             lv = part.level(P)
@@ -101,7 +110,7 @@ class PoissonHierarchy:
             elif node_order != "ascending":
                 raise ValueError("PoissonHierarchy: node_order is 'ascending' or 'basix'")
             op = MatFreeLaplacian(P, self.kappa, dofmap, self.xgeom, self.geom_dofmap, lv.lcells, lv.bcells,
-                                  lv.bc_marker, layout, node_order=node_order)  # :270-272
+                                  lv.bc_marker, layout, node_order=node_order, geometry_degree=gdeg)  # :270-272
             if kappa_field is not None:
                 kq = Vector(layout)
                 kq.data.copy_(torch.from_numpy(np.ascontiguousarray(
