@@ -4,7 +4,7 @@
 // tensor, the patch plan or any launch of the apply.
 //
 // The lifting needs the UNCONSTRAINED operator on the cells that hold a marked dof (on a box: the boundary shell).
-// Those cells recompute their geometry in the kernel, exactly as geometry_kernel does, instead of reading the stored
+// Those cells recompute their geometry in the kernel, exactly as the tensor kernels do, instead of reading the stored
 // tensor: the kernel is then independent of the tensor's layout, of batched-geometry mode (no resident tensor), of the
 // affine mode and of the chain form, and the shell is a small share of the mesh (9 % of the cells at 64^3).
 #include "laplacian.hpp"
@@ -29,7 +29,7 @@ struct LiftShape
 
 // b[dof] -= alpha * (A_cell u_cell)[t] for the unmarked owned rows of the listed cells, with
 // u_cell[t] = marked(dof) ? g[dof] - x0[dof] : 0 -- the element kernel of src/laplacian.hpp:143-278 without its row and
-// column treatment, G_q computed in place (src/laplacian.hpp:72-111, as geometry_kernel: w_q / detJ, times the nodal
+// column treatment, G_q computed in place (src/laplacian.hpp:72-111, as point_tensor: w_q / detJ, times the nodal
 // coefficient when one is set, and with the per-cell diffusion tensor between the two adjugates when one is set).
 // Unmarked entries of g and x0 are never read.
 template <int ND>
@@ -102,15 +102,11 @@ __global__ void __launch_bounds__(LiftShape<ND>::THREADS)
     }
     else
     {
-      const double g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-      const double g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-      const double g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-      const double g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-      const double g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-      const double g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
-      f0[ci * N + t] = kc * (g0 * d0 + g1 * d1 + g2 * d2);
-      f1[ci * N + t] = kc * (g1 * d0 + g3 * d1 + g4 * d2);
-      f2[ci * N + t] = kc * (g2 * d0 + g4 * d1 + g5 * d2);
+      double G[6];
+      metric(K, s, G);
+      f0[ci * N + t] = kc * (G[0] * d0 + G[1] * d1 + G[2] * d2);
+      f1[ci * N + t] = kc * (G[1] * d0 + G[3] * d1 + G[4] * d2);
+      f2[ci * N + t] = kc * (G[2] * d0 + G[4] * d1 + G[5] * d2);
     }
   }
   __syncthreads();
@@ -195,19 +191,6 @@ __global__ void robin_kernel(long long npoints, int nd, const int32_t* __restric
     atomicAdd(&d[dof], wdS * alpha[gid]);
 }
 
-// number of entries of alpha[0, n) that are not finite and >= 0, added to *bad (zeroed by the caller)
-__global__ void robin_check_kernel(long long n, const double* __restrict__ alpha, double* __restrict__ bad)
-{
-  int mine = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-  {
-    const double v = alpha[i];
-    mine += !(v >= 0.0 && v <= 1.79769313486231570e308); // NaN fails the first comparison, +inf the second
-  }
-  if (mine)
-    atomicAdd(bad, (double)mine);
-}
-
 // do p[0, np) and q[0, nq) share memory?
 bool overlaps(const double* p, size_t np, const double* q, size_t nq)
 {
@@ -215,14 +198,6 @@ bool overlaps(const double* p, size_t np, const double* q, size_t nq)
     return false;
   const uintptr_t a = (uintptr_t)p, c = (uintptr_t)q;
   return a < c + nq * sizeof(double) && c < a + np * sizeof(double);
-}
-
-int not_capturing(hipStream_t s, const char* what)
-{
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  PMG_HIP(hipStreamIsCapturing(s, &cap));
-  PMG_REQUIRE(cap == hipStreamCaptureStatusNone, "%s", what);
-  return PMG_OK;
 }
 
 // Are the (host) facet lists those of cells the operator holds, and of local facets 0..5?
@@ -384,25 +359,15 @@ extern "C" int pmg_laplacian_set_robin(pmg_laplacian op, int32_t nfacets, const 
   pmg_layout l = op->layout;
   const int total = l->total();
   const long long np = (long long)nfacets * op->nd * op->nd;
-  // every value finite and >= 0, on every rank (the count is summed over the ranks: all of them refuse, or none -- a
-  // rank without a facet takes part with a count of zero, so the call is collective whatever each rank lists)
-  double* bad = red_slot(l, 0);
-  PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
-  if (np > 0)
-    robin_check_kernel<<<(unsigned)std::min<long long>((np + 255) / 256, 1024), 256, 0, s>>>(np, alpha, bad);
-  PMG_HIP(hipGetLastError());
-  PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
-  double nbad = 0.0;
-  PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
-  if (nbad != 0.0)
-    return fail(PMG_ERR_INVALID, "pmg_laplacian_set_robin: %lld facet points have a value that is not finite and >= 0",
-                (long long)nbad);
+  // (a rank without a facet takes part with a count of zero, so the call is collective whatever each rank lists)
+  PMG_TRY(require_valid(l, np, alpha, FiniteNonNegative{},
+                        "pmg_laplacian_set_robin: %lld facet points have a value that is not finite and >= 0", s));
   if (nfacets == 0)
   {
     if (!op->has_robin)
       return PMG_OK;
     op->has_robin = false; // (a reaction term stays: the vector becomes d_sigma)
-    return laplacian_diagonal_term_changed(op, s);
+    return laplacian_data_changed(op, DATA_DIAGONAL_TERM, s);
   }
   int32_t* d_cells = nullptr;
   int8_t* d_local = nullptr;
@@ -442,5 +407,5 @@ extern "C" int pmg_laplacian_set_robin(pmg_laplacian op, int32_t nfacets, const 
     return fail(PMG_ERR_HIP, "pmg_laplacian_set_robin: %s", hipGetErrorString(e));
   }
   op->has_robin = true;
-  return laplacian_diagonal_term_changed(op, s);
+  return laplacian_data_changed(op, DATA_DIAGONAL_TERM, s);
 }

@@ -45,6 +45,15 @@ int fail(int code, const char* fmt, ...);
 
 inline hipStream_t S(pmg_stream s) { return reinterpret_cast<hipStream_t>(s); }
 
+// refuses, with the caller's message, a call that allocates, synchronises or reads back while `s` is being captured
+inline int not_capturing(hipStream_t s, const char* what)
+{
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  PMG_HIP(hipStreamIsCapturing(s, &cap));
+  PMG_REQUIRE(cap == hipStreamCaptureStatusNone, "%s", what);
+  return PMG_OK;
+}
+
 // a device copy of the host array src[0, n) (at least one element is allocated), stream-ordered
 template <typename T>
 int upload(T** dst, const T* src, size_t n, hipStream_t s)
@@ -321,9 +330,16 @@ int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hi
 bool laplacian_wants_zeroed_output(pmg_laplacian op);
 const double* laplacian_diag_inv(pmg_laplacian op);
 const double* laplacian_reaction(pmg_laplacian op); // the diagonal term, d_sigma + d_R; nullptr = none
-// a component of the diagonal term was set or removed (pmg_laplacian_set_reaction, pmg_laplacian_set_robin): rebuild
-// the summed vector in place and what follows it (float copy, computed inverse diagonal); waits for the stream
-int laplacian_diagonal_term_changed(pmg_laplacian op, hipStream_t s);
+// An input of the operator was set or removed -- the nodal field, the per-cell tensor, a component of the diagonal term
+// (pmg_laplacian_set_reaction, pmg_laplacian_set_robin) --: rebuild, in place, everything that follows it (the
+// dependency list is at the definition); waits for the stream.  `changed`: a sum of OperatorData values.
+enum OperatorData : unsigned
+{
+  DATA_FIELD = 1,
+  DATA_TENSOR = 2,
+  DATA_DIAGONAL_TERM = 4
+};
+int laplacian_data_changed(pmg_laplacian op, unsigned changed, hipStream_t s);
 pmg_layout laplacian_layout(pmg_laplacian op);
 long long laplacian_launches(pmg_laplacian op);
 long long laplacian_capture_state(pmg_laplacian op); // -1 = not capturable right now

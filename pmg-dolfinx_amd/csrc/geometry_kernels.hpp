@@ -1,5 +1,6 @@
 // Private fragment of laplacian.hip, included there and nowhere else (inside its anonymous namespace): the layout of
-// the stored geometry tensor G, and the geometry, export, diagonal and load-vector kernels that index it.
+// the stored geometry tensor G, and the affine-tensor, export, diagonal, load-vector and reaction kernels.  (The kernels
+// that build G are in tensor_kernels.hpp, shared with the float tensor.)
 
 // Layout of the stored geometry tensor G (double2 pairs (G00,G01)(G02,G11)(G12,G22)).  Two layouts:
 //   default: [slot][layer c][pair][a*nd+b]
@@ -35,60 +36,6 @@ __device__ __forceinline__ size_t gpos(int nd, int K, long long slot, int q, int
   return base + row + pair * (cw * nsq) + (sl - item * cw) * nsq + a * nd + b;
 }
 
-// G for the patch slots [slot0, slot0 + nslots) and every q, paired layout (absolute positions:
-// in batch mode G points `slot0` slots before its buffer).  kfield (optional): the nodal coefficient, one value per
-// local dof; G_q is scaled by its value at the point's own dof (GLL collocation: the points are the nodes).  Threads
-// of a wavefront walk q, so the dofmap read is contiguous; the kfield gather follows the dofmap like the apply's x.
-// ktensor (optional): the per-cell diffusion tensor [ncells][6]; G_q = adj(J) K_c adj(J)^T w_q / detJ (tensor_geometry).
-// Its six values are one 48-byte read per cell, the same address for (nearly) every lane of a wavefront; the address
-// depends on the cell alone, not on anything computed per point.  The read is written inside the branch, after the
-// Jacobian: hoisted above it, it holds twelve more registers across the Jacobian's gathers (68 VGPRs and 7 waves per
-// SIMD instead of 60 and 8, with or without a tensor).  Without a tensor the branch is uniform and not taken.
-__global__ void geometry_kernel(long long slot0, long long nslots, int nd, int K,
-                                const int32_t* __restrict__ pcell,
-                                const double* __restrict__ xgeom,
-                                const int32_t* __restrict__ geom_dofmap,
-                                const double* __restrict__ dphi, const double* __restrict__ w,
-                                const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
-                                const double* __restrict__ ktensor, double2* __restrict__ G)
-{
-  const int nq = nd * nd * nd;
-  long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= nslots * nq)
-    return;
-  long long slot = gid / nq;
-  int q = (int)(gid - slot * nq);
-  slot += slot0;
-  int c = pcell[slot];
-  double g0 = 0, g1 = 0, g2 = 0, g3 = 0, g4 = 0, g5 = 0;
-  if (c >= 0)
-  {
-    double K[3][3], detJ;
-    jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
-    double s = w[q] / detJ;
-    if (kfield)
-      s *= kfield[dofmap[(size_t)c * nq + q]];
-    if (ktensor)
-    {
-      double g[6];
-      tensor_geometry(K, ktensor + (size_t)c * 6, s, g);
-      g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5];
-    }
-    else
-    {
-      g0 = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s; // :99-111
-      g1 = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-      g2 = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-      g3 = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-      g4 = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-      g5 = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
-    }
-  }
-  G[gpos(nd, K, slot, q, 0)] = make_double2(g0, g1);
-  G[gpos(nd, K, slot, q, 1)] = make_double2(g2, g3);
-  G[gpos(nd, K, slot, q, 2)] = make_double2(g4, g5);
-}
-
 // Constant geometry tensor of an affine cell: K K^T / detJ at the cell centre
 // (q-independent when the cell is a parallelepiped); G_q = w_q * this.  ktensor (optional): the per-cell diffusion
 // tensor, constant over the cell like the rest: K Kc K^T / detJ.  g: the coordinate element's degree; the four corners
@@ -118,17 +65,8 @@ __global__ void affine_geometry_kernel(long long nslots, int gdeg, const int32_t
       J[i][1] = xy[i] - x0[i];
       J[i][2] = xz[i] - x0[i];
     }
-    double K[3][3];
-    K[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-    K[0][1] = -J[0][1] * J[2][2] + J[0][2] * J[2][1];
-    K[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-    K[1][0] = -J[1][0] * J[2][2] + J[1][2] * J[2][0];
-    K[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-    K[1][2] = -J[0][0] * J[1][2] + J[0][2] * J[1][0];
-    K[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
-    K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    const double detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]); // as jacobian(): |det J|
+    double K[3][3], detJ;
+    adjugate(J, K, detJ);
     const double s = 1.0 / detJ;
     if (ktensor)
     {
@@ -138,14 +76,7 @@ __global__ void affine_geometry_kernel(long long nslots, int gdeg, const int32_t
       tensor_geometry(K, t, s, g);
     }
     else
-    {
-      g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-      g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-      g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-      g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-      g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-      g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
-    }
+      metric(K, s, g);
   }
   for (int d = 0; d < 6; ++d)
     Gaff[slot * 6 + d] = g[d];

@@ -33,17 +33,17 @@
 // Roofline: HBM-bound, AI 0.85 (P=1) .. 2.05 (P=8) flop/B; algorithmic bytes per
 // cell 48N + 4N + 8 + 17U (model "storedG").
 //
-// One translation unit, five files and a header.  stiffness_layer.hpp (a real header, shared with laplacian_f32.hip)
+// One translation unit, five files and two headers.  stiffness_layer.hpp (a real header, shared with laplacian_f32.hip)
 // holds the layer march of the four apply kernels: fences, loads, the lane's table rows, the two halves of a layer, the
-// packed positions and the tensor stream.  The fragments are included below, inside the anonymous namespace, in this
-// order:
-//   geometry_kernels.hpp  layout of G (gflat, gpatch, gpos); geometry, export, diagonal and load-vector kernels
+// packed positions and the tensor stream; tensor_kernels.hpp (shared likewise) the kernels that build the geometry
+// tensor.  The fragments are included below, inside the anonymous namespace, in this order:
+//   geometry_kernels.hpp  layout of G (gflat, gpatch, gpos); affine-tensor, export, diagonal, load and reaction kernels
 //   stiffness_column.hpp  Shape<P> and its policies, write-back, diagnostic stamps, stiffness_column_kernel
 //   stiffness_chain.hpp   ChainShape<P>, stiffness_chain_kernel (P = 4)
 //   stiffness_restrict.hpp  stiffness_restrict_kernel: the apply fused with the restriction of r - A z
 //   laplacian.hip         the host side: launch plan, run_launches, the C ABI
 #include "laplacian.hpp"
-#include "curved_geometry.hpp"
+#include "tensor_kernels.hpp"
 #include "stiffness_layer.hpp"
 
 #include <algorithm>
@@ -61,7 +61,7 @@ namespace
 #include "stiffness_chain.hpp"
 #include "stiffness_restrict.hpp"
 
-// where the degree-g geometry kernels (curved_geometry.hpp) put a point's six values: the stored tensor's layout
+// where the geometry kernels (tensor_kernels.hpp) put a point's six values: the stored tensor's layout
 struct TensorOut64
 {
   double2* G; // absolute slot positions (batch_geometry)
@@ -85,15 +85,30 @@ __global__ void zero_list_kernel(int n, const int32_t* __restrict__ idx, double*
 const double2* batch_geometry(pmg_laplacian op, int first, int count, hipStream_t s)
 {
   double2* base = op->G - (size_t)first * gpatch(op->nd, op->K);
-  const long long nslots = (long long)count * op->K, n = nslots * op->N;
-  if (op->ng != 8) // a coordinate element of degree >= 2 (curved_geometry.hpp)
-    launch_curved_geometry(op, (long long)first * op->K, nslots, TensorOut64{base, op->nd, op->K}, s);
-  else if (n > 0)
-    geometry_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)first * op->K, nslots, op->nd, op->K,
-                                                              op->pcell, op->xgeom, op->geom_dofmap,
-                                                              op->dphi_geom, op->gweights, op->kfield, op->dofmap,
-                                                              op->ktensor, base);
+  launch_geometry(op, (long long)first * op->K, (long long)count * op->K, TensorOut64{base, op->nd, op->K}, s);
   return base;
+}
+
+// The two tensors that are rebuilt in place, by the constructor and by laplacian_data_changed: the resident G (in
+// batched-geometry mode there is none: every application recomputes its batches) ...
+int rebuild_resident_tensor(pmg_laplacian op, hipStream_t s)
+{
+  if (op->batch_patches == 0 && op->npatch > 0)
+    batch_geometry(op, 0, op->npatch, s);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
+// ... and Gaff, one constant tensor per (affine) cell
+int rebuild_affine_tensor(pmg_laplacian op, hipStream_t s)
+{
+  const long long nslots = (long long)op->npatch * op->K;
+  if (nslots > 0)
+    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->geom_degree, op->pcell,
+                                                                           op->xgeom, op->geom_dofmap, op->ktensor,
+                                                                           op->Gaff);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
 }
 
 // f(first patch, patch count, G base) over all patches: once with the resident tensor, or batch by
@@ -271,7 +286,7 @@ int laplacian_apply_restrict(pmg_laplacian op, const TransferView& tv, const dou
 }
 
 const double* laplacian_diag_inv(pmg_laplacian op) { return op->diag_inv; }
-// matrix.hip, amg.hip: the reaction and Robin components summed (laplacian_diagonal_term_changed); nullptr = none
+// matrix.hip, amg.hip: the reaction and Robin components summed (rebuild_diagonal_term); nullptr = none
 const double* laplacian_reaction(pmg_laplacian op) { return op->react; }
 pmg_layout laplacian_layout(pmg_laplacian op) { return op->layout; }
 long long laplacian_launches(pmg_laplacian op) { return op->applies; }
@@ -286,8 +301,8 @@ long long laplacian_capture_state(pmg_laplacian op)
   // every apply launch, and which launches an operator in chain form issues; a later set of either, and the second
   // component beside the first, rewrite the vector in place)
   // (batched geometry: the captured geometry launches carry the field's and the coefficient tensor's addresses -- one
-  // epoch counts both; the resident tensor is rebuilt in place by pmg_laplacian_set_coefficient_field / _tensor, so a
-  // graph over it stays valid)
+  // epoch counts both; the resident tensor is rebuilt in place, as everything else that follows the operator's data
+  // (laplacian_data_changed states what follows what), so a graph over it stays valid)
   const long long field = op->batch_patches > 0 ? (op->kfield_epoch & 0x3fff) << 44 : 0;
   return ((long long)op->geometry_mode << 40) ^ ((long long)op->batch_patches << 8) ^ (long long)(op->have_diag ? 1 : 0)
          ^ (long long)(op->chain_on ? 2 : 0) ^ (long long)(op->react ? 4 : 0) ^ field;
@@ -508,7 +523,7 @@ extern "C" int pmg_laplacian_create_curved(
           w3[(a * nd + b) * nd + c] = wts[a] * wts[b] * wts[c];
     PMG_TRY(upload(&op->dphi_geom, dphi.data(), dphi.size(), s));
     PMG_TRY(upload(&op->gweights, w3.data(), w3.size(), s));
-    if (g >= 2) // the cell-cooperative geometry kernel contracts with the 1-D tables (curved_geometry.hpp)
+    if (g >= 2) // the cell-cooperative geometry kernel contracts with the 1-D tables (tensor_kernels.hpp)
     {
       PMG_REQUIRE(curved_lds_bytes(nd, gm) <= 64 * 1024, "internal: the curved geometry kernel needs %zu bytes of LDS",
                   curved_lds_bytes(nd, gm));
@@ -646,12 +661,9 @@ extern "C" int pmg_laplacian_create_curved(
   }
 
   const long long nslots = (long long)plan.npatch * op->K;
-  const long long nq_total = nslots * N;
   PMG_TRY(upload(&op->W1, wts.data(), wts.size(), s));
   PMG_HIP(hipMalloc(&op->Gaff, sizeof(double) * 6 * (nslots ? nslots : 1)));
-  if (nslots > 0)
-    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, g, op->pcell, xgeom,
-                                                                           geom_dofmap, nullptr, op->Gaff);
+  PMG_TRY(rebuild_affine_tensor(op, s));
   {
     const size_t gsize = (size_t)op->npatch * gpatch(nd, op->K);
     PMG_HIP(hipMalloc(&op->G, sizeof(double2) * (gsize ? gsize : 1)));
@@ -661,11 +673,7 @@ extern "C" int pmg_laplacian_create_curved(
   PMG_HIP(hipMalloc(&op->diag_inv, sizeof(double) * (total ? total : 1)));
   PMG_HIP(hipEventCreate(&op->ev0));
   PMG_HIP(hipEventCreate(&op->ev1));
-  if (nq_total > 0)
-  {
-    batch_geometry(op, 0, op->npatch, s);
-    PMG_HIP(hipGetLastError());
-  }
+  PMG_TRY(rebuild_resident_tensor(op, s));
   PMG_HIP(hipStreamSynchronize(s)); // plan's host vectors are released on return
   *out = guard.release();
   return PMG_OK;
@@ -839,18 +847,83 @@ extern "C" int pmg_laplacian_compute_diag_inverse(pmg_laplacian op, pmg_stream s
   return PMG_OK;
 }
 
-// number of entries of kq[0, n) that are not finite and positive, added to *bad (zeroed by the caller)
-__global__ void coefficient_check_kernel(int n, const double* __restrict__ kq, double* __restrict__ bad)
+// react = d_sigma + d_R, in that order (both components present)
+__global__ void diagonal_term_sum_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
+                                         double* __restrict__ out)
 {
-  int mine = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-  {
-    const double v = kq[i];
-    mine += !(v > 0.0 && v <= 1.79769313486231570e308); // NaN fails the first comparison, +inf the second
-  }
-  if (mine)
-    atomicAdd(bad, (double)mine);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    out[i] = a[i] + b[i];
 }
+
+// The one vector the kernels read, from its components (d_sigma in sigma_buf, d_R in robin_buf): an exact copy of the
+// only component present, or d_sigma + d_R, always in react_buf, so a second set or a second component rewrites it at
+// the address a captured graph read it from; nullptr when neither is present.  apply_form,
+// pmg_laplacian_launches_per_apply and laplacian_capture_state read `react` itself.
+static int rebuild_diagonal_term(pmg_laplacian op, hipStream_t s)
+{
+  const int total = op->layout->total();
+  const size_t bytes = sizeof(double) * (total ? total : 1);
+  if (!op->has_sigma && !op->has_robin)
+  {
+    op->react = nullptr; // (the allocations stay with the handle: laplacian.hpp)
+    op->react32 = nullptr;
+    return PMG_OK;
+  }
+  if (!op->react_buf)
+    PMG_HIP(hipMalloc(&op->react_buf, bytes));
+  op->react = op->react_buf;
+  if (op->has_sigma && op->has_robin)
+  {
+    if (total > 0)
+      diagonal_term_sum_kernel<<<(total + 255) / 256, 256, 0, s>>>(total, op->sigma_buf, op->robin_buf, op->react);
+    PMG_HIP(hipGetLastError());
+  }
+  else
+    PMG_HIP(hipMemcpyAsync(op->react, op->has_sigma ? op->sigma_buf : op->robin_buf, bytes, hipMemcpyDeviceToDevice,
+                           s));
+  return PMG_OK;
+}
+
+namespace pmg
+{
+// What the operator derives from its data, and from which of it -- the statement of the dependencies, which the setters
+// and laplacian_capture_state rely on:
+//
+//   G         follows the geometry, the nodal field and the per-cell tensor; only while resident (in batched-geometry
+//             mode every application recomputes its batches from the same three)
+//   Gaff      follows the geometry and the tensor (the affine mode refuses a field)
+//   G32       follows what G follows, once it exists (the first FP32 use builds it)
+//   react     follows sigma_buf and robin_buf, the two components of the diagonal term
+//   react32   follows react, while G32 exists
+//   diag_inv  follows G, react and kappa, once pmg_laplacian_compute_diag_inverse has computed it (a diagonal the
+//             caller set is the caller's)
+//   diag32    follows diag_inv, lazily, by version (laplacian_f32_diag)
+//
+// `changed` names the data that was set or removed (OperatorData).  Everything that follows it is rebuilt here, in this
+// order, each in its own buffer -- so a captured graph of this operator's launches stays valid; what changes a kernel
+// argument or the launch list instead is in laplacian_capture_state.  Then waits for the stream: the setter's caller may
+// free its array on return.
+int laplacian_data_changed(pmg_laplacian op, unsigned changed, hipStream_t s)
+{
+  const bool tensors = (changed & (DATA_FIELD | DATA_TENSOR)) != 0;
+  if (tensors)
+    PMG_TRY(rebuild_resident_tensor(op, s));
+  if (changed & DATA_TENSOR)
+    PMG_TRY(rebuild_affine_tensor(op, s));
+  if (tensors)
+    PMG_TRY(laplacian_f32_refresh(op, s));
+  if (changed & DATA_DIAGONAL_TERM)
+  {
+    PMG_TRY(rebuild_diagonal_term(op, s));
+    PMG_TRY(laplacian_f32_reaction(op, s));
+  }
+  if (op->have_diag && op->diag_computed)
+    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, (pmg_stream)s));
+  PMG_HIP(hipStreamSynchronize(s));
+  return PMG_OK;
+}
+} // namespace pmg
 
 extern "C" int pmg_laplacian_has_coefficient_field(pmg_laplacian op) { return op ? (op->kfield ? 1 : 0) : -1; }
 
@@ -858,10 +931,8 @@ extern "C" int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const doubl
 {
   PMG_REQUIRE(op, "pmg_laplacian_set_coefficient_field: NULL argument");
   hipStream_t s = S(stream);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  PMG_HIP(hipStreamIsCapturing(s, &cap));
-  PMG_REQUIRE(cap == hipStreamCaptureStatusNone,
-              "pmg_laplacian_set_coefficient_field: not inside a stream capture (it allocates and synchronises)");
+  PMG_TRY(not_capturing(
+      s, "pmg_laplacian_set_coefficient_field: not inside a stream capture (it allocates and synchronises)"));
   pmg_layout l = op->layout;
   double* released = nullptr;
   if (!kq)
@@ -877,20 +948,9 @@ extern "C" int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const doubl
     PMG_REQUIRE(op->geometry_mode == 0,
                 "pmg_laplacian_set_coefficient_field: the affine mode streams one tensor per cell and cannot carry a "
                 "field (return to the stored tensor with pmg_laplacian_set_geometry_mode(op, 0) first)");
-    // every owned entry finite and > 0, on every rank (the count is summed over the ranks: all of them refuse, or
-    // none)
-    double* bad = red_slot(l, 0);
-    PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
-    if (l->size_local > 0)
-      coefficient_check_kernel<<<std::min((l->size_local + 255) / 256, 1024), 256, 0, s>>>(l->size_local, kq, bad);
-    PMG_HIP(hipGetLastError());
-    PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
-    double nbad = 0.0;
-    PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
-    if (nbad != 0.0)
-      return fail(PMG_ERR_INVALID,
-                  "pmg_laplacian_set_coefficient_field: %lld entries of the field are not finite and greater than 0",
-                  (long long)nbad);
+    PMG_TRY(require_valid(
+        l, l->size_local, kq, FinitePositive{},
+        "pmg_laplacian_set_coefficient_field: %lld entries of the field are not finite and greater than 0", s));
     if (!op->kfield)
     {
       PMG_HIP(hipMalloc(&op->kfield, sizeof(double) * (l->total() ? l->total() : 1)));
@@ -903,38 +963,10 @@ extern "C" int pmg_laplacian_set_coefficient_field(pmg_laplacian op, const doubl
       PMG_TRY(scatter_fwd_whole(l, op->kfield, s));
     }
   }
-  // what depends on G, each in its own buffer (a captured graph of this operator's launches stays valid)
-  if (op->batch_patches == 0 && op->npatch > 0)
-    batch_geometry(op, 0, op->npatch, s);
-  PMG_HIP(hipGetLastError());
-  PMG_TRY(laplacian_f32_refresh(op, s));
-  if (op->have_diag && op->diag_computed)
-    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
-  PMG_HIP(hipStreamSynchronize(s)); // the caller may free kq on return
+  PMG_TRY(laplacian_data_changed(op, DATA_FIELD, s)); // (it waits for the stream: the caller may free kq on return)
   if (released)
     PMG_HIP(hipFree(released));
   return PMG_OK;
-}
-
-// number of cells of kt[0, ncells)[6] whose tensor (xx, xy, xz, yy, yz, zz) is not finite and symmetric positive
-// definite (leading minors: xx > 0, xx yy - xy^2 > 0, det > 0), added to *bad (zeroed by the caller)
-__global__ void coefficient_tensor_check_kernel(int ncells, const double* __restrict__ kt, double* __restrict__ bad)
-{
-  int mine = 0;
-  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < ncells;
-       c += (long long)gridDim.x * blockDim.x)
-  {
-    const double* t = kt + c * 6;
-    const double xx = t[0], xy = t[1], xz = t[2], yy = t[3], yz = t[4], zz = t[5];
-    bool ok = true;
-    for (int d = 0; d < 6; ++d)
-      ok = ok && fabs(t[d]) <= 1.79769313486231570e308; // NaN and +-inf fail
-    const double m2 = xx * yy - xy * xy;
-    const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
-    mine += !(ok && xx > 0.0 && m2 > 0.0 && det > 0.0);
-  }
-  if (mine)
-    atomicAdd(bad, (double)mine);
 }
 
 extern "C" int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op) { return op ? (op->ktensor ? 1 : 0) : -1; }
@@ -943,11 +975,8 @@ extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const doub
 {
   PMG_REQUIRE(op, "pmg_laplacian_set_coefficient_tensor: NULL argument");
   hipStream_t s = S(stream);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  PMG_HIP(hipStreamIsCapturing(s, &cap));
-  PMG_REQUIRE(cap == hipStreamCaptureStatusNone,
-              "pmg_laplacian_set_coefficient_tensor: not inside a stream capture (it allocates and synchronises)");
-  pmg_layout l = op->layout;
+  PMG_TRY(not_capturing(
+      s, "pmg_laplacian_set_coefficient_tensor: not inside a stream capture (it allocates and synchronises)"));
   double* released = nullptr;
   if (!kt)
   {
@@ -959,21 +988,10 @@ extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const doub
   }
   else
   {
-    // every cell's tensor finite and positive definite, on every rank (the count is summed over the ranks: all of
-    // them refuse, or none; a cell that is a ghost elsewhere is counted on each rank that holds it)
-    double* bad = red_slot(l, 0);
-    PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
-    if (op->ncells > 0)
-      coefficient_tensor_check_kernel<<<std::min((op->ncells + 255) / 256, 1024), 256, 0, s>>>(op->ncells, kt, bad);
-    PMG_HIP(hipGetLastError());
-    PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
-    double nbad = 0.0;
-    PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
-    if (nbad != 0.0)
-      return fail(PMG_ERR_INVALID,
-                  "pmg_laplacian_set_coefficient_tensor: %lld cells have a tensor that is not finite and positive "
-                  "definite",
-                  (long long)nbad);
+    // (a cell that is a ghost elsewhere is counted on each rank that holds it)
+    PMG_TRY(require_valid(
+        op->layout, op->ncells, kt, FiniteSpd{},
+        "pmg_laplacian_set_coefficient_tensor: %lld cells have a tensor that is not finite and positive definite", s));
     if (!op->ktensor)
     {
       PMG_HIP(hipMalloc(&op->ktensor, sizeof(double) * 6 * (size_t)(op->ncells ? op->ncells : 1)));
@@ -981,86 +999,11 @@ extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const doub
     }
     PMG_HIP(hipMemcpyAsync(op->ktensor, kt, sizeof(double) * 6 * (size_t)op->ncells, hipMemcpyDeviceToDevice, s));
   }
-  // what depends on G, each in its own buffer (a captured graph of this operator's launches stays valid)
-  if (op->batch_patches == 0 && op->npatch > 0)
-    batch_geometry(op, 0, op->npatch, s);
-  const long long nslots = (long long)op->npatch * op->K;
-  if (nslots > 0)
-    affine_geometry_kernel<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(nslots, op->geom_degree, op->pcell,
-                                                                           op->xgeom, op->geom_dofmap, op->ktensor,
-                                                                           op->Gaff);
-  PMG_HIP(hipGetLastError());
-  PMG_TRY(laplacian_f32_refresh(op, s));
-  if (op->have_diag && op->diag_computed)
-    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, stream));
-  PMG_HIP(hipStreamSynchronize(s)); // the caller may free kt on return
+  PMG_TRY(laplacian_data_changed(op, DATA_TENSOR, s)); // (it waits for the stream: the caller may free kt on return)
   if (released)
     PMG_HIP(hipFree(released));
   return PMG_OK;
 }
-
-// number of entries of sigma[0, ncells) that are not finite and >= 0, added to *bad (zeroed by the caller)
-__global__ void reaction_check_kernel(int ncells, const double* __restrict__ sigma, double* __restrict__ bad)
-{
-  int mine = 0;
-  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < ncells;
-       c += (long long)gridDim.x * blockDim.x)
-  {
-    const double v = sigma[c];
-    mine += !(v >= 0.0 && v <= 1.79769313486231570e308); // NaN fails the first comparison, +inf the second
-  }
-  if (mine)
-    atomicAdd(bad, (double)mine);
-}
-
-// react = d_sigma + d_R, in that order (both components present)
-__global__ void diagonal_term_sum_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
-                                         double* __restrict__ out)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    out[i] = a[i] + b[i];
-}
-
-namespace pmg
-{
-// The diagonal term changed: a component (d_sigma in sigma_buf, d_R in robin_buf) was set, rewritten or removed.
-// Rebuilds the one vector the kernels read -- an exact copy of the only component present, or d_sigma + d_R, always in
-// react_buf, so a second set or a second component rewrites it at the address a captured graph read it from; nullptr
-// when neither is present -- and what follows it: the float copy and a computed inverse diagonal.  apply_form,
-// pmg_laplacian_launches_per_apply and laplacian_capture_state read `react` itself.  Waits for the stream.
-int laplacian_diagonal_term_changed(pmg_laplacian op, hipStream_t s)
-{
-  const int total = op->layout->total();
-  const size_t bytes = sizeof(double) * (total ? total : 1);
-  if (!op->has_sigma && !op->has_robin)
-  {
-    op->react = nullptr; // (the allocations stay with the handle: laplacian.hpp)
-    op->react32 = nullptr;
-  }
-  else
-  {
-    if (!op->react_buf)
-      PMG_HIP(hipMalloc(&op->react_buf, bytes));
-    op->react = op->react_buf;
-    if (op->has_sigma && op->has_robin)
-    {
-      if (total > 0)
-        diagonal_term_sum_kernel<<<(total + 255) / 256, 256, 0, s>>>(total, op->sigma_buf, op->robin_buf, op->react);
-      PMG_HIP(hipGetLastError());
-    }
-    else
-      PMG_HIP(hipMemcpyAsync(op->react, op->has_sigma ? op->sigma_buf : op->robin_buf, bytes, hipMemcpyDeviceToDevice,
-                             s));
-  }
-  // what depends on the vector, each in its own buffer
-  PMG_TRY(laplacian_f32_reaction(op, s));
-  if (op->have_diag && op->diag_computed)
-    PMG_TRY(pmg_laplacian_compute_diag_inverse(op, (pmg_stream)s));
-  PMG_HIP(hipStreamSynchronize(s));
-  return PMG_OK;
-}
-} // namespace pmg
 
 extern "C" int pmg_laplacian_has_reaction(pmg_laplacian op) { return op ? (op->has_sigma ? 1 : 0) : -1; }
 
@@ -1068,12 +1011,8 @@ extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma,
 {
   PMG_REQUIRE(op, "pmg_laplacian_set_reaction: NULL argument");
   hipStream_t s = S(stream);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  PMG_HIP(hipStreamIsCapturing(s, &cap));
-  PMG_REQUIRE(cap == hipStreamCaptureStatusNone,
-              "pmg_laplacian_set_reaction: not inside a stream capture (it allocates and synchronises)");
-  pmg_layout l = op->layout;
-  const int total = l->total();
+  PMG_TRY(not_capturing(s, "pmg_laplacian_set_reaction: not inside a stream capture (it allocates and synchronises)"));
+  const int total = op->layout->total();
   if (!sigma)
   {
     if (!op->has_sigma)
@@ -1082,19 +1021,9 @@ extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma,
   }
   else
   {
-    // every cell's value finite and >= 0, on every rank (the count is summed over the ranks: all of them refuse, or
-    // none; a cell that is a ghost elsewhere is counted on each rank that holds it)
-    double* bad = red_slot(l, 0);
-    PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
-    if (op->ncells > 0)
-      reaction_check_kernel<<<std::min((op->ncells + 255) / 256, 1024), 256, 0, s>>>(op->ncells, sigma, bad);
-    PMG_HIP(hipGetLastError());
-    PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
-    double nbad = 0.0;
-    PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
-    if (nbad != 0.0)
-      return fail(PMG_ERR_INVALID, "pmg_laplacian_set_reaction: %lld cells have a value that is not finite and >= 0",
-                  (long long)nbad);
+    // (a cell that is a ghost elsewhere is counted on each rank that holds it)
+    PMG_TRY(require_valid(op->layout, op->ncells, sigma, FiniteNonNegative{},
+                          "pmg_laplacian_set_reaction: %lld cells have a value that is not finite and >= 0", s));
     if (!op->sigma_buf)
       PMG_HIP(hipMalloc(&op->sigma_buf, sizeof(double) * (total ? total : 1)));
     op->has_sigma = true;
@@ -1107,7 +1036,7 @@ extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma,
                                                                  sigma, op->sigma_buf);
     PMG_HIP(hipGetLastError());
   }
-  return laplacian_diagonal_term_changed(op, s); // (it waits for the stream: the caller may free sigma on return)
+  return laplacian_data_changed(op, DATA_DIAGONAL_TERM, s); // (it waits for the stream: the caller may free sigma)
 }
 
 extern "C" int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream stream)
@@ -1201,10 +1130,9 @@ extern "C" int pmg_laplacian_set_geometry_batch(pmg_laplacian op, long long batc
   PMG_HIP(hipStreamSynchronize(nullptr)); // (null-stream fill: not ordered against the caller's non-blocking stream)
   op->batch_patches = bp;
   op->stream_policy = streams_past_the_cache((long long)sizeof(double2) * gsize);
-  if (bp == 0 && op->npatch > 0) // back to the resident tensor
+  if (bp == 0 && op->npatch > 0) // back to the resident tensor (on the null stream, as the fill above)
   {
-    batch_geometry(op, 0, op->npatch, nullptr);
-    PMG_HIP(hipGetLastError());
+    PMG_TRY(rebuild_resident_tensor(op, nullptr));
     PMG_HIP(hipDeviceSynchronize());
   }
   return PMG_OK;

@@ -4,6 +4,8 @@
 #include "common.hpp"
 #include "patches.hpp"
 
+#include <algorithm>
+
 struct pmg_laplacian_s
 {
   pmg_layout layout = nullptr;
@@ -24,7 +26,7 @@ struct pmg_laplacian_s
   // owned
   double2* G = nullptr;        // [nslots][3][N]
   // nodal coefficient (pmg_laplacian_set_coefficient_field): folded into G, and into the float tensor, where they are
-  // built (geometry_kernel); nullptr = none
+  // built (point_tensor); nullptr = none
   double* kfield = nullptr;    // [size_local + num_ghosts], ghosts filled by the layout's forward scatter
   long long kfield_epoch = 0;  // bumped when kfield is allocated or freed (laplacian_capture_state, batch mode)
   // per-cell diffusion tensor (pmg_laplacian_set_coefficient_tensor): symmetric positive definite, physical
@@ -46,7 +48,7 @@ struct pmg_laplacian_s
   // The vector has two components, set and removed independently: d_sigma (pmg_laplacian_set_reaction) and d_R, the
   // face mass of a Robin boundary term (pmg_laplacian_set_robin, boundary.hip).  Each is kept in a buffer of its own,
   // made on first need and kept with the handle; `react` is an exact copy of the only one present, or d_sigma + d_R in
-  // that order (laplacian_diagonal_term_changed), always in react_buf.
+  // that order (laplacian_data_changed), always in react_buf.
   double* sigma_buf = nullptr; // d_sigma [size_local + num_ghosts]
   double* robin_buf = nullptr; // d_R     [size_local + num_ghosts]
   bool has_sigma = false, has_robin = false;
@@ -60,7 +62,7 @@ struct pmg_laplacian_s
   // coordinate element (pmg_laplacian_create_curved): tensor-product Lagrange of degree geom_degree, ng = (g + 1)^3
   // nodes per cell in ascending tensor order.  geom_L / geom_Lp [nd][g + 1]: its 1-D basis and derivative at the
   // operator's GLL points, present when the library built the tabulation itself and g >= 2 -- the cell-cooperative
-  // geometry kernel contracts with them (curved_geometry.hpp); nullptr with caller tables (per-point dense path).
+  // geometry kernel contracts with them (tensor_kernels.hpp); nullptr with caller tables (per-point dense path).
   int geom_degree = 1, ng = 8;
   double* geom_L = nullptr;
   double* geom_Lp = nullptr;
@@ -182,7 +184,71 @@ int walk_launches(pmg_laplacian op, int l0, int l1, ApplyForm form, hipStream_t 
   return PMG_OK;
 }
 
-// adj(J) and |det J| of a Jacobian formed elsewhere (the degree-g paths), as jacobian() below forms them
+// ---- validation of a caller's device array: what one entry must be ... ----
+struct FinitePositive // finite and > 0 (the nodal field)
+{
+  __device__ bool operator()(const double* __restrict__ v, long long i) const
+  {
+    return v[i] > 0.0 && v[i] <= 1.79769313486231570e308; // NaN fails the first comparison, +inf the second
+  }
+};
+struct FiniteNonNegative // finite and >= 0; all zeros is legal (reaction and Robin values)
+{
+  __device__ bool operator()(const double* __restrict__ v, long long i) const
+  {
+    return v[i] >= 0.0 && v[i] <= 1.79769313486231570e308;
+  }
+};
+struct FiniteSpd // six values (xx, xy, xz, yy, yz, zz) per entry: finite, symmetric positive definite (the cell tensor)
+{
+  __device__ bool operator()(const double* __restrict__ v, long long i) const
+  {
+    const double* t = v + i * 6;
+    const double xx = t[0], xy = t[1], xz = t[2], yy = t[3], yz = t[4], zz = t[5];
+    bool ok = true;
+    for (int d = 0; d < 6; ++d)
+      ok = ok && fabs(t[d]) <= 1.79769313486231570e308; // NaN and +-inf fail
+    // leading minors: xx > 0, xx yy - xy^2 > 0, det > 0
+    const double m2 = xx * yy - xy * xy;
+    const double det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+    return ok && xx > 0.0 && m2 > 0.0 && det > 0.0;
+  }
+};
+
+// ... the number of entries of v[0, n) that are not, added to *bad (zeroed by the caller) ...
+template <typename Valid>
+__global__ void count_invalid_kernel(long long n, const double* __restrict__ v, double* __restrict__ bad, Valid valid)
+{
+  int mine = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    mine += !valid(v, i);
+  if (mine)
+    atomicAdd(bad, (double)mine);
+}
+
+// ... and the refusal: the count is summed over the ranks through the layout's reduction slot, so all of them refuse,
+// or none (a rank with n = 0 takes part with a count of zero: the call is collective).  `message` is the caller's, with
+// one %lld for the count.  Reads back: not inside a stream capture.
+template <typename Valid>
+int require_valid(pmg_layout l, long long n, const double* v, Valid valid, const char* message, hipStream_t s)
+{
+  double* bad = red_slot(l, 0);
+  PMG_HIP(hipMemsetAsync(bad, 0, sizeof(double), s));
+  if (n > 0)
+    count_invalid_kernel<<<(unsigned)std::min<long long>((n + 255) / 256, 1024), 256, 0, s>>>(n, v, bad, valid);
+  PMG_HIP(hipGetLastError());
+  PMG_TRY(reduce_slots_async(l, 0, 1, false, s));
+  double nbad = 0.0;
+  PMG_TRY(fetch_slots(l, 0, 1, &nbad, s));
+  if (nbad != 0.0)
+    return fail(PMG_ERR_INVALID, message, (long long)nbad);
+  return PMG_OK;
+}
+
+// adj(J) and |det J| of a Jacobian: the one cofactor expansion.  Full expansion along the first row (the reference's
+// :97 drops to the diagonal-J special case).  |det J|: a cell's local frame may be left-handed (vertex order of an
+// imported mesh); the volume measure, G, the load and the reaction weights do not depend on it.  K keeps its sign: it
+// enters G twice and the facet measure through a norm.  (fabs changes no bit of a positive determinant.)
 __device__ __forceinline__ void adjugate(const double J[3][3], double K[3][3], double& detJ)
 {
   K[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
@@ -197,58 +263,23 @@ __device__ __forceinline__ void adjugate(const double J[3][3], double K[3][3], d
   detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]);
 }
 
-// ---- geometry: J, adj(J), |det| at one quadrature point (src/laplacian.hpp:72-97) ----
-__device__ inline void jacobian(const double* __restrict__ xgeom,
-                                const int32_t* __restrict__ gdofs, const double* __restrict__ dphi,
-                                int nq, int q, double K[3][3], double& detJ)
-{
-  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int k = 0; k < 8; ++k)
-  {
-    const double* xk = xgeom + 3 * (size_t)gdofs[k];
-    double x0 = xk[0], x1 = xk[1], x2 = xk[2];
-    double d0 = dphi[(0 * nq + q) * 8 + k], d1 = dphi[(1 * nq + q) * 8 + k],
-           d2 = dphi[(2 * nq + q) * 8 + k];
-    J[0][0] += x0 * d0;
-    J[0][1] += x0 * d1;
-    J[0][2] += x0 * d2;
-    J[1][0] += x1 * d0;
-    J[1][1] += x1 * d1;
-    J[1][2] += x1 * d2;
-    J[2][0] += x2 * d0;
-    J[2][1] += x2 * d1;
-    J[2][2] += x2 * d2;
-  }
-  K[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-  K[0][1] = -J[0][1] * J[2][2] + J[0][2] * J[2][1];
-  K[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-  K[1][0] = -J[1][0] * J[2][2] + J[1][2] * J[2][0];
-  K[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-  K[1][2] = -J[0][0] * J[1][2] + J[0][2] * J[1][0];
-  K[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-  K[2][1] = -J[0][0] * J[2][1] + J[0][1] * J[2][0];
-  K[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-  // full cofactor expansion along the first row (the reference's :97 drops to
-  // the diagonal-J special case).  |det J|: a cell's local frame may be left-handed (vertex order of an imported
-  // mesh); the volume measure, G, the load and the reaction weights do not depend on it.  K keeps its sign: it enters
-  // G twice and the facet measure through a norm.  (fabs changes no bit of a positive determinant.)
-  detJ = fabs(J[0][0] * K[0][0] + J[0][1] * K[1][0] + J[0][2] * K[2][0]);
-}
-
-// The same for a coordinate element of `ng` nodes per cell (dense table [3][nq][ng], gdofs = the cell's ng nodes).  The
-// trilinear element keeps its own code above: ng == 8 goes there, so a degree-1 operator computes what it always did.
+// ---- geometry: J, adj(J), |det| at one quadrature point (src/laplacian.hpp:72-97) of a cell whose coordinate element
+// has NG nodes (dense table [3][nq][NG], gdofs = the cell's nodes).  NG = 8, the trilinear element: the node loop is
+// unrolled over a compile-time count.  NG = 0: the run-time count `ng` (degree >= 2). ----
+template <int NG>
 __device__ inline void jacobian(const double* __restrict__ xgeom, const int32_t* __restrict__ gdofs,
                                 const double* __restrict__ dphi, int nq, int q, int ng, double K[3][3], double& detJ)
 {
-  if (ng == 8)
-    return jacobian(xgeom, gdofs, dphi, nq, q, K, detJ);
+  static_assert(NG == 8 || NG == 0, "a compile-time node count other than the trilinear element's has no instantiation");
   double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  const double *t0 = dphi + (size_t)q * ng, *t1 = t0 + (size_t)nq * ng, *t2 = t1 + (size_t)nq * ng;
-  for (int k = 0; k < ng; ++k)
+  const int n = NG ? NG : ng;
+  const double *t0 = dphi + (size_t)q * ng, *t1 = t0 + (size_t)nq * ng, *t2 = t1 + (size_t)nq * ng; // (NG = 0)
+  for (int k = 0; k < n; ++k)
   {
     const double* xk = xgeom + 3 * (size_t)gdofs[k];
     const double x0 = xk[0], x1 = xk[1], x2 = xk[2];
-    const double d0 = t0[k], d1 = t1[k], d2 = t2[k];
+    const double d0 = NG ? dphi[(0 * nq + q) * NG + k] : t0[k], d1 = NG ? dphi[(1 * nq + q) * NG + k] : t1[k],
+                 d2 = NG ? dphi[(2 * nq + q) * NG + k] : t2[k];
     J[0][0] += x0 * d0;
     J[0][1] += x0 * d1;
     J[0][2] += x0 * d2;
@@ -260,6 +291,32 @@ __device__ inline void jacobian(const double* __restrict__ xgeom, const int32_t*
     J[2][2] += x2 * d2;
   }
   adjugate(J, K, detJ);
+  // The trilinear form has always rounded J00 K00 on its own and fused the other two products onto it; left to the
+  // compiler, the expression in adjugate() rounds J01 K10 first here, which moves |det J| of a sheared cell by a few
+  // ulps (profiles/point_geometry.md).  Degree-1 operators keep their bits: the contraction is written out.
+  if constexpr (NG == 8)
+    detJ = fabs(fma(J[0][2], K[2][0], fma(J[0][1], K[1][0], J[0][0] * K[0][0])));
+}
+
+// The same for a run-time node count: the trilinear element goes to its own form, so a degree-1 operator computes
+// what it always did.
+__device__ inline void jacobian(const double* __restrict__ xgeom, const int32_t* __restrict__ gdofs,
+                                const double* __restrict__ dphi, int nq, int q, int ng, double K[3][3], double& detJ)
+{
+  if (ng == 8)
+    return jacobian<8>(xgeom, gdofs, dphi, nq, q, 8, K, detJ);
+  jacobian<0>(xgeom, gdofs, dphi, nq, q, ng, K, detJ);
+}
+
+// ---- the six entries of adj(J) adj(J)^T * s (src/laplacian.hpp:99-111); K = adj(J) as jacobian() returns it ----
+__device__ __forceinline__ void metric(const double K[3][3], double s, double g[6])
+{
+  g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
+  g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
+  g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
+  g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
+  g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
+  g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
 }
 
 // ---- the six entries of adj(J) T adj(J)^T * s for a symmetric T = (xx, xy, xz, yy, yz, zz) in physical coordinates:
@@ -281,5 +338,26 @@ __device__ __forceinline__ void tensor_geometry(const double K[3][3], const doub
   g[3] = (M[1][0] * K[1][0] + M[1][1] * K[1][1] + M[1][2] * K[1][2]) * s;
   g[4] = (M[2][0] * K[1][0] + M[2][1] * K[1][1] + M[2][2] * K[1][2]) * s;
   g[5] = (M[2][0] * K[2][0] + M[2][1] * K[2][1] + M[2][2] * K[2][2]) * s;
+}
+
+// G_q from adj(J) and |det J| at the point q of cell c, the one place that forms it: w_q / detJ, times the nodal
+// coefficient at the point's own dof (kfield, optional; GLL collocation: the points are the nodes), with the per-cell
+// tensor between the two adjugates when one is set (ktensor, optional, [ncells][6]).  The tensor's six values are one
+// 48-byte read per cell, the same address for (nearly) every lane of a wavefront; the address depends on the cell
+// alone, not on anything computed per point.  The read is written inside the branch, after the caller's Jacobian:
+// hoisted above it, it holds twelve more registers across the Jacobian's gathers (in the 8-node per-point kernel 68
+// VGPRs and 7 waves per SIMD instead of 60 and 8, with or without a tensor).  Without a tensor the branch is uniform
+// and not taken.
+__device__ __forceinline__ void point_tensor(const double K[3][3], double detJ, int c, int nq, int q, const double* w,
+                                             const double* kfield, const int32_t* dofmap, const double* ktensor,
+                                             double g[6])
+{
+  double s = w[q] / detJ;
+  if (kfield)
+    s *= kfield[dofmap[(size_t)c * nq + q]];
+  if (ktensor)
+    tensor_geometry(K, ktensor + (size_t)c * 6, s, g);
+  else
+    metric(K, s, g);
 }
 } // namespace pmg

@@ -20,7 +20,7 @@
 // every degree run eight wavefronts per workgroup where it has the items (P = 6: 49 of 64 lanes, P = 7: 64 of 64),
 // and P = 5 / P = 8 share one item of 7 / 3 cells between four wavefronts as the FP64 kernel does.
 #include "laplacian.hpp"
-#include "curved_geometry.hpp"
+#include "tensor_kernels.hpp"
 #include "stiffness_layer.hpp"
 
 #include <algorithm>
@@ -58,50 +58,8 @@ struct Shape32
   static_assert(MAXM <= 65535, "patch positions are 16-bit");
 };
 
-// G for the patch slots [0, nslots) and every q, rounded once: [slot][layer c][pair][a*nd+b]; kfield (optional) is
-// the nodal coefficient and ktensor (optional) the per-cell diffusion tensor, both folded in as in geometry_kernel, in
-// double, before the one rounding
-__global__ void geometry_f32_kernel(long long nslots, int nd, const int32_t* __restrict__ pcell,
-                                    const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
-                                    const double* __restrict__ dphi, const double* __restrict__ w,
-                                    const double* __restrict__ kfield, const int32_t* __restrict__ dofmap,
-                                    const double* __restrict__ ktensor, float2* __restrict__ G)
-{
-  const int nsq = nd * nd, nq = nsq * nd;
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= nslots * nq)
-    return;
-  const long long slot = gid / nq;
-  const int q = (int)(gid - slot * nq);
-  const int c = pcell[slot];
-  double g[6] = {0, 0, 0, 0, 0, 0};
-  if (c >= 0)
-  {
-    double K[3][3], detJ;
-    jacobian(xgeom, geom_dofmap + (size_t)c * 8, dphi, nq, q, K, detJ);
-    double s = w[q] / detJ;
-    if (kfield)
-      s *= kfield[dofmap[(size_t)c * nq + q]];
-    if (ktensor)
-      tensor_geometry(K, ktensor + (size_t)c * 6, s, g);
-    else
-    {
-      g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-      g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-      g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-      g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-      g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-      g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
-    }
-  }
-  const int a = q / nsq, b = (q - a * nsq) / nd, cc = q - a * nsq - b * nd;
-  float2* o = G + (size_t)slot * 3 * nq + (size_t)cc * 3 * nsq + a * nd + b;
-  o[0] = make_float2((float)g[0], (float)g[1]);
-  o[nsq] = make_float2((float)g[2], (float)g[3]);
-  o[2 * nsq] = make_float2((float)g[4], (float)g[5]);
-}
-
-// the float tensor's layout for the degree-g geometry kernels (curved_geometry.hpp): the one rounding
+// Where the geometry kernels (tensor_kernels.hpp) put a point's six values: G32 [slot][layer c][pair][a*nd+b].  The
+// values are formed in double, nodal coefficient and per-cell tensor folded in (point_tensor); this is the one rounding.
 struct TensorOut32
 {
   float2* G;
@@ -333,21 +291,14 @@ int laplacian_f32_refresh(pmg_laplacian op, hipStream_t s)
 {
   if (!op->G32)
     return PMG_OK;
-  const long long nslots = (long long)op->npatch * op->K, n = nslots * op->N;
-  if (op->ng != 8) // a coordinate element of degree >= 2: the FP64 tensor's routine, rounded at the end
-    launch_curved_geometry(op, 0, nslots, TensorOut32{op->G32, op->nd}, s);
-  else if (n > 0)
-    geometry_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nslots, op->nd, op->pcell, op->xgeom,
-                                                                    op->geom_dofmap, op->dphi_geom, op->gweights,
-                                                                    op->kfield, op->dofmap, op->ktensor,
-                                                                    op->G32);
+  launch_geometry(op, 0, (long long)op->npatch * op->K, TensorOut32{op->G32, op->nd}, s); // the FP64 tensor's routine
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }
 
 // The float copy of the reaction vector: in use exactly while the vector and the float tensor both exist (allocated
 // once, rewritten in place by a later set of the reaction or the Robin term; the removal of the last of the two takes
-// it out of use with the vector -- laplacian_diagonal_term_changed)
+// it out of use with the vector -- laplacian_data_changed)
 int laplacian_f32_reaction(pmg_laplacian op, hipStream_t s)
 {
   if (!op->G32 || !op->react)

@@ -1,16 +1,17 @@
-// Geometry tensor of cells with a coordinate element of degree g >= 2 (pmg_laplacian_create_curved), shared by the
-// FP64 tensor (laplacian.hip) and the float tensor (laplacian_f32.hip).  Two kernels, one per source of the tabulation:
+// The kernels that build the geometry tensor, shared by the FP64 tensor (laplacian.hip) and the float tensor
+// (laplacian_f32.hip), and launch_geometry, which picks one:
 //
-//   curved_geometry_kernel  the library's own tensor-product element: one workgroup owns the points of one patch slot
-//                           (several slots at P <= 2, as LiftShape groups cells, so that a wavefront is full), stages
-//                           the cell's 3 (g+1)^3 coordinates in LDS once and sum-factorises dx/dxi: contract along z
-//                           with L and L', then along y, then every thread finishes its own point with 3 * 3 * (g+1)
-//                           FMAs.  A thread per point with the dense table would read 2 * 3 * (g+1)^3 values per point
-//                           (162 at g = 2, 750 at g = 4; the 8-node kernel reads 48).
-//   dense_geometry_kernel   caller tables: the library cannot assume a tensor-product element, so a thread per point
-//                           walks the dense table [3][nq][ng] (jacobian() with ng).
+//   dense_geometry_kernel   a thread per point walks the dense table [3][nq][ng] (jacobian()): the trilinear element
+//                           (NG = 8, 48 table values per point), and caller tables of a coordinate element of degree
+//                           g >= 2 (pmg_laplacian_create_curved), where no tensor product can be assumed (NG = 0).
+//   curved_geometry_kernel  the library's own tensor-product element of degree g >= 2: one workgroup owns the points of
+//                           one patch slot (several slots at P <= 2, as LiftShape groups cells, so that a wavefront is
+//                           full), stages the cell's 3 (g+1)^3 coordinates in LDS once and sum-factorises dx/dxi:
+//                           contract along z with L and L', then along y, then every thread finishes its own point with
+//                           3 * 3 * (g+1) FMAs.  A thread per point with the dense table would read 2 * 3 * (g+1)^3
+//                           values per point (162 at g = 2, 750 at g = 4).
 //
-// Both form adj(J), |det J| and G as geometry_kernel does (point_tensor), write zeros into empty slots, and hand the six
+// Both form adj(J) and |det J| (adjugate) and G from them (point_tensor), write zeros into empty slots, and hand the six
 // values to `out(slot, q, g)`: the caller's layout of the tensor (gpos for the FP64 tensor, the float layout rounds).
 #pragma once
 
@@ -26,29 +27,6 @@ __host__ __device__ constexpr int curved_slot_doubles(int nd, int m) { return 3 
 inline size_t curved_lds_bytes(int nd, int m)
 {
   return sizeof(double) * ((size_t)2 * nd * m + (size_t)curved_slots_per_group(nd * nd * nd) * curved_slot_doubles(nd, m));
-}
-
-// G_q from adj(J) and |det J| at the point q of cell c, as geometry_kernel forms it: w_q / detJ, times the nodal
-// coefficient at the point's own dof, with the per-cell tensor between the two adjugates when one is set
-__device__ __forceinline__ void point_tensor(const double K[3][3], double detJ, int c, int nq, int q,
-                                             const double* __restrict__ w, const double* __restrict__ kfield,
-                                             const int32_t* __restrict__ dofmap, const double* __restrict__ ktensor,
-                                             double g[6])
-{
-  double s = w[q] / detJ;
-  if (kfield)
-    s *= kfield[dofmap[(size_t)c * nq + q]];
-  if (ktensor)
-    tensor_geometry(K, ktensor + (size_t)c * 6, s, g);
-  else
-  {
-    g[0] = (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]) * s;
-    g[1] = (K[1][0] * K[0][0] + K[1][1] * K[0][1] + K[1][2] * K[0][2]) * s;
-    g[2] = (K[2][0] * K[0][0] + K[2][1] * K[0][1] + K[2][2] * K[0][2]) * s;
-    g[3] = (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]) * s;
-    g[4] = (K[2][0] * K[1][0] + K[2][1] * K[1][1] + K[2][2] * K[1][2]) * s;
-    g[5] = (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]) * s;
-  }
 }
 
 // Patch slots [slot0, slot0 + nslots), `cpw` of them per workgroup; M = g + 1.  L, Lp [nd][M]: the coordinate element's
@@ -172,8 +150,10 @@ __global__ void __launch_bounds__(768)
   out(slot, q, g);
 }
 
-// A thread per point with the dense table [3][nq][ng] (caller tables)
-template <typename Out>
+// A thread per point with the dense table [3][nq][NG]; NG = 8: the trilinear element, 0: `ng` nodes (caller tables).
+// Threads of a wavefront walk q, so the dofmap read is contiguous; the kfield gather follows the dofmap like the
+// apply's x.
+template <int NG, typename Out>
 __global__ void dense_geometry_kernel(long long slot0, long long nslots, int nq, int ng,
                                       const int32_t* __restrict__ pcell, const double* __restrict__ xgeom,
                                       const int32_t* __restrict__ geom_dofmap, const double* __restrict__ dphi,
@@ -191,26 +171,29 @@ __global__ void dense_geometry_kernel(long long slot0, long long nslots, int nq,
   if (c >= 0)
   {
     double K[3][3], detJ;
-    jacobian(xgeom, geom_dofmap + (size_t)c * ng, dphi, nq, q, ng, K, detJ);
+    jacobian<NG>(xgeom, geom_dofmap + (size_t)c * (NG ? NG : ng), dphi, nq, q, ng, K, detJ);
     point_tensor(K, detJ, c, nq, q, w, kfield, dofmap, ktensor, g);
   }
   out(slot, q, g);
 }
 
-// The tensor of the slots [slot0, slot0 + nslots) of a degree-g operator (g >= 2) through `out`: the cooperative kernel
-// with the library's own tabulation, the dense one with the caller's
+// The tensor of the slots [slot0, slot0 + nslots) through `out`, the one place that picks the kernel: per point over
+// the 8 nodes of the trilinear element; at degree >= 2 the cooperative kernel with the library's own tabulation, the
+// per-point kernel over the dense table with the caller's
 template <typename Out>
-void launch_curved_geometry(pmg_laplacian op, long long slot0, long long nslots, Out out, hipStream_t s)
+void launch_geometry(pmg_laplacian op, long long slot0, long long nslots, Out out, hipStream_t s)
 {
   if (nslots <= 0)
     return;
-  if (!op->geom_L)
+  if (!op->geom_L) // (the 1-D tables exist at degree >= 2 with the library's tabulation only)
   {
     const long long n = nslots * op->N;
-    dense_geometry_kernel<Out><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(slot0, nslots, op->N, op->ng, op->pcell,
-                                                                          op->xgeom, op->geom_dofmap, op->dphi_geom,
-                                                                          op->gweights, op->kfield, op->dofmap,
-                                                                          op->ktensor, out);
+    auto launch = [&](auto ng) {
+      dense_geometry_kernel<decltype(ng)::value, Out><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(
+          slot0, nslots, op->N, op->ng, op->pcell, op->xgeom, op->geom_dofmap, op->dphi_geom, op->gweights, op->kfield,
+          op->dofmap, op->ktensor, out);
+    };
+    op->ng == 8 ? launch(std::integral_constant<int, 8>{}) : launch(std::integral_constant<int, 0>{});
     return;
   }
   const int cpw = curved_slots_per_group(op->N), threads = curved_threads(op->N), m = op->geom_degree + 1;
@@ -229,3 +212,4 @@ void launch_curved_geometry(pmg_laplacian op, long long slot0, long long nslots,
   }
 }
 } // namespace pmg
+
