@@ -12,6 +12,10 @@
 //   --lift             the right-hand side from the ONE operator: assemble_rhs, apply_lifting, set_bc
 //                      (pmg_laplacian_apply_lifting / _set_bc) -- no second operator with an empty marker, no
 //                      full-volume apply for a product whose input lives on the boundary shell
+//   --neumann          the pure Neumann problem: no Dirichlet marker, the load made compatible with acc::remove_mean, and
+//                      step 1 becomes the solve of that system by the CG with the constant null space
+//                      (pmg_cg_set_nullspace) to rtol 1e-6 in at most max(--cg-its, 1000) iterations; its relative
+//                      residual is printed.  The Chebyshev iterations then smooth the same singular system
 //   --ranks px,py,pz   one process per GPU and brick on the library's RCCL communicator
 //                      (examples/pmg/run_ranks.sh launches the processes)
 #define PMG_AMD_DOLFINX_NAMESPACE
@@ -44,6 +48,7 @@ struct Options : examples::RankOptions
 {
   int n = 16, order = 3, cg_its = 20, cheb_its = 30;
   bool lift = false; // --lift: b through apply_lifting / set_bc on `op` instead of a second, unconstrained operator
+  bool neumann = false; // --neumann: no marker, compatible load, CG with the constant null space
   bool csr = false; // --csr: the eigenvalue estimate on the assembled operator (examples/cg/main.cpp:224-229)
 };
 
@@ -62,7 +67,9 @@ void solve(const Options& o)
   examples::BrickPartition mesh(o.n, o.ranks, o.rank);
   std::vector<double> gll(nd), w(nd);
   check(pmg_gll_table(nd, gll.data(), w.data()));
-  const examples::PartitionLevel lv = mesh.level(order, gll);
+  examples::PartitionLevel lv = mesh.level(order, gll);
+  if (o.neumann) // natural conditions on the whole boundary
+    std::fill(lv.bc_marker.begin(), lv.bc_marker.end(), std::int8_t(0));
   std::shared_ptr<const common::IndexMap> map
       = comm ? std::make_shared<const common::IndexMap>(lv.size_local, lv.num_ghosts, lv.send_indices, lv.recv_indices,
                                                          comm, lv.neighbors, lv.send_counts, lv.recv_counts, o.halo())
@@ -122,6 +129,8 @@ void solve(const Options& o)
         bh[d] = g_bc;
     upload(b, bh);
   }
+  if (o.neumann) // (no marked dof: g = 0 and b is the load alone) 1 . b = 0: compatible
+    acc::remove_mean(b);
 
   DeviceVector b_d(map, 1);
   b_d.set(T{1.0});
@@ -132,9 +141,12 @@ void solve(const Options& o)
 
   // Create distributed CG solver (:245-254)
   dolfinx::acc::CGSolver<DeviceVector> cg(map, 1);
-  cg.set_max_iterations(o.cg_its);
+  cg.set_max_iterations(o.neumann ? std::max(o.cg_its, 1000) : o.cg_its);
   cg.set_tolerance(1e-6);
   cg.store_coefficients(true);
+  cg.set_nullspace(o.neumann);
+  if (o.neumann) // the system itself: b = 1 is the null vector, its projection is zero
+    acc::copy(b_d, b);
 
   auto t0 = std::chrono::steady_clock::now();
   std::unique_ptr<acc::MatrixOperator<T>> mat; // :224: the reference's estimate runs on its MatrixOperator
@@ -149,6 +161,16 @@ void solve(const Options& o)
   hip_check(hipDeviceSynchronize(), "sync");
   const double t_cg = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
+  if (o.neumann)
+  {
+    DeviceVector Ax(map, 1), r(map, 1);
+    op(x, Ax);
+    acc::axpy(r, -1.0, Ax, b); // r = b - A x
+    const T rn = acc::norm(r), bn = acc::norm(b);
+    if (root)
+      std::printf("Neumann CG: %d iterations, |b - A x| / |b| = %.3e (%s)\n", its, rn / bn,
+                  its < std::max(o.cg_its, 1000) ? "converged" : "NOT converged");
+  }
   std::vector<T> eign = cg.compute_eigenvalues();
   std::sort(eign.begin(), eign.end());
   std::array<T, 2> eig_range = {0.1 * eign.back(), 1.1 * eign.back()};
@@ -231,6 +253,8 @@ int main(int argc, char** argv)
         o.csr = true;
       else if (!std::strcmp(argv[i], "--lift"))
         o.lift = true;
+      else if (!std::strcmp(argv[i], "--neumann"))
+        o.neumann = true;
       else if (!std::strcmp(argv[i], "--cheb-its"))
         o.cheb_its = std::atoi(next());
       else if (!std::strcmp(argv[i], "--ranks"))
@@ -247,7 +271,7 @@ int main(int argc, char** argv)
         o.id_file = next();
       else
       {
-        std::cout << "usage: cg [--n cells_per_direction | --ndofs N_per_rank] [--degree P] [--cg-its N] [--cheb-its N] [--csr] [--lift]\n"
+        std::cout << "usage: cg [--n cells_per_direction | --ndofs N_per_rank] [--degree P] [--cg-its N] [--cheb-its N] [--csr] [--lift] [--neumann]\n"
                      "          [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows] [--comm rccl|windows]\n";
         return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
       }

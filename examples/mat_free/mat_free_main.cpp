@@ -15,6 +15,9 @@
 // --robin A keeps the Dirichlet marker on the face x = 0 only and puts a Robin term with alpha = A (1 + y) at the facet
 // points of the other five faces (not in the reference; pmg_laplacian_set_robin); it combines with the three above,
 // and the stencil comparison is left out as well.
+// --neumann removes the Dirichlet marker altogether: the singular, pure Neumann operator (the one pmg_cg_set_nullspace
+// and pmg_amg_set_nullspace are for); with --mat_comp the matrix-free product is compared with the CSR product of that
+// operator on a vector that is not constant.  The stencil comparison is left out as well.
 // --curved G (1..4) bends the box by a fixed smooth map (examples/common/box_mesh.hpp: curved_map) and hands the library
 // a coordinate element of degree G (pmg_laplacian_create_curved through the adapter, which infers G from the geometry
 // dofmap's width); G = 1 is the straight-sided mesh through the mapped vertices.  It combines with every flag above
@@ -43,6 +46,7 @@ int main(int argc, char** argv)
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
   bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false;
+  bool neumann = false; // --neumann: no Dirichlet marker (the singular, pure Neumann operator)
   double reaction = 0.0; // S of --reaction; 0 = no term
   double robin = 0.0;    // A of --robin; 0 = no term
   int curved = 0;        // G of --curved; 0 = the unit box, trilinear
@@ -68,6 +72,8 @@ int main(int argc, char** argv)
       reaction = std::atof(next());
     else if (!std::strcmp(argv[i], "--robin"))
       robin = std::atof(next());
+    else if (!std::strcmp(argv[i], "--neumann"))
+      neumann = true;
     else if (!std::strcmp(argv[i], "--curved"))
       curved = std::atoi(next());
     else if (!std::strcmp(argv[i], "--lift"))
@@ -77,7 +83,7 @@ int main(int argc, char** argv)
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift] [--neumann]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -97,6 +103,9 @@ int main(int argc, char** argv)
 
     if (robin > 0.0) // Dirichlet on x = 0 only; the other five faces carry the Robin term
       examples::keep_marker_on_x0(V.bc_marker, V.x);
+
+    if (neumann) // natural conditions on the whole boundary: the operator the null-space solvers work on
+      std::fill(V.bc_marker.begin(), V.bc_marker.end(), std::int8_t(0));
 
     auto map = std::make_shared<const IndexMap>(V.ndofs, 0);
     device_array<double> kappa(std::vector<double>(mesh.ncells(), 2.0)); // :132
@@ -140,7 +149,7 @@ int main(int argc, char** argv)
       op.handle(map);
       op.set_robin(rb.cells, rb.local_facets, alpha.span()); // the library keeps the vector it builds from it
     }
-    if (kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0)
+    if (kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0 || neumann) // (--neumann: u = 1 is the null vector)
     {
       std::vector<double> kh(V.ndofs);
       // u = 1 lies in the kernel of the operator away from the boundary whatever the coefficient: a vector that
@@ -209,7 +218,7 @@ int main(int argc, char** argv)
       std::printf("CSR Matvec: %d reps, %.3f us per apply\n", nreps, ms * 1e3 / nreps);
       std::printf("CSR nnz = %zu\n", mat.nnz());
       acc::axpy(ec, -1.0, y, zc);
-      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0 || curved)
+      if (degree != 1 || kappa_field || kappa_tensor || reaction > 0.0 || robin > 0.0 || curved || neumann)
       {
         std::printf("Norm of z = %.15e\n", acc::norm(zc));
         std::printf("Norm of error = %.3e\n", acc::norm(ec));

@@ -37,6 +37,14 @@
 //                    element of degree G = 1..4 (pmg_laplacian_create_curved); G = 1: the straight-sided mesh through
 //                    the mapped vertices.  The data of the other flags stay functions of the box coordinates;
 //                    combines with --kappa-field, --kappa-tensor, --reaction, --robin, --fp32-cycle, --csr, --amg, --pcg
+//   --neumann        the pure Neumann problem: no Dirichlet marker on any level, the load made compatible with
+//                    acc::remove_mean, the constant null space set on the outer CG, the coarse CG and the AMG
+//                    (pmg_cg_set_nullspace / pmg_amg_set_nullspace).  On the undeformed unit box with constant
+//                    coefficient the load is that of u = cos pi x cos pi y cos pi z (zero normal derivative on every
+//                    face, zero mean) and --pcg prints the largest nodal error after removing the lumped-mass mean.
+//                    Combines with --kappa-field, --kappa-tensor, --curved, --fp32-cycle, --csr, --graph, --amg-cycles;
+//                    refused with --reaction or --robin (the operator is then not singular) and with --amg on
+//                    several ranks
 //   --check-partition px,py,pz   host-only consistency check of the brick partition (no GPU)
 //   --node-order basix   the dofmaps handed over in basix's cell-local node order (endpoints first), as dolfinx
 //                    gives them to the reference (examples/pmg/main.cpp:83-87); same numbers as without
@@ -99,6 +107,7 @@ struct Options : examples::RankOptions
   bool kappa_tensor = false;   // --kappa-tensor: per-cell tensor, eigenvalues (1, 2 + x, 4) rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z)
   double reaction = 0.0;       // --reaction S: sigma_c = S (1 + x_c); 0 = no term
   double robin = 0.0;          // --robin A: Dirichlet on x = 0 only, alpha = A (1 + y) on the other five faces; 0 = no term
+  bool neumann = false;        // --neumann: no Dirichlet marker, compatible load, constant null space on every solver
   int curved = 0;              // --curved G: the box bent by examples::curved_map, coordinate element of degree G; 0 = the unit box
   bool csr = false;            // --csr [levels]: assembled levels (solve<acc::MatrixOperator<T>>, :285,457-458)
   std::vector<int> csr_levels; // empty with --csr: every level
@@ -147,6 +156,8 @@ void solve(const Options& o)
     V[i] = std::make_shared<Space>(Space{std::make_shared<Element>(Element{{P}}), mesh.level(P, gll)});
     if (o.robin > 0.0) // Dirichlet on x = 0 only; the other five faces carry the Robin term
       examples::keep_marker_on_x0(V[i]->lv.bc_marker, V[i]->lv.x);
+    if (o.neumann) // natural conditions on the whole boundary
+      std::fill(V[i]->lv.bc_marker.begin(), V[i]->lv.bc_marker.end(), std::int8_t(0));
     const examples::PartitionLevel& lv = V[i]->lv;
     if (comm)
       maps[i] = std::make_shared<const common::IndexMap>(lv.size_local, lv.num_ghosts, lv.send_indices,
@@ -171,6 +182,8 @@ void solve(const Options& o)
                   (long long)mesh.global_ndofs(P), lv.size_local, lv.num_ghosts, lv.neighbors.size());
   }
 
+  // --neumann on the undeformed unit box with constant coefficient: the manufactured problem
+  const bool manufactured = o.neumann && !o.curved && !o.kappa_field && !o.kappa_tensor;
   std::vector<std::shared_ptr<FineOperator>> operators(V.size());
   std::vector<std::shared_ptr<DeviceVector>> bs(V.size());
   for (std::size_t i = 0; i < V.size(); i++)
@@ -213,11 +226,15 @@ void solve(const Options& o)
     std::vector<T> fh(lv.ndofs());
     const double pi = M_PI, c2 = (4.0 + 9.0 + 16.0) * pi * pi;
     for (std::int32_t d = 0; d < lv.ndofs(); ++d)
-      fh[d] = c2 * std::sin(2 * pi * lv.x[3 * d]) * std::sin(3 * pi * lv.x[3 * d + 1]) * std::sin(4 * pi * lv.x[3 * d + 2]);
+      fh[d] = manufactured // -div(grad u) of u = cos pi x cos pi y cos pi z
+                  ? 3.0 * pi * pi * std::cos(pi * lv.x[3 * d]) * std::cos(pi * lv.x[3 * d + 1]) * std::cos(pi * lv.x[3 * d + 2])
+                  : c2 * std::sin(2 * pi * lv.x[3 * d]) * std::sin(3 * pi * lv.x[3 * d + 1]) * std::sin(4 * pi * lv.x[3 * d + 2]);
     DeviceVector f(maps[i], 1);
     hip_check(hipMemcpy(f.mutable_array().data(), fh.data(), sizeof(T) * fh.size(), hipMemcpyHostToDevice), "H2D");
     bs[i] = std::make_shared<DeviceVector>(maps[i], 1);
     operators[i]->assemble_rhs(f, *bs[i]); // :289-300
+    if (o.neumann) // 1 . b = 0: the right-hand side is compatible
+      acc::remove_mean(*bs[i]);
   }
 
   // --csr: the listed levels (default: all) as assembled matrices, the reference's solve<acc::MatrixOperator<T>>
@@ -285,6 +302,8 @@ void solve(const Options& o)
       coarse_solver = std::make_shared<CoarseSolverType<T>>(*operators[0], maps[0]);
     if (o.amg_cycles > 0)
       coarse_solver->set_cycles(o.amg_cycles);
+    if (o.neumann)
+      coarse_solver->set_nullspace(true);
     if (root)
       std::printf("AMG coarse solver: %d levels, set-up %.2f s, %s\n", coarse_solver->num_levels(),
                   std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
@@ -309,6 +328,7 @@ void solve(const Options& o)
     coarse_cg = std::make_shared<dolfinx::acc::CGSolver<DeviceVector>>(maps[0], 1);
     coarse_cg->set_max_iterations(60);
     coarse_cg->set_tolerance(1e-5);
+    coarse_cg->set_nullspace(o.neumann);
     check(pmg_multigrid_set_coarse_solver(pmg.handle(), coarse_cg->handle()));
   }
 
@@ -376,6 +396,7 @@ void solve(const Options& o)
     cg.set_tolerance(1e-8);
     // with a Krylov coarse solve inside, the cycle is not a fixed linear operator
     cg.set_flexible(o.coarse_cg || (o.use_amg && o.amg_cycles == 0)); // (stationary AMG cycles: a fixed operator)
+    cg.set_nullspace(o.neumann);
     DeviceVector rhs(maps.back(), 1);
     if (o.random_rhs)
     {
@@ -390,6 +411,8 @@ void solve(const Options& o)
     }
     else
       acc::copy(rhs, *bs.back());
+    if (o.neumann)
+      acc::remove_mean(rhs);
     x.set(0.0);
     const int its = cg.solve(*operators.back(), x, rhs, pmg, false);
     DeviceVector Ax(maps.back(), 1), r(maps.back(), 1);
@@ -399,6 +422,25 @@ void solve(const Options& o)
     if (root)
       std::printf("PCG with V-cycle preconditioner: %d iterations, |b - A x| / |b| = %.3e, Norm of x = %.15e\n", its,
                   rn / bn, xn);
+    if (manufactured && !o.random_rhs)
+    {
+      // the constant of the solution is fixed by a zero integral mean: lumped-mass weights (assemble_rhs of ones), on
+      // the computed solution and on the nodal values of u alike
+      const examples::PartitionLevel& lv = V.back()->lv;
+      std::vector<T> uh(lv.ndofs());
+      for (std::int32_t d = 0; d < lv.ndofs(); ++d)
+        uh[d] = std::cos(M_PI * lv.x[3 * d]) * std::cos(M_PI * lv.x[3 * d + 1]) * std::cos(M_PI * lv.x[3 * d + 2]);
+      DeviceVector ones(maps.back(), 1), mass(maps.back(), 1), u(maps.back(), 1);
+      ones.set(T{1.0});
+      operators.back()->assemble_rhs(ones, mass);
+      hip_check(hipMemcpy(u.mutable_array().data(), uh.data(), sizeof(T) * uh.size(), hipMemcpyHostToDevice), "H2D");
+      acc::remove_mean(u, mass);
+      acc::remove_mean(x, mass);
+      acc::axpy(r, -1.0, u, x); // r = x - u
+      const T err = acc::norm(r, dolfinx::la::Norm::linf);
+      if (root)
+        std::printf("Neumann manufactured solution: max nodal error = %.6e\n", err);
+    }
   }
 
   if (!o.output.empty()) // :369-379 (VTX there; here the fine-level points of this rank as legacy VTK)
@@ -465,6 +507,8 @@ int main(int argc, char** argv)
         o.reaction = std::atof(argv[++i]);
       else if (!std::strcmp(argv[i], "--robin") && i + 1 < argc)
         o.robin = std::atof(argv[++i]);
+      else if (!std::strcmp(argv[i], "--neumann"))
+        o.neumann = true;
       else if (!std::strcmp(argv[i], "--curved") && i + 1 < argc)
       {
         o.curved = std::atoi(argv[++i]);
@@ -537,7 +581,7 @@ int main(int argc, char** argv)
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
                      "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
-                     "           [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G]\n"
+                     "           [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--neumann]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
                      "           [--node-order ascending|basix] [--amg-setup distributed|gathered]\n"
@@ -553,6 +597,12 @@ int main(int argc, char** argv)
     if (o.fp32_cycle && size > 1)
       throw std::runtime_error("--fp32-cycle is single-domain only (--ranks asks for " + std::to_string(size)
                                + " ranks)");
+    if (o.neumann && (o.reaction > 0.0 || o.robin > 0.0))
+      throw std::runtime_error("--neumann with --reaction or --robin: the operator is then not singular, and "
+                               "projecting out the constants would be wrong");
+    if (o.neumann && o.use_amg && size > 1)
+      throw std::runtime_error("--neumann with --amg on several ranks: the replicated and distributed AMG take no "
+                               "null space");
     if (ndofs) // cells per direction of the whole mesh so that a rank holds about ndofs fine dofs
       o.n = examples::cells_for_ndofs(ndofs * (std::size_t)size, o.orders.back());
     if (!check_dims.empty())

@@ -262,6 +262,13 @@ int pmg_vec_squared_norm(pmg_layout l, const double* a, double* result, pmg_stre
 /* norm_type 0 = l2, 1 = linf (max |a_i|; the reference's abs-after-max slip,
  * src/vector.hpp:381-382, is not reproduced). */
 int pmg_vec_norm(pmg_layout l, const double* a, int norm_type, double* result, pmg_stream stream);
+/* Remove the mean (not in the reference): x <- x - (sum x_i) / N with w == NULL, N the number of owned entries over
+ * all ranks; with weights x <- x - (w . x) / (w . 1) -- w the lumped mass (pmg_laplacian_assemble_rhs of ones) gives
+ * a zero integral mean.  The sums run over the owned entries through the layout's reduction path, the subtraction
+ * over size_local + num_ghosts entries (the ghosts stay consistent).  The mean is the quotient sum / N, read by the
+ * subtracting kernel from the device: no host synchronisation, and the call can be captured in a graph.  N is
+ * counted once per layout (on several ranks that first call reduces and reads back: not inside a capture). */
+int pmg_vec_remove_mean(pmg_layout l, double* x, const double* w, pmg_stream stream);
 
 /* ---- matrix-free Laplacian (acc::MatFreeLaplacian, src/laplacian.hpp:284-526)
  * Arguments mirror the reference constructor (:289-297); all arrays are device
@@ -666,6 +673,22 @@ int pmg_cg_solve(pmg_cg s, pmg_laplacian A, double* x, const double* b, pmg_mult
  * linear operator -- a Krylov coarse solver inside -- beta = r_new.(z_new - z_old) / r_old.z_old
  * keeps the recurrence residual honest.  No effect without `precond`. */
 int pmg_cg_set_flexible(pmg_cg s, int flag);
+/* Null space of the operator (not in the reference).  PMG_NULLSPACE_NONE (default): the iteration above.
+ * PMG_NULLSPACE_CONSTANT: the operator has no Dirichlet row, no reaction and no Robin term, so A 1 = 0 -- the pure
+ * Neumann problem.  With Pi = I - 1 1^T / N the solver runs r_0 = Pi (b - A x_0), z = M r,
+ * rz = r . z - (1 . r)(1 . z) / N, p = Pi z + beta p, alpha = rz / (p . y), stops on rz / rz_0 as before and ends with
+ * x <- Pi x: a right-hand side with a constant component is projected, not diverged on, and the result has zero mean.
+ * An iteration issues the launches of the plain one and reads no vector an extra time (the three sums come out of one
+ * pass, the shift is applied inside the direction kernel).  What a solve adds: the projection of r_0, the final
+ * projection of x, and one first-direction kernel (z_0 is formed beside r and p_0 = Pi z_0 written from it, where the
+ * plain loop preconditions straight into p).  Works with pmg_cg_set_flexible and with pmg_cg_solve_matrix; a solver installed with
+ * pmg_multigrid_set_coarse_solver honours its own mode.  Refused with PMG_ERR_INVALID (message in pmg_last_error): an
+ * unknown mode, here; a solve with the mode on and an operator that has a marked row (on any rank), a reaction term
+ * or a Robin term.  pmg_cg_nullspace returns the mode. */
+#define PMG_NULLSPACE_NONE 0
+#define PMG_NULLSPACE_CONSTANT 1
+int pmg_cg_set_nullspace(pmg_cg s, int mode);
+int pmg_cg_nullspace(pmg_cg s);
 /* alphas()/betas(), :118-119; returns the number stored. */
 int pmg_cg_coefficients(pmg_cg s, double* alphas, double* betas, int capacity);
 /* compute_eigenvalues(), :121-142: sorted ascending; returns the count or <0. */
@@ -849,6 +872,21 @@ int pmg_amg_set_krylov(pmg_amg amg, int max_iter, double rtol);
  * solved redundantly on every rank.  0: the whole hierarchy replicated, one all-reduce of a level-0 vector per solve
  * (the redundant work then grows with the rank count).  Same arithmetic up to summation order either way. */
 int pmg_amg_set_distributed_fine_level(pmg_amg amg, int enable);
+/* Null space of the degree-1 operator (PMG_NULLSPACE_NONE, the default, or PMG_NULLSPACE_CONSTANT; single-domain
+ * hierarchies only).  The set-up is untouched -- pmg_amg_export returns the same bytes either way.  With the mode on:
+ *   - the coarsest level is inverted as A_c + gamma v v^T, v = P_{L-2}^T ... P_0^T 1 the ones restricted through the
+ *     hierarchy's own transfers (v = 1 on a hierarchy of one level) and gamma = max diag(A_c) / (v^T v): the exact
+ *     solve of every coarse right-hand side a mean-free residual restricts to, and a rank-one SPD perturbation where
+ *     the level is only nearly singular.  A Cholesky factorisation that fails is PMG_ERR_NUMERIC, not a fall back to
+ *     smoothing; a coarsest level too large to invert keeps smoothing;
+ *   - pmg_amg_cycle and the stationary solve end with x <- x - mean(x), on the device (capturable);
+ *   - the Krylov mode runs its CG with PMG_NULLSPACE_CONSTANT.
+ * Setting PMG_NULLSPACE_NONE restores the plain inverse.  Refused with PMG_ERR_INVALID: an unknown mode, a replicated
+ * or distributed hierarchy, an operator with marked rows, a reaction term or a Robin term -- here, and again by
+ * pmg_amg_solve and pmg_amg_cycle while the mode is on (a term attached to the operator afterwards is refused, not
+ * projected). */
+int pmg_amg_set_nullspace(pmg_amg amg, int mode);
+int pmg_amg_nullspace(pmg_amg amg);
 /* solve(x, b) of src/amg.hpp:67-68; *iterations = CG iterations (or cycles) used. */
 int pmg_amg_solve(pmg_amg amg, double* x, const double* b, int* iterations, pmg_stream stream);
 /* One V-cycle of the hierarchy from a zero initial guess: x = M b (the preconditioner alone). */

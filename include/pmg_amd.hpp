@@ -564,6 +564,20 @@ void scale(Vector& r, S alpha)
 {
   check(pmg_vec_scale(r.map()->layout(), r.mutable_array().data(), (double)alpha, nullptr));
 }
+/// x <- x - (sum x) / N over the owned entries of all ranks, ghosts shifted alike (not in the reference): makes a
+/// right-hand side of the pure Neumann problem compatible, fixes the constant of its solution.
+template <typename Vector>
+void remove_mean(Vector& x)
+{
+  check(pmg_vec_remove_mean(x.map()->layout(), x.mutable_array().data(), nullptr, nullptr));
+}
+/// x <- x - (w . x) / (w . 1): with the lumped mass as w, a zero integral mean.
+template <typename Vector>
+void remove_mean(Vector& x, const Vector& w)
+{
+  require_same_map(x, w);
+  check(pmg_vec_remove_mean(x.map()->layout(), x.mutable_array().data(), w.array().data(), nullptr));
+}
 /// a = b
 template <typename Vector>
 void copy(Vector& a, const Vector& b)
@@ -931,6 +945,11 @@ public:
   void store_coefficients(bool flag) { check(pmg_cg_store_coefficients(_s, flag ? 1 : 0)); } // :116
   /// Polak-Ribiere beta for a V-cycle preconditioner with a Krylov coarse solver (not in the reference).
   void set_flexible(bool flag) { check(pmg_cg_set_flexible(_s, flag ? 1 : 0)); }
+  /// The operator's null space is the constants (pure Neumann problem): projected iteration, zero-mean solution.
+  void set_nullspace(bool constant)
+  {
+    check(pmg_cg_set_nullspace(_s, constant ? PMG_NULLSPACE_CONSTANT : PMG_NULLSPACE_NONE));
+  }
   /// Jacobi-preconditioned CG (:147-222); returns the iteration count.
   template <typename Operator>
   int solve(Operator& A, Vector& x, const Vector& b, bool /*verbose*/ = false)
@@ -1026,6 +1045,12 @@ public:
   /// n AMG cycles from a zero initial guess: a fixed linear operator, no host synchronisation.
   void set_cycles(int n) { check(pmg_amg_set_cycles(_a, n)); }
   void set_smoother_iterations(int k) { check(pmg_amg_set_smoother_iterations(_a, k)); }
+  /// The degree-1 operator's null space is the constants: coarsest level inverted as A_c + gamma v v^T, zero-mean
+  /// output, projected CG in the Krylov mode (single-domain hierarchies).
+  void set_nullspace(bool constant)
+  {
+    check(pmg_amg_set_nullspace(_a, constant ? PMG_NULLSPACE_CONSTANT : PMG_NULLSPACE_NONE));
+  }
   void solve(Vector& x, Vector& y) // src/amg.hpp:67-68
   {
     check(pmg_amg_solve(_a, x.mutable_array().data(), y.array().data(), &_its, nullptr));

@@ -215,7 +215,24 @@ _SIGS = {
     "pmg_chebyshev_solve_matrix": (C.c_int, [vp, vp, vp, vp, vp]),
     "pmg_cg_solve_matrix": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
     "pmg_multigrid_set_level_matrix": (C.c_int, [vp, C.c_int, vp]),
+    "pmg_vec_remove_mean": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_cg_set_nullspace": (C.c_int, [vp, C.c_int]),
+    "pmg_cg_nullspace": (C.c_int, [vp]),
+    "pmg_amg_set_nullspace": (C.c_int, [vp, C.c_int]),
+    "pmg_amg_nullspace": (C.c_int, [vp]),
 }
+
+NULLSPACE_MODES = {None: 0, "none": 0, "constant": 1}  # PMG_NULLSPACE_NONE / PMG_NULLSPACE_CONSTANT
+
+
+def nullspace_mode(mode) -> int:
+    """"constant" | None -> the header's PMG_NULLSPACE_* value; an integer passes through (the library checks it)."""
+    if isinstance(mode, int) and not isinstance(mode, bool):
+        return mode
+    try:
+        return NULLSPACE_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown null space {mode!r}: 'constant' or None") from None
 
 # functions whose int return value is a count, not a status
 _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplacian_geometry_bytes", "pmg_comm_rank", "pmg_comm_size", "pmg_comm_capture_overlaps", "pmg_cg_coefficients", "pmg_cg_compute_eigenvalues", "pmg_multigrid_apply_counts", "pmg_version",
@@ -224,7 +241,7 @@ _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplac
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_laplacian_geometry_degree", "pmg_layout_forward_scatters",
                 "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions",
-                "pmg_chebyshev_recomputed"}
+                "pmg_chebyshev_recomputed", "pmg_cg_nullspace", "pmg_amg_nullspace"}
 
 _lib = None
 

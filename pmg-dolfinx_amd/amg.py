@@ -51,6 +51,16 @@ class AmgSolver:
     def handle(self):
         return self._handle
 
+    def set_nullspace(self, mode):
+        """"constant": the degree-1 operator is the pure Neumann one -- the coarsest level is inverted as
+        A_c + gamma v v^T (v the restricted ones), ``cycle`` and the stationary solve return a zero-mean vector, the
+        Krylov mode runs the projected CG.  None restores the plain inverse.  Single-domain hierarchies only; the
+        set-up (``export``) is unchanged (``pmg_amg_set_nullspace``)."""
+        call("pmg_amg_set_nullspace", self._handle, _lib.nullspace_mode(mode))
+
+    def nullspace(self):
+        return "constant" if call("pmg_amg_nullspace", self._handle) == 1 else None
+
     def solve(self, x: Vector, b: Vector) -> int:
         its = C.c_int()
         call("pmg_amg_solve", self._handle, ptr(x.data), ptr(b.data), C.byref(its), current_stream())

@@ -37,6 +37,15 @@ class CGSolver:
         with a Krylov coarse solver); not in the reference."""
         call("pmg_cg_set_flexible", self._handle, int(bool(val)))
 
+    def set_nullspace(self, mode):
+        """"constant": the operator has no Dirichlet row, reaction or Robin term (pure Neumann) -- the iteration runs
+        projected on the complement of the constants and returns a zero-mean solution.  None: the plain iteration.
+        Not in the reference (``pmg_cg_set_nullspace``)."""
+        call("pmg_cg_set_nullspace", self._handle, _lib.nullspace_mode(mode))
+
+    def nullspace(self):
+        return "constant" if call("pmg_cg_nullspace", self._handle) == 1 else None
+
     def solve(self, A, x: Vector, b: Vector, verbose: bool = False, preconditioner=None) -> int:  # :147-222
         from .matrix import MatrixOperator
 

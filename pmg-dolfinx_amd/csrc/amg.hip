@@ -523,6 +523,7 @@ HostCsr smoothed_prolongator(const HostCsr& A, const std::vector<double>& d, con
 }
 
 // dense inverse of an SPD matrix by Cholesky (n <= a few thousand); returns false if not SPD
+bool dense_spd_inverse(int n, std::vector<double>& L, std::vector<double>& inv);
 bool dense_spd_inverse(const HostCsr& A, std::vector<double>& inv)
 {
   const int n = A.n;
@@ -530,6 +531,11 @@ bool dense_spd_inverse(const HostCsr& A, std::vector<double>& inv)
   for (int i = 0; i < n; ++i)
     for (int k = A.rp[i]; k < A.rp[i + 1]; ++k)
       L[(size_t)i * n + A.ci[k]] = A.v[k];
+  return dense_spd_inverse(n, L, inv);
+}
+// ... of the dense matrix L [n x n] (its lower triangle is read), factorised in place
+bool dense_spd_inverse(int n, std::vector<double>& L, std::vector<double>& inv)
+{
   for (int j = 0; j < n; ++j) // in-place lower Cholesky
   {
     double s = L[(size_t)j * n + j];
@@ -588,8 +594,12 @@ struct pmg_amg_s
   pmg_laplacian op = nullptr; // the degree-1 operator (Krylov mode applies it)
   pmg_layout layout = nullptr;
   std::vector<AmgLevel> levels;
-  double* dense_inv = nullptr; // coarsest level, n x n
+  double* dense_inv = nullptr; // coarsest level, n x n: the inverse in use, one of the two below (nullptr: smooth it)
   int n_coarsest = 0;
+  // Constant null space (pmg_amg_set_nullspace).  Both inverses are kept once built, so a captured cycle never holds
+  // a freed address: the plain one of the set-up (nullptr where its Cholesky stopped) and that of A_c + gamma v v^T.
+  int nullspace = PMG_NULLSPACE_NONE;
+  double *dense_inv_plain = nullptr, *dense_inv_null = nullptr;
   int smoother_its = 2;
   int cycles = 0;       // > 0: stationary mode, that many cycles per solve
   int max_iter = 60;    // Krylov mode (src/amg.hpp:39-40)
@@ -744,7 +754,8 @@ long long amg_capture_state(pmg_amg amg)
 {
   if (amg->cycles <= 0 || (amg->replicated && !amg->layout->comm && amg->layout->allreduce))
     return -1;
-  return ((long long)amg->cycles << 16) ^ amg->smoother_its ^ (amg->replicated ? 1 << 30 : 0) ^ (amg->dist0 ? 1 << 29 : 0);
+  return ((long long)amg->cycles << 16) ^ amg->smoother_its ^ (amg->replicated ? 1 << 30 : 0) ^ (amg->dist0 ? 1 << 29 : 0) ^
+         (amg->nullspace ? 1 << 28 : 0);
 }
 } // namespace pmg
 
@@ -753,6 +764,10 @@ namespace
 // the solve on one rank's vectors of n entries: `A` is the operator of the Krylov mode
 int solve_on(pmg_amg amg, double* x, const double* b, int n, size_t total, const ApplyFn& A, hipStream_t s)
 {
+  // the Krylov mode calls cg_iterate itself, so the refusals of pmg_cg_solve are repeated here: a reaction or Robin
+  // term attached to the operator after pmg_amg_set_nullspace is refused, not projected (flags and a cached count)
+  if (amg->nullspace == PMG_NULLSPACE_CONSTANT)
+    PMG_TRY(laplacian_require_singular(amg->op, "pmg_amg_solve", s));
   if (amg->cycles > 0)
   {
     PMG_TRY(amg_cycle(amg, 0, x, b, s));
@@ -763,6 +778,8 @@ int solve_on(pmg_amg amg, double* x, const double* b, int n, size_t total, const
       PMG_TRY(amg_cycle(amg, 0, amg->xc, l0.b, s));
       launch_add(n, x, amg->xc, s);
     }
+    if (amg->nullspace == PMG_NULLSPACE_CONSTANT) // (single domain: the mode is refused on the replicated forms)
+      PMG_TRY(remove_mean_async(amg->layout, x, nullptr, s));
     amg->last_iterations = amg->cycles;
     return PMG_OK;
   }
@@ -1277,7 +1294,8 @@ int build_hierarchy(pmg_amg amg, HostCsr&& A0, size_t level0_len, double theta0)
     if (Ac.n <= 4096 && dense_spd_inverse(Ac, inv))
     {
       amg->n_coarsest = Ac.n;
-      PMG_TRY(to_device(&amg->dense_inv, inv));
+      PMG_TRY(to_device(&amg->dense_inv_plain, inv));
+      amg->dense_inv = amg->dense_inv_plain;
     }
   }
   tm.lap("upload + dense inverse");
@@ -1720,7 +1738,8 @@ extern "C" int pmg_amg_destroy(pmg_amg amg)
     (void)hipFree(lv.z);
     (void)hipFree(lv.q);
   }
-  (void)hipFree(amg->dense_inv);
+  (void)hipFree(amg->dense_inv_plain);
+  (void)hipFree(amg->dense_inv_null);
   (void)hipFree(amg->xc);
   (void)hipFree(amg->gid);
   (void)hipFree(amg->d0_dinv);
@@ -1793,8 +1812,81 @@ extern "C" int pmg_amg_cycle(pmg_amg amg, double* x, const double* b, pmg_stream
 {
   PMG_REQUIRE(amg && x && b && x != b, "pmg_amg_cycle: bad argument");
   PMG_REQUIRE(!amg->replicated, "pmg_amg_cycle: a replicated hierarchy works on gathered vectors; use pmg_amg_solve");
-  return amg_cycle(amg, 0, x, b, S(stream));
+  if (amg->nullspace == PMG_NULLSPACE_CONSTANT)
+    PMG_TRY(laplacian_require_singular(amg->op, "pmg_amg_cycle", S(stream)));
+  PMG_TRY(amg_cycle(amg, 0, x, b, S(stream)));
+  if (amg->nullspace == PMG_NULLSPACE_CONSTANT)
+    PMG_TRY(remove_mean_async(amg->layout, x, nullptr, S(stream)));
+  return PMG_OK;
 }
+
+// The coarsest-level inverse of a hierarchy whose level 0 has the constants as its null space:
+// v = P_{L-2}^T ... P_0^T 1, the ones restricted through the hierarchy's own transfers, and the inverse of
+// A_c + gamma v v^T with gamma = max diag(A_c) / (v^T v), by the Cholesky factorisation of the plain inverse.
+static int nullspace_inverse(pmg_amg amg, std::vector<double>& inv)
+{
+  std::vector<double> v((size_t)amg->hA[0].n, 1.0);
+  for (const HostCsr& P : amg->hP) // v <- P^T v
+  {
+    std::vector<double> c((size_t)P.m, 0.0);
+    for (int i = 0; i < P.n; ++i)
+      for (int k = P.rp[i]; k < P.rp[i + 1]; ++k)
+        c[P.ci[k]] += P.v[k] * v[i];
+    v.swap(c);
+  }
+  const HostCsr& Ac = amg->hA.back();
+  const int n = Ac.n;
+  PMG_REQUIRE((int)v.size() == n, "pmg_amg_set_nullspace: internal: the transfers do not end on the coarsest level");
+  double vv = 0.0, dmax = 0.0;
+  for (int i = 0; i < n; ++i)
+    vv += v[i] * v[i];
+  for (double d : diagonal(Ac))
+    dmax = std::max(dmax, d);
+  if (!(vv > 0.0) || !(dmax > 0.0))
+    return fail(PMG_ERR_NUMERIC, "pmg_amg_set_nullspace: the restricted ones vanish on the coarsest level");
+  const double gamma = dmax / vv;
+  std::vector<double> D((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i)
+    for (int k = Ac.rp[i]; k < Ac.rp[i + 1]; ++k)
+      D[(size_t)i * n + Ac.ci[k]] = Ac.v[k];
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j)
+      D[(size_t)i * n + j] += gamma * v[i] * v[j];
+  if (!dense_spd_inverse(n, D, inv))
+    return fail(PMG_ERR_NUMERIC, "pmg_amg_set_nullspace: A_c + gamma v v^T of the coarsest level (%d rows) is not "
+                                 "positive definite: the operator's null space is not the constants", n);
+  return PMG_OK;
+}
+
+extern "C" int pmg_amg_set_nullspace(pmg_amg amg, int mode)
+{
+  PMG_REQUIRE(mode == PMG_NULLSPACE_NONE || mode == PMG_NULLSPACE_CONSTANT, "pmg_amg_set_nullspace: unknown mode %d",
+              mode);
+  PMG_REQUIRE(amg, "pmg_amg_set_nullspace: NULL argument");
+  if (mode == PMG_NULLSPACE_CONSTANT)
+  {
+    PMG_REQUIRE(!amg->replicated, "pmg_amg_set_nullspace: the replicated and distributed hierarchies do not take a "
+                                  "null space; the single-domain form (pmg_amg_create) only");
+    PMG_REQUIRE(!amg->layout->multi_rank(), "pmg_amg_set_nullspace: the layout has several ranks; the single-domain "
+                                            "form only");
+    PMG_TRY(laplacian_require_singular(amg->op, "pmg_amg_set_nullspace", nullptr));
+    if (!amg->dense_inv_null && !amg->hA.empty() && amg->hA.back().n <= 4096)
+    {
+      std::vector<double> inv;
+      PMG_TRY(nullspace_inverse(amg, inv));
+      PMG_TRY(to_device(&amg->dense_inv_null, inv));
+      amg->n_coarsest = amg->hA.back().n;
+    }
+    amg->dense_inv = amg->dense_inv_null; // (nullptr: a coarsest level too large to invert keeps smoothing)
+  }
+  else
+    amg->dense_inv = amg->dense_inv_plain;
+  amg->nullspace = mode;
+  PMG_TRY(pmg_cg_set_nullspace(amg->cg, mode)); // the Krylov mode's work object
+  return PMG_OK;
+}
+
+extern "C" int pmg_amg_nullspace(pmg_amg amg) { return amg ? amg->nullspace : PMG_ERR_INVALID; }
 
 extern "C" int pmg_amg_num_levels(pmg_amg amg) { return amg ? (int)amg->levels.size() : -1; }
 

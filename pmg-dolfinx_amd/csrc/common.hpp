@@ -188,6 +188,11 @@ struct pmg_layout_s
   // reduction scratch (owned)
   double* d_partials = nullptr; // [RED_BLOCKS] block partials + [RED_SLOTS] results
   double* h_result = nullptr;   // pinned, [RED_SLOTS]
+  // the constant null space (pmg_vec_remove_mean, pmg_cg_set_nullspace): partials of up to three sums formed in one
+  // pass, [3][RED_BLOCKS] behind the result slots of d_partials (not owned separately), and N, the number of owned
+  // entries over all ranks (-1: not yet counted; layout_global_size)
+  double* d_partials_multi = nullptr;
+  long long global_size = -1;
   long long fwd_scatters = 0; // forward scatters issued (pmg_layout_forward_scatters: exchange bookkeeping tests)
   bool multi_rank() const { return comm != nullptr || allreduce != nullptr; }
   int32_t total() const { return size_local + num_ghosts; }
@@ -322,7 +327,37 @@ void launch_cg_update2(int n, double* x, double* r, const double* p, const doubl
                        const double* d_py, hipStream_t s);
 void launch_cg_direction(int n, double* p, const double* y, double rnorm, const double* d_new,
                          const double* d_sub, hipStream_t s);
-
+// The constant null space (pmg_cg_set_nullspace).  r . z of the projected iteration,
+// r . z - (1 . r)(1 . z) / N: the ONE expression, evaluated on the device for alpha and beta and on the host for the
+// stopping test, with its roundings fixed so that both get the same bits.
+__host__ __device__ inline double projected_rz(double rz, double sum_r, double sum_z, double N)
+{
+#pragma clang fp contract(off)
+  const double t = sum_r * sum_z;
+  return rz - t / N;
+}
+// r . z, 1 . r, 1 . z of the owned entries -> result slots [slot, slot + 3) in one pass; with dinv, z = dinv r is formed
+// and stored in that pass
+int cg_sums3_async(pmg_layout l, const double* r, double* z, const double* dinv, int slot, hipStream_t s);
+// x += alpha p ; r -= alpha y with alpha = projected_rz(d_rz[0..2], N) / *d_py
+void launch_cg_update2_null(int n, double* x, double* r, const double* p, const double* y, const double* d_rz,
+                            double N, const double* d_py, hipStream_t s);
+// p = (z - d_rz[2] / N) + beta p, beta = (projected_rz(d_rz[0..2]) - projected_rz(*d_sub, d_rz[1], sz_old)) / rnorm
+// (d_sub optional: the flexible variant); first: p = z - d_rz[2] / N, p is not read
+void launch_cg_direction_null(int n, double* p, const double* z, bool first, double rnorm, const double* d_rz,
+                              const double* d_sub, double sz_old, double N, hipStream_t s);
+// sum of one host count over the layout's ranks (slot 7); one rank: no device work; several: collective, synchronises
+// and reads back -- refused with `what` inside a stream capture
+int sum_count_over_ranks(pmg_layout l, long long mine, long long* total, const char* what, hipStream_t s);
+// N = owned entries over all ranks (cached in the layout; the first call on several ranks reduces and reads back)
+int layout_global_size(pmg_layout l, double* N, hipStream_t s);
+// x <- x - (sum x) / N, or with weights x <- x - (w . x) / (w . 1), over size_local + num_ghosts entries; no host
+// synchronisation (result slots 6 and 7), capturable
+int remove_mean_async(pmg_layout l, double* x, const double* w, hipStream_t s);
+// the operator can carry the constant null space: no marked row on any rank, no reaction, no Robin term -- else the
+// refusal (PMG_ERR_INVALID), in `who`'s name.  The count of marked rows is reduced once per operator and cached.
+int laplacian_require_singular(pmg_laplacian op, const char* who, hipStream_t s);
+pmg_laplacian matrix_source(pmg_matrix M);
 // laplacian.hip -- the matrix-free operator, as the solvers, the AMG set-up and the assembled operator use it
 int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);

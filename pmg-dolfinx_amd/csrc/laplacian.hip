@@ -548,6 +548,8 @@ extern "C" int pmg_laplacian_create_curved(
                            hipMemcpyDeviceToHost, s));
     PMG_HIP(hipMemcpyAsync(h_x.data(), xgeom, sizeof(double) * h_x.size(), hipMemcpyDeviceToHost, s));
     PMG_HIP(hipStreamSynchronize(s));
+    for (int32_t i = 0; i < layout->size_local; ++i)
+      op->n_marked += h_bc[i] != 0;
     for (size_t i = 0; i < h_gd.size(); ++i) // all (g+1)^3 nodes of every cell
       PMG_REQUIRE(h_gd[i] >= 0 && h_gd[i] < npoints, "pmg_laplacian_create: geometry dofmap entry %d out of range",
                   h_gd[i]);
@@ -1006,6 +1008,25 @@ extern "C" int pmg_laplacian_set_coefficient_tensor(pmg_laplacian op, const doub
 }
 
 extern "C" int pmg_laplacian_has_reaction(pmg_laplacian op) { return op ? (op->has_sigma ? 1 : 0) : -1; }
+
+namespace pmg
+{
+int laplacian_require_singular(pmg_laplacian op, const char* who, hipStream_t s)
+{
+  PMG_REQUIRE(!op->has_sigma, "%s: the constant null space is set, but the operator has a reaction term: it is not "
+                              "singular and a projection would be wrong", who);
+  PMG_REQUIRE(!op->has_robin, "%s: the constant null space is set, but the operator has a Robin term: it is not "
+                              "singular and a projection would be wrong", who);
+  if (op->n_marked_global < 0) // (collective on several ranks: every rank of a null-space solve gets here)
+    PMG_TRY(sum_count_over_ranks(op->layout, op->n_marked, &op->n_marked_global,
+                                 "the first null-space solve with an operator of several ranks counts its marked rows "
+                                 "over the ranks and reads the count back: issue one outside the stream capture",
+                                 s));
+  PMG_REQUIRE(op->n_marked_global == 0, "%s: the constant null space is set, but the operator has %lld marked "
+                                        "(Dirichlet) rows: it is not singular", who, op->n_marked_global);
+  return PMG_OK;
+}
+} // namespace pmg
 
 extern "C" int pmg_laplacian_set_reaction(pmg_laplacian op, const double* sigma, pmg_stream stream)
 {

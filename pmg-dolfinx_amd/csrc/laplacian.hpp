@@ -17,6 +17,9 @@ struct pmg_laplacian_s
   const double* xgeom = nullptr;
   const int32_t* geom_dofmap = nullptr;
   const int8_t* bc = nullptr;
+  // marked entries among the owned ones, counted at creation, and their sum over the ranks (-1: not yet reduced;
+  // laplacian_require_singular)
+  long long n_marked = 0, n_marked_global = -1;
   // cell-local node order of the caller's arrays (pmg_amd.h): the kernels index nodes by ascending coordinate, so a
   // caller in another order gets an ascending copy of its dofmap (op->dofmap then points to it) and its
   // quadrature-indexed arrays are permuted on the way in (tables) and out (get_geometry)

@@ -289,6 +289,7 @@ int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s)
 }
 const double* matrix_diag_inv(pmg_matrix M) { return M->dinv; }
 pmg_layout matrix_layout(pmg_matrix M) { return M->layout; }
+pmg_laplacian matrix_source(pmg_matrix M) { return M->op; }
 
 // The pattern of dolfinx's create_sparsity_pattern from a dofmap (host): dof -> (cell, local node) incidences in
 // ascending cell order, then per row the sorted distinct dofs of its cells (a row no listed cell touches keeps its

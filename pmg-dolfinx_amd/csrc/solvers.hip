@@ -43,6 +43,7 @@ struct pmg_cg_s
   double *r = nullptr, *y = nullptr, *p = nullptr; // src/cg.hpp:101-104
   double* zold = nullptr;                           // flexible variant only
   bool flexible = false;
+  int nullspace = PMG_NULLSPACE_NONE; // pmg_cg_set_nullspace
   std::vector<double> alphas, betas, residuals;
 };
 
@@ -694,6 +695,97 @@ extern "C" int pmg_cg_store_coefficients(pmg_cg cg, int flag)
   return PMG_OK;
 }
 
+namespace
+{
+// cg_iterate for an operator whose null space is the constants (pmg_cg_set_nullspace), with
+// Pi = I - 1 1^T / N:
+//   r_0 = Pi (b - A x_0);  z = M r;  rz = r . z - (1 . r)(1 . z) / N;  p = Pi z + beta p;  alpha = rz / (p . y);
+//   after the loop x <- Pi x.
+// Pi z is never formed on its own: r . z, 1 . r and 1 . z come out of one pass over r and z (cg_sums3_async; the
+// Jacobi branch forms z = dinv r in it), the shift (1 . z) / N is applied inside the direction kernel, and the
+// projected rz is formed from the slots -- on the device for alpha and beta, on the host, by the same expression
+// (projected_rz), for the stopping test.  An iteration issues the launches of the plain loop and keeps its one fetch;
+// a solve adds the projections of r_0 and of x and one first-direction kernel (p_0 = Pi z_0 written from z_0, where
+// the plain loop preconditions straight into p).
+// Flexible variant: r . Pi z_old = r . z_old - (1 . r)(1 . z_old) / N with last iteration's 1 . z carried on the host.
+// Result slots: 1 = p.y, 2 = r.z, 3 = 1.r, 4 = 1.z, 5 = r.z_old.
+int cg_iterate_nullspace(pmg_cg cg, const ApplyFn& A, const double* dinv, const PrecondFn* M, bool flex, double* x,
+                         const double* b, int* iterations, hipStream_t s)
+{
+  pmg_layout l = cg->layout;
+  const int n = l->size_local;
+  double *r = cg->r, *y = cg->y, *p = cg->p;
+  double N = 0.0;
+  PMG_TRY(layout_global_size(l, &N, s));
+  PMG_REQUIRE(N > 0.0, "CG with the constant null space: the layout has no entries");
+  auto precondition_and_sums = [&]() -> int
+  {
+    if (M)
+      PMG_TRY((*M)(y, r));
+    PMG_TRY(cg_sums3_async(l, r, y, M ? nullptr : dinv, 2, s));
+    return PMG_OK;
+  };
+  PMG_TRY(A(x, y));
+  launch_axpy(n, r, -1.0, y, b, s);
+  PMG_TRY(remove_mean_async(l, r, nullptr, s)); // r_0 = Pi (b - A x_0)
+  PMG_TRY(precondition_and_sums());
+  PMG_TRY(reduce_slots_async(l, 2, 3, false, s));
+  launch_cg_direction_null(n, p, y, true, 1.0, red_slot(l, 2), nullptr, 0.0, N, s); // p_0 = Pi z_0
+  if (flex)
+    PMG_HIP(hipMemcpyAsync(cg->zold, y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  double v0[3] = {0, 0, 0};
+  PMG_TRY(fetch_slots(l, 2, 3, v0, s));
+  const double rnorm0 = projected_rz(v0[0], v0[1], v0[2], N);
+  double sz_old = v0[2];
+  double rnorm = rnorm0;
+  const double rtol2 = cg->rtol * cg->rtol;
+  if (!std::isfinite(rnorm0) || rnorm0 < 0.0)
+    return fail(PMG_ERR_NUMERIC, "CG: r . M^-1 r = %g at the start is not a non-negative finite number", rnorm0);
+  int k = 0;
+  while (rnorm0 != 0.0 && k < cg->max_iter)
+  {
+    ++k;
+    Range range("pmg:cg_iteration");
+    PMG_TRY(A(p, y));
+    PMG_TRY(dot_async(l, p, y, 1, s));
+    PMG_TRY(reduce_slots_async(l, 1, 1, false, s));
+    launch_cg_update2_null(n, x, r, p, y, red_slot(l, 2), N, red_slot(l, 1), s);
+    PMG_TRY(precondition_and_sums());
+    if (flex)
+      PMG_TRY(dot_async(l, r, cg->zold, 5, s));
+    PMG_TRY(reduce_slots_async(l, 2, flex ? 4 : 3, false, s));
+    launch_cg_direction_null(n, p, y, false, rnorm, red_slot(l, 2), flex ? red_slot(l, 5) : nullptr, sz_old, N, s);
+    if (flex)
+      PMG_HIP(hipMemcpyAsync(cg->zold, y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    double v[5] = {0, 0, 0, 0, 0};
+    PMG_TRY(fetch_slots(l, 1, flex ? 5 : 4, v, s)); // the iteration's one host synchronisation
+    const double alpha = rnorm / v[0];
+    const double rnorm_new = projected_rz(v[1], v[2], v[3], N);
+    const double beta = (rnorm_new - (flex ? projected_rz(v[4], v[2], sz_old, N) : 0.0)) / rnorm;
+    sz_old = v[3];
+    rnorm = rnorm_new;
+    if (rnorm / rnorm0 < rtol2)
+      break;
+    if (cg->store)
+    {
+      cg->alphas.push_back(alpha);
+      cg->betas.push_back(beta);
+      cg->residuals.push_back(rnorm);
+    }
+  }
+  PMG_TRY(remove_mean_async(l, x, nullptr, s)); // x <- Pi x
+  if (!cg->store || rnorm0 == 0.0)
+  {
+    cg->residuals.clear();
+    cg->residuals.push_back(rnorm);
+  }
+  if (iterations)
+    *iterations = k;
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+} // namespace
+
 namespace pmg
 {
 // src/cg.hpp:147-222 over any operator `A`; the preconditioner is `M` (z = M r) if given, else the
@@ -717,6 +809,8 @@ int cg_iterate(pmg_cg cg, const ApplyFn& A, const double* dinv, const PrecondFn*
   const bool flex = flexible && precond;
   if (flex && !cg->zold)
     PMG_TRY(alloc_vec(l, &cg->zold));
+  if (cg->nullspace == PMG_NULLSPACE_CONSTANT)
+    return cg_iterate_nullspace(cg, A, dinv, M, flex, x, b, iterations, s);
   PMG_TRY(A(x, y)); // :159
   launch_axpy(n, r, -1.0, y, b, s);     // :160
   PMG_TRY(precondition(p, r));          // :161
@@ -798,6 +892,8 @@ extern "C" int pmg_cg_solve(pmg_cg cg, pmg_laplacian A, double* x, const double*
   PMG_REQUIRE(cg && A && x && b, "pmg_cg_solve: NULL argument");
   PMG_REQUIRE(laplacian_layout(A) == cg->layout, "pmg_cg_solve: operator and solver layouts differ");
   hipStream_t s = S(stream);
+  if (cg->nullspace != PMG_NULLSPACE_NONE)
+    PMG_TRY(laplacian_require_singular(A, "pmg_cg_solve", s));
   const ApplyFn apply = [A, s](double* in, double* out) { return laplacian_apply(A, in, out, s); };
   // the V-cycle from a zero initial guess: folded into the smoothers' x_zero path, no memset of z
   const PrecondFn vcycle = [precond, s](double* z, const double* r) -> int
@@ -816,6 +912,8 @@ extern "C" int pmg_cg_solve_matrix(pmg_cg cg, pmg_matrix M, double* x, const dou
   PMG_REQUIRE(cg && M && x && b, "pmg_cg_solve_matrix: NULL argument");
   PMG_REQUIRE(matrix_layout(M) == cg->layout, "pmg_cg_solve_matrix: matrix and solver layouts differ");
   hipStream_t s = S(stream);
+  if (cg->nullspace != PMG_NULLSPACE_NONE)
+    PMG_TRY(laplacian_require_singular(matrix_source(M), "pmg_cg_solve_matrix", s));
   const ApplyFn apply = [M, s](double* in, double* out) { return matrix_apply(M, in, out, s); };
   const PrecondFn vcycle = [precond, s](double* z, const double* r) -> int
   {
@@ -833,6 +931,17 @@ extern "C" int pmg_cg_set_flexible(pmg_cg cg, int flag)
   cg->flexible = flag != 0;
   return PMG_OK;
 }
+
+extern "C" int pmg_cg_set_nullspace(pmg_cg cg, int mode)
+{
+  PMG_REQUIRE(mode == PMG_NULLSPACE_NONE || mode == PMG_NULLSPACE_CONSTANT, "pmg_cg_set_nullspace: unknown mode %d",
+              mode);
+  PMG_REQUIRE(cg, "pmg_cg_set_nullspace: NULL argument");
+  cg->nullspace = mode;
+  return PMG_OK;
+}
+
+extern "C" int pmg_cg_nullspace(pmg_cg cg) { return cg ? cg->nullspace : PMG_ERR_INVALID; }
 
 extern "C" int pmg_cg_coefficients(pmg_cg cg, double* alphas, double* betas, int capacity)
 {

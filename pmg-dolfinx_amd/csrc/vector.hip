@@ -694,6 +694,192 @@ __global__ void fold_kernel(int nb, const double* __restrict__ partials, double*
   if (threadIdx.x == 0)
     out[0] = acc;
 }
+
+// the same fold for several sums at once: block q folds the q-th run of partials (runs `stride` apart) into out[q]
+__global__ void fold_multi_kernel(int nb, const double* __restrict__ partials, double* __restrict__ out, int stride)
+{
+  partials += (size_t)blockIdx.x * stride;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x)
+    acc += partials[i];
+  acc = block_reduce<false>(acc);
+  if (threadIdx.x == 0)
+    out[blockIdx.x] = acc;
+}
+
+// ---- several sums out of ONE pass (the constant null space: pmg_vec_remove_mean, cg_iterate) ----
+// F::NQ quantities per entry, accumulated per lane, one wavefront-level reduction per quantity; the partials of
+// quantity q are partials[q * stride + block], folded by fold_multi_kernel with one block per quantity.
+template <typename F>
+__global__ void multi_partial_kernel(int n, F f, double* __restrict__ partials, int stride, int vec)
+{
+  double acc[F::NQ];
+  for (int q = 0; q < F::NQ; ++q)
+    acc[q] = 0.0;
+  if (vec)
+  {
+    const int n2 = n / 2;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += gridDim.x * blockDim.x)
+      f.pair(i, acc);
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+      f.one(n - 1, acc);
+  }
+  else
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+      f.one(i, acc);
+  for (int q = 0; q < F::NQ; ++q)
+  {
+    const double v = block_reduce<false>(acc[q]);
+    if (threadIdx.x == 0)
+      partials[(size_t)q * stride + blockIdx.x] = v;
+    __syncthreads(); // block_reduce's shared words are reused by the next quantity
+  }
+}
+struct SumF
+{ // sum x
+  static constexpr int NQ = 1;
+  const double* x;
+  __device__ void pair(int i, double* acc) const
+  {
+    const double2 v = CD2(x)[i];
+    acc[0] += v.x + v.y;
+  }
+  __device__ void one(int i, double* acc) const { acc[0] += x[i]; }
+};
+struct WeightedSumF
+{ // w . x, w . 1
+  static constexpr int NQ = 2;
+  const double* w;
+  const double* x;
+  __device__ void pair(int i, double* acc) const
+  {
+    const double2 vw = CD2(w)[i], vx = CD2(x)[i];
+    acc[0] += vw.x * vx.x + vw.y * vx.y;
+    acc[1] += vw.x + vw.y;
+  }
+  __device__ void one(int i, double* acc) const
+  {
+    acc[0] += w[i] * x[i];
+    acc[1] += w[i];
+  }
+};
+template <bool JACOBI>
+struct CgSums3F
+{ // r . z, 1 . r, 1 . z;  JACOBI: z = dinv r is formed and stored here (CgUpdateF's fused preconditioner)
+  static constexpr int NQ = 3;
+  const double* r;
+  double* z;
+  const double* dinv;
+  __device__ void pair(int i, double* acc) const
+  {
+    const double2 vr = CD2(r)[i];
+    double2 vz;
+    if constexpr (JACOBI)
+    {
+      const double2 vd = CD2(dinv)[i];
+      vz = make_double2(vd.x * vr.x, vd.y * vr.y);
+      D2(z)[i] = vz;
+    }
+    else
+      vz = CD2(z)[i];
+    acc[0] += vr.x * vz.x + vr.y * vz.y;
+    acc[1] += vr.x + vr.y;
+    acc[2] += vz.x + vz.y;
+  }
+  __device__ void one(int i, double* acc) const
+  {
+    const double vr = r[i];
+    double vz;
+    if constexpr (JACOBI)
+      z[i] = vz = dinv[i] * vr;
+    else
+      vz = z[i];
+    acc[0] += vr * vz;
+    acc[1] += vr;
+    acc[2] += vz;
+  }
+};
+template <bool NT>
+struct ShiftF
+{ // x -= *num / den, den = *d_den or the host's count: the mean is a quotient, formed once per lane
+  double* x;
+  const double* num;
+  const double* d_den;
+  double den;
+  __device__ double mean() const { return *num / (d_den ? *d_den : den); }
+  __device__ void pair(int i) const
+  {
+    const double m = mean();
+    double2 v = ld2<NT>(x, i);
+    v.x -= m;
+    v.y -= m;
+    st2<NT>(x, i, v);
+  }
+  __device__ void one(int i) const { x[i] -= mean(); }
+};
+struct CgUpdate2NullF
+{ // CgUpdate2F with alpha = (r . z of the projected iteration, from the slots) / p . y
+  double* x;
+  double* r;
+  const double* p;
+  const double* y;
+  const double* d_rz; // r . z, 1 . r, 1 . z
+  double N;
+  const double* d_py;
+  __device__ double alpha() const { return projected_rz(d_rz[0], d_rz[1], d_rz[2], N) / *d_py; }
+  __device__ void pair(int i) const
+  {
+    const double a = alpha();
+    double2 vx = D2(x)[i], vr = D2(r)[i], vy = CD2(y)[i], vp = CD2(p)[i];
+    D2(x)[i] = make_double2(vx.x + a * vp.x, vx.y + a * vp.y);
+    D2(r)[i] = make_double2(vr.x - a * vy.x, vr.y - a * vy.y);
+  }
+  __device__ void one(int i) const
+  {
+    const double a = alpha();
+    x[i] += a * p[i];
+    r[i] -= a * y[i];
+  }
+};
+template <bool FIRST>
+struct CgDirectionNullF
+{ // p = (z - (1 . z) / N) + beta p;  FIRST: p = z - (1 . z) / N, p is not read.
+  // beta = (rz_new - rz_sub) / rnorm with rz_new = r . z - (1 . r)(1 . z) / N from the slots and, for the flexible
+  // variant, rz_sub = r . z_old - (1 . r) sz_old / N (d_sub; sz_old = 1 . z_old, the host's from the last fetch)
+  double* p;
+  const double* z;
+  double rnorm;
+  const double* d_rz; // r . z, 1 . r, 1 . z
+  const double* d_sub;
+  double sz_old, N;
+  __device__ double beta() const
+  {
+    const double rz_new = projected_rz(d_rz[0], d_rz[1], d_rz[2], N);
+    const double rz_sub = d_sub ? projected_rz(*d_sub, d_rz[1], sz_old, N) : 0.0;
+    return (rz_new - rz_sub) / rnorm;
+  }
+  __device__ void pair(int i) const
+  {
+    const double shift = d_rz[2] / N;
+    const double2 vz = CD2(z)[i];
+    if constexpr (FIRST)
+      D2(p)[i] = make_double2(vz.x - shift, vz.y - shift);
+    else
+    {
+      const double b = beta();
+      const double2 vp = D2(p)[i];
+      D2(p)[i] = make_double2(b * vp.x + (vz.x - shift), b * vp.y + (vz.y - shift));
+    }
+  }
+  __device__ void one(int i) const
+  {
+    const double shift = d_rz[2] / N;
+    if constexpr (FIRST)
+      p[i] = z[i] - shift;
+    else
+      p[i] = beta() * p[i] + (z[i] - shift);
+  }
+};
 } // namespace
 
 namespace pmg
@@ -890,7 +1076,105 @@ void launch_cg_direction(int n, double* p, const double* y, double rnorm, const 
   ew_launch(n, aligned16(p) && aligned16(y), CgDirectionF{p, y, rnorm, d_new, d_sub}, s);
 }
 
+void launch_cg_update2_null(int n, double* x, double* r, const double* p, const double* y, const double* d_rz,
+                            double N, const double* d_py, hipStream_t s)
+{
+  bool v = aligned16(x) && aligned16(r) && aligned16(y) && aligned16(p);
+  ew_launch(n, v, CgUpdate2NullF{x, r, p, y, d_rz, N, d_py}, s);
+}
+void launch_cg_direction_null(int n, double* p, const double* z, bool first, double rnorm, const double* d_rz,
+                              const double* d_sub, double sz_old, double N, hipStream_t s)
+{
+  const bool v = aligned16(p) && aligned16(z);
+  if (first)
+    ew_launch(n, v, CgDirectionNullF<true>{p, z, rnorm, d_rz, d_sub, sz_old, N}, s);
+  else
+    ew_launch(n, v, CgDirectionNullF<false>{p, z, rnorm, d_rz, d_sub, sz_old, N}, s);
+}
+
 double* red_slot(pmg_layout l, int slot) { return l->d_partials + RED_BLOCKS + slot; }
+
+// F's sums over the owned entries -> the slots [slot, slot + F::NQ), stream-ordered: one pass, one fold
+template <typename F>
+static int sums_async(pmg_layout l, F f, bool vec, int slot, hipStream_t s)
+{
+  PMG_REQUIRE(slot >= 0 && slot + F::NQ <= RED_SLOTS, "sums_async: bad slot range");
+  const int n = l->size_local;
+  int nb = ew_blocks((n + 1) / 2);
+  if (nb > RED_BLOCKS)
+    nb = RED_BLOCKS;
+  multi_partial_kernel<<<nb, RED_THREADS, 0, s>>>(n, f, l->d_partials_multi, RED_BLOCKS, vec ? 1 : 0);
+  fold_multi_kernel<<<F::NQ, RED_THREADS, 0, s>>>(nb, l->d_partials_multi, red_slot(l, slot), RED_BLOCKS);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+// r . z, 1 . r, 1 . z of the owned entries -> slots [slot, slot + 3); with dinv, z = dinv r is written in the same pass
+int cg_sums3_async(pmg_layout l, const double* r, double* z, const double* dinv, int slot, hipStream_t s)
+{
+  if (dinv)
+    return sums_async(l, CgSums3F<true>{r, z, dinv}, aligned16(r) && aligned16(z) && aligned16(dinv), slot, s);
+  return sums_async(l, CgSums3F<false>{r, z, nullptr}, aligned16(r) && aligned16(z), slot, s);
+}
+
+// The sum of one host count over the ranks of the layout, through result slot 7 (no solver's).  One rank: the count
+// itself, no device work.  Several ranks: collective; it synchronises the stream and reads back, so it is refused, in
+// `what`'s words, inside a stream capture.
+int sum_count_over_ranks(pmg_layout l, long long mine, long long* total, const char* what, hipStream_t s)
+{
+  if (!l->multi_rank())
+  {
+    *total = mine;
+    return PMG_OK;
+  }
+  PMG_TRY(not_capturing(s, what));
+  PMG_HIP(hipStreamSynchronize(s)); // h_result may still be the source or target of an earlier copy
+  l->h_result[7] = (double)mine;
+  PMG_HIP(hipMemcpyAsync(red_slot(l, 7), l->h_result + 7, sizeof(double), hipMemcpyHostToDevice, s));
+  PMG_HIP(hipStreamSynchronize(s));
+  PMG_TRY(reduce_slots_async(l, 7, 1, false, s));
+  double v = 0.0;
+  PMG_TRY(fetch_slots(l, 7, 1, &v, s));
+  *total = (long long)(v + 0.5);
+  return PMG_OK;
+}
+
+// N, the number of owned entries over all ranks: obtained once per layout and cached
+int layout_global_size(pmg_layout l, double* N, hipStream_t s)
+{
+  if (l->global_size < 0)
+    PMG_TRY(sum_count_over_ranks(l, l->size_local, &l->global_size,
+                                 "the first null-space operation on a layout of several ranks counts the dofs over "
+                                 "the ranks and reads the count back: issue one outside the stream capture",
+                                 s));
+  *N = (double)l->global_size;
+  return PMG_OK;
+}
+
+// x <- x - mean over size_local + num_ghosts entries; the sums are the owned entries' (slots 6, 7: no solver's)
+int remove_mean_async(pmg_layout l, double* x, const double* w, hipStream_t s)
+{
+  double N = 0.0;
+  if (!w)
+  {
+    PMG_TRY(layout_global_size(l, &N, s));
+    if (N == 0.0)
+      return PMG_OK;
+    PMG_TRY(sums_async(l, SumF{x}, aligned16(x), 6, s));
+    PMG_TRY(reduce_slots_async(l, 6, 1, false, s));
+  }
+  else
+  {
+    PMG_TRY(sums_async(l, WeightedSumF{w, x}, aligned16(x) && aligned16(w), 6, s));
+    PMG_TRY(reduce_slots_async(l, 6, 2, false, s));
+  }
+  const double* den = w ? red_slot(l, 7) : nullptr;
+  if (streams(l->total()))
+    ew_launch(l->total(), aligned16(x), ShiftF<true>{x, red_slot(l, 6), den, N}, s);
+  else
+    ew_launch(l->total(), aligned16(x), ShiftF<false>{x, red_slot(l, 6), den, N}, s);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
 
 // local (this rank) dot of the owned entries -> result slot, stream-ordered
 int dot_async(pmg_layout l, const double* a, const double* b, int slot, hipStream_t s)
@@ -980,7 +1264,7 @@ extern "C" int pmg_layout_create(pmg_layout* out, int32_t size_local, int32_t nu
   l->exchange = exchange;
   l->allreduce = allreduce_sum;
   l->user = user;
-  hipError_t e = hipMalloc(&l->d_partials, sizeof(double) * (RED_BLOCKS + RED_SLOTS));
+  hipError_t e = hipMalloc(&l->d_partials, sizeof(double) * (RED_BLOCKS + RED_SLOTS + 3 * RED_BLOCKS));
   if (e == hipSuccess)
     e = hipHostMalloc(&l->h_result, sizeof(double) * RED_SLOTS, hipHostMallocDefault);
   if (e != hipSuccess)
@@ -988,6 +1272,7 @@ extern "C" int pmg_layout_create(pmg_layout* out, int32_t size_local, int32_t nu
     delete l;
     return fail(PMG_ERR_HIP, "pmg_layout_create: %s", hipGetErrorString(e));
   }
+  l->d_partials_multi = l->d_partials + RED_BLOCKS + RED_SLOTS;
   *out = l;
   return PMG_OK;
 }
@@ -1192,6 +1477,12 @@ extern "C" int pmg_vec_pointwise_mult(pmg_layout l, double* w, const double* x, 
   launch_pointwise(l->size_local, w, x, y, S(stream));
   PMG_HIP(hipGetLastError());
   return PMG_OK;
+}
+
+extern "C" int pmg_vec_remove_mean(pmg_layout l, double* x, const double* w, pmg_stream stream)
+{
+  PMG_REQUIRE(l && x, "pmg_vec_remove_mean: NULL argument");
+  return remove_mean_async(l, x, w, S(stream));
 }
 
 extern "C" int pmg_vec_inner_product(pmg_layout l, const double* a, const double* b,

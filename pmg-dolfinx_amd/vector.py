@@ -476,6 +476,17 @@ class Vector:
     def set(self, v: float):  # :109-115
         call("pmg_vec_set", self.layout.handle, ptr(self._x), float(v), current_stream())
 
+    def remove_mean(self, weights: "Vector | None" = None):
+        """x <- x - (sum x) / N over the owned entries of all ranks, or with ``weights`` (the lumped mass:
+        ``assemble_rhs`` of ones) x <- x - (w . x) / (w . 1); the ghosts are shifted alike.  No host synchronisation
+        (``pmg_vec_remove_mean``; not in the reference)."""
+        if weights is not None and weights.layout is not self.layout and (
+                weights.layout.size_local != self.layout.size_local
+                or weights.layout.num_ghosts != self.layout.num_ghosts):
+            raise RuntimeError("Incompatible vector sizes")  # the kernel reads size_local entries of both
+        call("pmg_vec_remove_mean", self.layout.handle, ptr(self._x), ptr(weights.data) if weights is not None else vp(0),
+             current_stream())
+
     def copy_from_host(self, other):  # :117-122 (owned part only)
         import torch
 
