@@ -99,7 +99,10 @@ def _rank_checks(pm, rank, world, n, dims, orders, comm=None, cell_frames=None):
     H = pm.PoissonHierarchy(n, orders, kappa=2.0, cheb_its=k, proc_dims=dims, rank=rank, size=world, warp=warp,
                             comm=comm, cell_frames=cell_frames)
     out = {"eig": H.eig_ranges, "ghosts": [lv.num_ghosts for lv in H.levels],
-           "neighbors": [len(lv.neighbors) for lv in H.levels]}
+           "neighbors": [len(lv.neighbors) for lv in H.levels],
+           "halo_entries": [(sum(lv.send_counts), sum(lv.recv_counts)) for lv in H.levels],
+           "cell_lists": [(len(lv.lcells), len(lv.bcells)) for lv in H.levels],
+           "launches": [op.launches_per_apply() for op in H.operators]}
     # operator apply on every level against the global oracle
     gm = po.BoxMesh(n, warp=warp)
     errs = []
@@ -334,10 +337,23 @@ def test_ranks_share_one_gpu(dims, n, built):
     _assert_rank_results(_run_ranks(_worker, world, (n, dims, orders)))
 
 
-@pytest.mark.parametrize("route", ["windows", "window-comm", "windows-split"])
-@pytest.mark.parametrize("dims,n", [((1, 1, 2), (3, 4, 8)), ((1, 2, 2), (3, 4, 6)),
-                                    ((1, 1, 3), (3, 4, 9))])  # a chain: the middle rank has two neighbours, the ends
-                                                               # one -- a rank's place in its neighbours' lists differs
+_WINDOW_MESHES = [((1, 1, 2), (3, 4, 8)), ((1, 2, 2), (3, 4, 6)),
+                  ((1, 1, 3), (3, 4, 9))]  # a chain: the middle rank has two neighbours, the ends
+                                           # one -- a rank's place in its neighbours' lists differs
+# A halo of several blocks: 16 x 16 x 2 cells per rank, the rank boundary a face of 65^2 degree-4 dofs.  A rank keeps
+# one layer of ghost cells, so the degree-4 exchange is 5 planes one way (21 125 entries: 6 blocks of the one-launch
+# kernel, 11 of the split ones) and 4 planes the other (16 900: 5 and 9); degree 2 moves 3 267 / 2 178 (one block of
+# the one-launch kernel, 2 of the split ones).  Every exchange of the degree-4 level counts its blocks in, the split
+# ones of degree 2 as well.  Two cell layers per rank and not one: with one, all
+# owned cells of the upper rank touch the ghost plane, its interior list is empty and laplacian_single_launch (two
+# merged launches walked as one) does not hold there.
+_MULTIBLOCK_MESH = ((1, 1, 2), (16, 16, 4))
+_WINDOW_CASES = ([pytest.param(d, n, r, id=f"dims{i}-n{i}-{r}") for r in ("windows", "window-comm", "windows-split")
+                  for i, (d, n) in enumerate(_WINDOW_MESHES)]
+                 + [pytest.param(*_MULTIBLOCK_MESH, r, id=f"dims3-n3-{r}") for r in ("windows", "windows-split")])
+
+
+@pytest.mark.parametrize("dims,n,route", _WINDOW_CASES)
 def test_ranks_share_one_gpu_through_halo_windows(dims, n, route, built):
     """The same checks with the halo moved by the library's windows: every rank (a process) stores its packed
     values straight into its neighbours' interprocess-mapped windows and waits on their flags -- the whole protocol of
@@ -346,7 +362,9 @@ def test_ranks_share_one_gpu_through_halo_windows(dims, n, route, built):
     made of windows -- no transport library at all, every reduction (the dot products of CG, the sums of whole level
     vectors in the replicated coarse solve: chunked) two kernels of direct stores and flags; "windows-split": the levels
     of these small meshes take their exchange whole, in one launch in front of one launch over all cells (round 4,
-    laplacian_single_launch) -- this route runs them the way a large level runs, PMG_FUSED_EXCHANGE=0.  Not run with the ranks as threads of one process: eight
+    laplacian_single_launch) -- this route runs them the way a large level runs, PMG_FUSED_EXCHANGE=0.  The last mesh
+    (_MULTIBLOCK_MESH) repeats the two-rank checks with a halo of several blocks, so that cycles and graph replays run
+    on the count-in path of the window kernels, whole and split.  Not run with the ranks as threads of one process: eight
     streams share the process's four hardware queues, and a kernel waiting for a flag at the head of a queue would
     hold back the very kernel that raises it."""
     import torch
@@ -361,6 +379,12 @@ def test_ranks_share_one_gpu_through_halo_windows(dims, n, route, built):
         assert out["graph_replays"] >= 7 and out["graph_vs_eager"] < 1e-12, (out["graph_replays"], out["graph_vs_eager"])
         if route == "window-comm":
             assert out["long_allreduce_ok"] and out["long_allgather_ok"]
+        if (dims, n) == _MULTIBLOCK_MESH:
+            # the degree-4 exchange is more than one block of either window kernel, both ways, and the level has the
+            # launch plan that takes the one-launch form on route "windows": an interior and a boundary list, each
+            # merged into one atomic launch (many patches of several colours each)
+            assert min(out["halo_entries"][-1]) > 4096, out["halo_entries"]
+            assert min(out["cell_lists"][-1]) > 0 and out["launches"][-1] == 2, (out["cell_lists"], out["launches"])
 
 
 # ---------------------------------------------------------------------------------------------
