@@ -80,7 +80,7 @@ class AmgCycle:
 
 
 # ---- the set-up restated ----------------------------------------------------------------------
-# Written from the algorithm as the header of csrc/amg.hip states it (smoothed aggregation: strength
+# Written from the algorithm as the header of csrc/amg_setup.hpp states it (smoothed aggregation: strength
 # graph |a_ij| >= theta sqrt(a_ii a_jj), greedy aggregation in three passes, piecewise-constant
 # tentative prolongator normalised by 1 / sqrt(size), P = (I - 4 / (3 rho) D^-1 A) T, Galerkin
 # product, rho = 1.05 x 20 steps of the power method on D^-1 A), in plain numpy/scipy.  The tests
