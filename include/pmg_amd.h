@@ -583,6 +583,24 @@ int pmg_laplacian_degree(pmg_laplacian op);
  * (pmg_laplacian_set_coefficient_tensor) is constant over a cell and is carried by both modes. */
 int pmg_laplacian_is_affine(pmg_laplacian op);
 int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode);
+/* Recomputed tensor (not in the reference).  Where the coordinate element is trilinear the Jacobian down a column of
+ * quadrature points is linear in the column's coordinate, so the degree-1 and degree-2 apply kernels can form G_q in
+ * their layer march from 24 coefficients per cell (192 bytes) instead of streaming 48 bytes per point; same result to
+ * rounding (about 1e-15 of max |y|).  G is still built and kept: the diagonal, pmg_laplacian_get_geometry, the
+ * assembled matrix, the AMG set-up and the FP32 cycle read it.
+ * An operator is eligible when it was created without caller tables and with geometry degree 1, its degree is 1 or 2,
+ * the geometry is resident (no batching), the geometry mode is 0, and neither a nodal coefficient field nor a per-cell
+ * coefficient tensor is set; eligibility is evaluated at every application, so setting a field falls back to the
+ * stream and removing it returns to the recomputed form.
+ * mode -1 (default): automatic -- on at both degrees (profiles/tensor_recompute.md); 0: always stream;
+ * 1: recompute where eligible -- PMG_ERR_INVALID with the reason if the operator is not eligible now, nothing changes.
+ * PMG_TENSOR_RECOMPUTE=0 / 1 in the environment, read at creation, sets mode 0 / 1 (1 without the error: an ineligible
+ * operator streams); a measurement switch like PMG_STREAM_POLICY.  The first choice of the form builds the
+ * coefficients on the default stream: not inside a stream capture.  A graph captured by pmg_multigrid_set_graph is
+ * re-captured when the choice changes.
+ * pmg_laplacian_tensor_recomputed: 1 if the next application recomputes, 0 if it streams, -1 for NULL. */
+int pmg_laplacian_set_tensor_recompute(pmg_laplacian op, int mode);
+int pmg_laplacian_tensor_recomputed(pmg_laplacian op);
 /* Geometry batching (src/laplacian.hpp:383-396; examples/mat_free/main.cpp:34-50 --batch_size):
  * with batch_cells > 0 the tensor G is not kept; every application recomputes it for about
  * batch_cells cells at a time (rounded up to whole patches) into a buffer of that size, right

@@ -802,6 +802,14 @@ public:
       check(pmg_laplacian_set_robin(_op, 0, nullptr, nullptr, nullptr, nullptr));
   }
   bool has_robin() const { return _op && pmg_laplacian_has_robin(_op) == 1; }
+  /// Recomputed tensor (pmg_laplacian_set_tensor_recompute): -1 automatic, 0 always stream, 1 recompute (an error on
+  /// an operator that cannot).  The handle must exist.
+  void set_tensor_recompute(int mode)
+  {
+    if (!_op)
+      throw std::runtime_error("MatFreeLaplacian: set_tensor_recompute before the operator has seen an index map");
+    check(pmg_laplacian_set_tensor_recompute(_op, mode));
+  }
   int degree() const { return _degree; }
   int geometry_degree() const { return _geom_degree; }
 

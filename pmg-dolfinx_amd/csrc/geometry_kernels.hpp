@@ -82,6 +82,34 @@ __global__ void affine_geometry_kernel(long long nslots, int gdeg, const int32_t
     Gaff[slot * 6 + d] = g[d];
 }
 
+// Monomial coefficients of a trilinear cell's map, x = sum c_ijk xi^i eta^j zeta^k on [0,1]^3, from its eight vertices
+// v[4 i + 2 j + l]: Ccell[slot][4 i + 2 j + k][3]; an empty slot holds zeros.  Read by the recomputed form of the apply
+// (TensorStream, stiffness_layer.hpp).
+__global__ void cell_coefficient_kernel(long long nslots, const int32_t* __restrict__ pcell,
+                                        const double* __restrict__ xgeom, const int32_t* __restrict__ geom_dofmap,
+                                        double* __restrict__ Ccell)
+{
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= nslots * 3)
+    return;
+  const long long slot = gid / 3;
+  const int i = (int)(gid - slot * 3);
+  const int c = pcell[slot];
+  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c >= 0)
+    for (int k = 0; k < 8; ++k)
+      v[k] = xgeom[3 * (size_t)geom_dofmap[(size_t)c * 8 + k] + i];
+  double* o = Ccell + slot * 24 + i;
+  o[0] = v[0];
+  o[3] = v[1] - v[0];                                              // zeta
+  o[6] = v[2] - v[0];                                              // eta
+  o[9] = (v[3] - v[2]) - (v[1] - v[0]);                            // eta zeta
+  o[12] = v[4] - v[0];                                             // xi
+  o[15] = (v[5] - v[4]) - (v[1] - v[0]);                           // xi zeta
+  o[18] = (v[6] - v[4]) - (v[2] - v[0]);                           // xi eta
+  o[21] = ((v[7] - v[6]) - (v[5] - v[4])) - ((v[3] - v[2]) - (v[1] - v[0])); // xi eta zeta
+}
+
 // paired slot layout -> the reference's [cell][q][6]
 // (qperm: the caller's quadrature-point number -> ascending; nullptr = the caller's order is ascending)
 __global__ void geometry_export_kernel(long long slot0, long long nslots, int nd, int K,

@@ -111,6 +111,41 @@ int rebuild_affine_tensor(pmg_laplacian op, hipStream_t s)
   return PMG_OK;
 }
 
+// ---- the recomputed tensor (GEO_RECOMPUTE, stiffness_layer.hpp) ----
+// Degrees whose column kernel (and fused pair) has the form, and those where it is the automatic choice: decided by
+// measurement, profiles/tensor_recompute.md.  From P = 3 the 15 values per lane do not fit beside the march.
+constexpr bool recompute_form(int P) { return P == 1 || P == 2; }
+constexpr bool recompute_default(int P) { return P == 1 || P == 2; }
+
+// Could this operator's apply recompute its tensor at all?  What never changes after creation: a trilinear coordinate
+// element with the library's own tabulation and weights, at a degree that has the form.
+bool recompute_possible(pmg_laplacian op) { return op->geom_degree == 1 && op->own_tables && recompute_form(op->P); }
+bool recompute_wanted(pmg_laplacian op)
+{
+  return op->recompute_request == 1 || (op->recompute_request < 0 && recompute_default(op->P));
+}
+// ... and does its next application?  The one place that decides: resident geometry in the stored mode, no nodal field
+// and no per-cell tensor (both are folded into G where it is built, and the form carries neither).  Evaluated at every
+// use, so it follows a field or tensor that is set or removed, the geometry mode and the batching.
+bool recomputes_tensor(pmg_laplacian op)
+{
+  return recompute_possible(op) && recompute_wanted(op) && op->Ccell && op->batch_patches == 0
+         && op->geometry_mode == 0 && !op->kfield && !op->ktensor;
+}
+// Ccell, built once when the form is first chosen (the geometry never changes)
+int ensure_cell_coefficients(pmg_laplacian op, hipStream_t s)
+{
+  if (op->Ccell || !recompute_possible(op) || !recompute_wanted(op))
+    return PMG_OK;
+  const long long nslots = (long long)op->npatch * op->K;
+  PMG_HIP(hipMalloc(&op->Ccell, sizeof(double) * 24 * (nslots ? nslots : 1)));
+  if (nslots > 0)
+    cell_coefficient_kernel<<<(unsigned)((nslots * 3 + 255) / 256), 256, 0, s>>>(nslots, op->pcell, op->xgeom,
+                                                                                 op->geom_dofmap, op->Ccell);
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
 // f(first patch, patch count, G base) over all patches: once with the resident tensor, or batch by
 // batch with the tensor recomputed into the batch buffer
 template <typename F>
@@ -130,20 +165,28 @@ int for_each_geometry_chunk(pmg_laplacian op, hipStream_t s, F f)
   return PMG_OK;
 }
 
-// The (AFF, NT) instantiation of an apply kernel that an operator runs, chosen in one place: launch(AFF, NT) is called
-// with the two as std::bool_constant.  Cache policy: a tensor that is read once per application and is larger than the
+// The (GEO, NT) instantiation of an apply kernel that an operator runs, chosen in one place: launch(GEO, NT) is called
+// with the two as std::integral_constant / std::bool_constant, and with the per-slot array the form reads beside G
+// (Gaff, Ccell).  Cache policy: a tensor that is read once per application and is larger than the
 // Infinity Cache is streamed (nt), so that it does not displace x, y and the tables; a tensor that fits stays resident
 // between two applications under the default policy (streams_past_the_cache; profiles/kernel_tuning_r03.md).  The
-// affine mode reads no tensor: AFFINE_NT is the kernel's one instantiation for it.
+// affine mode and the recomputed form read no tensor: AFFINE_NT is the kernel's one instantiation for them.
+template <int G>
+using geo_constant = std::integral_constant<int, G>;
 template <int P, bool AFFINE_NT, typename F>
 void apply_variant(pmg_laplacian op, F launch)
 {
+  if constexpr (recompute_form(P))
+  {
+    if (recomputes_tensor(op))
+      return launch(geo_constant<GEO_RECOMPUTE>{}, std::bool_constant<AFFINE_NT>{}, (const double*)op->Ccell);
+  }
   if (op->geometry_mode == 1)
-    launch(std::true_type{}, std::bool_constant<AFFINE_NT>{});
+    launch(geo_constant<GEO_AFFINE>{}, std::bool_constant<AFFINE_NT>{}, (const double*)op->Gaff);
   else if (P >= NT_FROM && op->stream_policy)
-    launch(std::false_type{}, std::true_type{});
+    launch(geo_constant<GEO_STORED>{}, std::true_type{}, (const double*)op->Gaff);
   else
-    launch(std::false_type{}, std::false_type{});
+    launch(geo_constant<GEO_STORED>{}, std::false_type{}, (const double*)op->Gaff);
 }
 
 template <int P>
@@ -161,10 +204,11 @@ int launch_stiffness(pmg_laplacian op, const double* x, double* y, int first, in
   const double2* G = op->G;
   if (op->batch_patches > 0 && op->geometry_mode == 0)
     G = batch_geometry(op, first, count, s); // :391-396
-  apply_variant<P, (P >= NT_FROM)>(op, [&](auto aff, auto nt) { // (affine cells: nt is for the y stores)
-    constexpr bool AFF = decltype(aff)::value, NT = decltype(nt)::value;
-    stiffness_column_kernel<P, AFF, NT><<<count, Shape<P>::WTHREADS, 0, s>>>(
-        x, y, G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
+  apply_variant<P, (P >= NT_FROM)>(op, [&](auto geo, auto nt, const double* Gcell) { // (no stream: nt is for the y stores)
+    constexpr int GEO = decltype(geo)::value;
+    constexpr bool NT = decltype(nt)::value;
+    stiffness_column_kernel<P, GEO, NT><<<count, Shape<P>::WTHREADS, 0, s>>>(
+        x, y, G, Gcell, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell, op->kappa, op->D,
         op->react, first, atomic_out);
   });
   op->launches++;
@@ -222,10 +266,11 @@ int launch_stiffness_restrict(pmg_laplacian op, const TransferView& tv, const do
   constexpr int cm = RestrictShape<P, PC>::CM;
   PMG_REQUIRE(tv.cmax_m <= cm, "internal: a patch holds %d coarse dofs, the fused kernel %d", tv.cmax_m, cm);
   const RestrictLists R{tv.cpoff, tv.clmap_id, tv.cpdofs, tv.clmaps, tv.pmult, tv.M1};
-  apply_variant<P, false>(op, [&](auto aff, auto nt) {
-    constexpr bool AFF = decltype(aff)::value, NT = decltype(nt)::value;
-    stiffness_restrict_kernel<P, PC, AFF, NT><<<op->npatch, Shape<P>::WTHREADS, 0, s>>>(
-        z, r, coarse, op->G, op->Gaff, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell,
+  apply_variant<P, false>(op, [&](auto geo, auto nt, const double* Gcell) {
+    constexpr int GEO = decltype(geo)::value;
+    constexpr bool NT = decltype(nt)::value;
+    stiffness_restrict_kernel<P, PC, GEO, NT><<<op->npatch, Shape<P>::WTHREADS, 0, s>>>(
+        z, r, coarse, op->G, Gcell, op->W1, op->poff, op->pdofs, op->lmap_id, op->lmaps, op->pcell, op->pncell,
         op->kappa, op->D, op->react, R);
   });
   PMG_HIP(hipGetLastError());
@@ -304,8 +349,10 @@ long long laplacian_capture_state(pmg_laplacian op)
   // epoch counts both; the resident tensor is rebuilt in place, as everything else that follows the operator's data
   // (laplacian_data_changed states what follows what), so a graph over it stays valid)
   const long long field = op->batch_patches > 0 ? (op->kfield_epoch & 0x3fff) << 44 : 0;
+  // (recomputed tensor: another kernel, reading another array)
   return ((long long)op->geometry_mode << 40) ^ ((long long)op->batch_patches << 8) ^ (long long)(op->have_diag ? 1 : 0)
-         ^ (long long)(op->chain_on ? 2 : 0) ^ (long long)(op->react ? 4 : 0) ^ field;
+         ^ (long long)(op->chain_on ? 2 : 0) ^ (long long)(op->react ? 4 : 0) ^ (long long)(recomputes_tensor(op) ? 8 : 0)
+         ^ field;
 }
 
 PatchView laplacian_patches(pmg_laplacian op)
@@ -495,6 +542,7 @@ extern "C" int pmg_laplacian_create_curved(
   // the 3-D weights (examples/pmg/main.cpp:216-238)
   op->geom_degree = g;
   op->ng = ng;
+  op->own_tables = !(dphi_geometry && G_weights);
   if (dphi_geometry && G_weights)
   {
     PMG_HIP(hipMalloc(&op->dphi_geom, sizeof(double) * 3 * ng * N));
@@ -663,7 +711,16 @@ extern "C" int pmg_laplacian_create_curved(
   }
 
   const long long nslots = (long long)plan.npatch * op->K;
-  PMG_TRY(upload(&op->W1, wts.data(), wts.size(), s));
+  {
+    std::vector<double> w1(wts);
+    w1.insert(w1.end(), pts.begin(), pts.end());
+    PMG_TRY(upload(&op->W1, w1.data(), w1.size(), s));
+    PMG_HIP(hipStreamSynchronize(s)); // w1 goes out of scope
+  }
+  // PMG_TENSOR_RECOMPUTE=0 / 1 forces the streamed / (where eligible) the recomputed form (measurements)
+  if (const char* e = std::getenv("PMG_TENSOR_RECOMPUTE"))
+    op->recompute_request = e[0] != '0' ? 1 : 0;
+  PMG_TRY(ensure_cell_coefficients(op, s));
   PMG_HIP(hipMalloc(&op->Gaff, sizeof(double) * 6 * (nslots ? nslots : 1)));
   PMG_TRY(rebuild_affine_tensor(op, s));
   {
@@ -729,6 +786,7 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->qperm);
   (void)hipFree(op->D);
   (void)hipFree(op->Gaff);
+  (void)hipFree(op->Ccell);
   (void)hipFree(op->kfield);
   (void)hipFree(op->ktensor);
   (void)hipFree(op->react_buf);
@@ -798,6 +856,36 @@ extern "C" int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode)
   op->geometry_mode = mode;
   return PMG_OK;
 }
+
+extern "C" int pmg_laplacian_set_tensor_recompute(pmg_laplacian op, int mode)
+{
+  PMG_REQUIRE(op && mode >= -1 && mode <= 1, "pmg_laplacian_set_tensor_recompute: bad argument");
+  hipStream_t s = nullptr; // (the first choice of the form builds the cell coefficients: not inside a stream capture)
+  const int before = op->recompute_request;
+  op->recompute_request = mode;
+  if (mode == 1)
+  {
+    const char* why = op->geom_degree != 1           ? "the coordinate element is not trilinear"
+                      : !op->own_tables              ? "the operator was created with the caller's tables"
+                      : !recompute_form(op->P)       ? "the form exists at degrees 1 and 2 only"
+                      : op->batch_patches != 0       ? "the geometry is batched"
+                      : op->geometry_mode != 0       ? "the operator is in the affine mode"
+                      : op->kfield                   ? "a nodal coefficient field is set"
+                      : op->ktensor                  ? "a per-cell coefficient tensor is set"
+                                                     : nullptr;
+    if (why)
+    {
+      op->recompute_request = before;
+      return fail(PMG_ERR_INVALID, "pmg_laplacian_set_tensor_recompute: this operator cannot recompute its tensor: %s",
+                  why);
+    }
+  }
+  PMG_TRY(ensure_cell_coefficients(op, s));
+  PMG_HIP(hipStreamSynchronize(s));
+  return PMG_OK;
+}
+
+extern "C" int pmg_laplacian_tensor_recomputed(pmg_laplacian op) { return op ? (recomputes_tensor(op) ? 1 : 0) : -1; }
 
 extern "C" int pmg_laplacian_apply(pmg_laplacian op, double* in, double* out, pmg_stream stream)
 {

@@ -57,7 +57,13 @@ struct pmg_laplacian_s
   bool has_sigma = false, has_robin = false;
   bool diag_computed = false;  // diag_inv came from pmg_laplacian_compute_diag_inverse (it follows a change of field)
   double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell (K Kc K^T / detJ with a coefficient tensor)
-  double* W1 = nullptr;        // [nd] 1-D GLL weights
+  double* W1 = nullptr;        // [2][nd] 1-D GLL weights, then the nodes on [0,1]
+  // Recomputed tensor (pmg_laplacian_set_tensor_recompute, laplacian_recomputes_tensor): the apply of a trilinear
+  // operator forms G in its layer march from Ccell instead of streaming it.  Ccell follows the geometry alone; it is
+  // built when the form is first chosen (at creation where it is the default) and kept.
+  double* Ccell = nullptr;     // [nslots][8][3] monomial coefficients c_ijk of x = sum c_ijk xi^i eta^j zeta^k, m = 4i+2j+k
+  bool own_tables = false;     // the library built the coordinate element's tabulation and the weights itself
+  int recompute_request = -1;  // -1 = automatic (per degree), 0 = always stream, 1 = recompute where eligible
   bool all_affine = false;     // every listed cell is a parallelepiped
   int geometry_mode = 0;       // 0 = stored G (reference data structure), 1 = affine cells
   double* D = nullptr;         // [nd*nd]

@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(Shape32<P>::THREADS, Shape32<P>::MIN_WAVES)
     for (int k = 0; k < ND; ++k)
       l[k] = lmb[lmo + (unsigned)(k * NQ2)];
     // layers 0 .. GD-1 in flight, slot k % GD refilled with layer k + GD once layer k is read
-    TensorStream<float2, ND, WL, false, false, 0, NT, GD> gs;
+    TensorStream<float2, ND, WL, GEO_STORED, false, 0, NT, GD> gs;
     gs.prime(G + (size_t)p * K * 3 * N, (unsigned)(slotc * 3 * N + ab));
     // kappa multiplies the cell's input once (the operator is linear in it), as in the FP64 kernels
     const float kap = skap[slotc];

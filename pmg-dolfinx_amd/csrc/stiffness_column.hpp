@@ -160,10 +160,13 @@ constexpr int min_waves_per_simd()
   // (P = 5 with the identity: the allocator lands on 129 registers; asked for four wavefronts per SIMD it has to find 128)
   return P <= 4 ? (2 * Shape<P>::NW + 3) / 4 : transposes_by_identity(P) ? 4 : 1;
 }
-template <int P, bool AFF, bool NT>
+// GEO: where the tensor comes from (stiffness_layer.hpp).  Gcell: the per-slot data of the two forms without a stream,
+// [slot][6] constant tensors (GEO_AFFINE) or [slot][24] trilinear coefficients (GEO_RECOMPUTE).  W1 [2][nd]: the 1-D GLL
+// weights, then the nodes.
+template <int P, int GEO, bool NT>
 __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
     stiffness_column_kernel(const double* __restrict__ x, double* __restrict__ y,
-                            const double2* __restrict__ G, const double* __restrict__ Gaff,
+                            const double2* __restrict__ G, const double* __restrict__ Gcell,
                             const double* __restrict__ W1, const int32_t* __restrict__ poff,
                             const uint32_t* __restrict__ pdofs,
                             const int32_t* __restrict__ lmap_id,
@@ -177,6 +180,8 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   constexpr int MAXM = Sh::MAXM, THREADS = Sh::WTHREADS, ITER = Sh::WITER;
   constexpr int WL = CW * NQ2; // columns of one item (a wave, or WPC waves sharing a cell)
   // NT: streaming cache policy for G and the y write-back (chosen per operator, launch_stiffness)
+  constexpr bool AFF = GEO == GEO_AFFINE, RCP = GEO == GEO_RECOMPUTE;
+  static_assert(!RCP || (WPC == 1 && !transposes_by_identity(P)), "the recomputed form covers the low degrees only");
   constexpr bool UNPAIRED = unpaired_slice_reads(P);
   constexpr bool SHARED = WPC > 1; // the item's wavefronts exchange their slices through workgroup barriers
   __shared__ double sD[ND * ND];
@@ -188,11 +193,13 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   // per workgroup behind its closing barrier.
   constexpr bool LIST_IN_LDS = list_in_lds(P);
   __shared__ uint32_t sm[LIST_IN_LDS ? MAXM : 1];
-  __shared__ double sq[NG * WL];
-  __shared__ double sgr[NG * WL];
-  __shared__ double sgs[NG * WL];
+  // (recomputed form: the three slices of every item in flight in ONE array, one address register, as the restrict
+  // kernel has them)
+  __shared__ double sq[(RCP ? 3 : 1) * NG * WL];
+  __shared__ double sgr[RCP ? 1 : NG * WL];
+  __shared__ double sgs[RCP ? 1 : NG * WL];
   // flat G layout: one layer of the item, as loaded (NJ x 64 double2), for the hand-over to the lanes
-  constexpr bool FLAT = !AFF && WPC == 1 && gflat(ND);
+  constexpr bool FLAT = GEO == GEO_STORED && WPC == 1 && gflat(ND);
   constexpr int FL = 3 * WL, NJ = (FL + 63) / 64, LS = gls(ND);
   __shared__ double2 sgb[FLAT ? NG * NJ * 64 : 1];
 
@@ -281,8 +288,8 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   }
   const double wab = AFF ? W1[a] * W1[b] : 0.0; // 1-D GLL weights of the lane's column
   double* q_s = sq + wave * WL + cw * NQ2;  // this cell's slices
-  double* gr_s = sgr + wave * WL + cw * NQ2;
-  double* gs_s = sgs + wave * WL + cw * NQ2;
+  double* gr_s = RCP ? q_s + NG * WL : sgr + wave * WL + cw * NQ2;
+  double* gs_s = RCP ? q_s + 2 * NG * WL : sgs + wave * WL + cw * NQ2;
   double* gr_w = gr_s + ab; // where the lane writes its x flux (the identity path, P = 5)
   const int items = WPC > 1 ? (((nc + CW - 1) / CW + NG - 1) / NG) * NG : (nc + CW - 1) / CW;
 
@@ -303,16 +310,26 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
     for (int k = 0; k < ND; ++k)
       l[k] = lmb[lmo + (unsigned)(k * NQ2)];
     // the tensor, one layer ahead of the march (affine cells: G_q = w_a w_b w_c * Gc, one constant tensor Gc per cell)
-    TensorStream<double2, ND, WL, AFF, FLAT, LS, NT, 1> gs;
+    // (trilinear cells: formed in the march from the cell's coefficients and the column's (xi_a, eta_b))
+    TensorStream<double2, ND, WL, GEO, FLAT, LS, NT, 1> gs;
     if constexpr (AFF)
-      gs.prime_affine(Gaff + ((size_t)p * K + slotc) * 6, 1.0);
+      gs.prime_affine(Gcell + ((size_t)p * K + slotc) * 6, 1.0);
+    else if constexpr (RCP)
+    {
+      // (the column's weights and nodes are read per item, from an opaque copy of the column index: held through the
+      // layer loop they are six registers the march has no room for)
+      int abv = ab;
+      asm volatile("" : "+v"(abv));
+      const int av = abv / ND, bv = abv - av * ND;
+      gs.prime_recompute(Gcell + ((size_t)p * K + slotc) * 24, W1[ND + av], W1[ND + bv], W1[av] * W1[bv], W1 + ND);
+    }
     else if constexpr (FLAT) // (the item index is wave-uniform: a scalar base plus 32-bit lane offsets)
       gs.prime_flat(G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS,
                     sgb + wave * (NJ * 64), lane, lw);
     else
       gs.prime(G + (size_t)p * ((long long)K * 3 * N), (unsigned)(slotc * 3 * N + ab));
     // (identity modes: kappa multiplies the cell's INPUT once -- the operator is linear in it, same value to rounding --
-    // and the positions are held two to a register through the layer loop)
+    // and the positions are held two to a register through the layer loop; so they are in the recomputed form)
     const double kap = IDT ? 1.0 : skap[slotc];
     double u[ND], Aq[ND];
     {
@@ -324,14 +341,15 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
         Aq[k] = 0.0;
       }
     }
-    unsigned lp[IDT ? (ND + 1) / 2 : 1];
-    if constexpr (IDT)
+    unsigned lp[IDT || RCP ? (ND + 1) / 2 : 1];
+    if constexpr (IDT || RCP)
       pack_positions(l, lp);
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
       double2 g01, g23, g45;
-      gs.take(k, AFF ? wab * W1[k] : 0.0, g01, g23, g45); // w_a w_b w_c; W1[k] is wave-uniform (scalar load)
+      // w_a w_b w_c; W1[k] is wave-uniform (scalar load)
+      gs.take(k, AFF ? wab * W1[k] : RCP ? W1[k] : 0.0, g01, g23, g45);
       double fr, fs, ft;
       layer_forward<ND, UNPAIRED, SHARED>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, kap, fr, fs, ft);
       if constexpr (IDT)
@@ -364,7 +382,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
-      const int lk = IDT ? (int)packed_position(lp, k) : l[k];
+      const int lk = IDT || RCP ? (int)packed_position(lp, k) : l[k];
       const double Ak = Aq[k];
       atomicAdd(&sy[lk], contributes ? Ak : 0.0); // :270,277 -- in LDS (ds_add_f64)
     }

@@ -12,10 +12,17 @@
 // P = 4, 6, 7: 6 VGPRs more; P = 8 stored: 2 fewer).  The table and the timings are in profiles/layer_march.md.
 #pragma once
 
+#include "laplacian.hpp" // adjugate, metric: the recomputed tensor is formed with the geometry kernels' expressions
+
 #include <hip/hip_runtime.h>
 
 namespace pmg
 {
+// where an apply kernel's tensor comes from (a template argument of the column and restrict kernels)
+constexpr int GEO_STORED = 0;    // the stored tensor G is streamed
+constexpr int GEO_AFFINE = 1;    // one constant tensor per (parallelepiped) cell
+constexpr int GEO_RECOMPUTE = 2; // trilinear cells: G is formed in the layer march from the cell's 24 coefficients
+
 // ---- synchronisation of a slice exchange (also of the patch transfers' wave-private scratch, interpolate.hip) -----
 // LDS executes a wavefront's instructions in order: where one wavefront owns the slices a compiler fence is all the
 // exchange needs, no s_barrier and no waitcnt.
@@ -179,20 +186,28 @@ __device__ __forceinline__ unsigned packed_position(const unsigned* lp, int k)
 }
 
 // ---- the tensor stream of the column and restrict kernels: one layer ahead of the march ---------------------------
-// Three forms.  Default layout: the lane's three pairs of layers 0 .. GD-1 in flight in registers, slot k % GD
+// Four forms.  Default layout: the lane's three pairs of layers 0 .. GD-1 in flight in registers, slot k % GD
 // refilled with layer k + GD once layer k is taken.  Flat layout (FLAT, P = 2): the item's next layer as loaded,
 // NJ x 64 pairs with a layer stride of LS, handed over to the lanes through `gb` in LDS.  Affine cells (AFF):
-// G_q = w_a w_b w_c Gc with one constant tensor Gc per cell, no stream.
-template <typename T2, int ND, int WL, bool AFF, bool FLAT, int LS, bool NT, int GD>
+// G_q = w_a w_b w_c Gc with one constant tensor Gc per cell, no stream.  Trilinear cells (RCP): x = sum c_ijk xi^i
+// eta^j zeta^k on [0,1]^3, so down the lane's column (xi_a, eta_b fixed) dx/dxi and dx/deta are linear in zeta and
+// dx/dzeta is constant: 15 values per lane, from which layer k forms J(zeta_k), adj(J), |det J| and the six entries
+// w_a w_b w_k adj(J) adj(J)^T / |det J| with the geometry kernels' own adjugate() and metric() -- the stored tensor to
+// rounding, no stream.  adj adj^T / det is homogeneous of degree one in J, so w_a w_b is folded into the 15 values.
+template <typename T2, int ND, int WL, int GEO, bool FLAT, int LS, bool NT, int GD>
 struct TensorStream
 {
   using T = typename scalar_of<T2>::type;
+  static constexpr bool AFF = GEO == GEO_AFFINE, RCP = GEO == GEO_RECOMPUTE;
+  static_assert(!(FLAT && GEO != GEO_STORED), "the flat layout is a layout of the stored tensor");
   static constexpr int GPS = ND * ND; // stride between the three pairs of a layer
   static constexpr int FL = 3 * WL, NJ = (FL + 63) / 64;
-  T2 gq[AFF || FLAT ? 1 : GD][3];
+  T2 gq[AFF || RCP || FLAT ? 1 : GD][3];
   T2 gfl[FLAT ? NJ : 1]; // flat layout: the next layer as loaded
   int eo[FLAT ? NJ : 1]; // the lane's elements of a layer (clamped: the tail lanes re-read the last one)
   T gc[AFF ? 6 : 1];
+  T jc[RCP ? 5 : 1][3]; // dx/dxi at zeta = 0 and its slope in zeta, dx/deta likewise, dx/dzeta; times w_a w_b
+  const T* zeta;        // the 1-D GLL nodes (wave-uniform reads)
   const T2* base;    // scalar base: the patch (default layout) or the item (flat layout)
   unsigned lane_off; // default layout: the lane's (layer 0, pair 0) as a 32-bit offset (a 64-bit per-lane pointer
                      // costs two registers, and a spilled one is reloaded behind a wait that drains the memory counter)
@@ -202,7 +217,7 @@ struct TensorStream
   // default layout: request layers 0 .. GD-1
   __device__ __forceinline__ void prime(const T2* patch, unsigned lane_off_)
   {
-    static_assert(!AFF && !FLAT);
+    static_assert(GEO == GEO_STORED && !FLAT);
     base = patch;
     lane_off = lane_off_;
 #pragma unroll
@@ -232,13 +247,32 @@ struct TensorStream
     for (int d = 0; d < 6; ++d)
       gc[d] = fold * ga[d];
   }
+  // trilinear cells: cc = the cell's eight coefficient vectors [4 i + 2 j + k][3] (all zero in an empty slot), (xi, eta)
+  // the lane's column, `fold` its weights w_a w_b, nodes the 1-D GLL nodes
+  __device__ __forceinline__ void prime_recompute(const T* cc, T xi, T eta, T fold, const T* nodes)
+  {
+    static_assert(RCP);
+    zeta = nodes;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+    {
+      const T c001 = cc[3 + i], c010 = cc[6 + i], c011 = cc[9 + i], c100 = cc[12 + i], c101 = cc[15 + i],
+              c110 = cc[18 + i], c111 = cc[21 + i];
+      const T e1 = c011 + c111 * xi;
+      jc[0][i] = fold * (c100 + c110 * eta);
+      jc[1][i] = fold * (c101 + c111 * eta);
+      jc[2][i] = fold * (c010 + c110 * xi);
+      jc[3][i] = fold * e1;
+      jc[4][i] = fold * (c001 + c101 * xi + e1 * eta);
+    }
+  }
   __device__ __forceinline__ void fetch(int slot, int layer)
   {
     gq[slot][0] = gload<NT>(base + (lane_off + (unsigned)(layer * 3 * GPS)));
     gq[slot][1] = gload<NT>(base + (lane_off + (unsigned)(layer * 3 * GPS + GPS)));
     gq[slot][2] = gload<NT>(base + (lane_off + (unsigned)(layer * 3 * GPS + 2 * GPS)));
   }
-  // layer k's three pairs (affine cells: times `sc`), and the refill behind them
+  // layer k's three pairs (affine and trilinear cells: times `sc`), and the refill behind them
   __device__ __forceinline__ void take(int k, T sc, T2& g01, T2& g23, T2& g45)
   {
     if constexpr (AFF)
@@ -246,6 +280,29 @@ struct TensorStream
       g01.x = sc * gc[0], g01.y = sc * gc[1];
       g23.x = sc * gc[2], g23.y = sc * gc[3];
       g45.x = sc * gc[4], g45.y = sc * gc[5];
+    }
+    else if constexpr (RCP)
+    {
+      const T z = zeta[k];
+      T J[3][3], K[3][3], detJ, g[6];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+      {
+        J[i][0] = jc[0][i] + z * jc[1][i];
+        J[i][1] = jc[2][i] + z * jc[3][i];
+        J[i][2] = jc[4][i];
+      }
+      adjugate(J, K, detJ);
+      // 1 / |det J| from the hardware's estimate and two Newton steps: full precision for a normal determinant, without
+      // the scaling and fix-up instructions of an IEEE division (the march is bound by its FP64 issue in this form).
+      // (an empty slot: J = 0, and G = 0 as the stored tensor has it)
+      T r = __builtin_amdgcn_rcp(detJ);
+      r = fma(fma(-detJ, r, 1.0), r, r);
+      r = fma(fma(-detJ, r, 1.0), r, r);
+      metric(K, detJ > 0 ? sc * r : 0, g);
+      g01.x = g[0], g01.y = g[1];
+      g23.x = g[2], g23.y = g[3];
+      g45.x = g[4], g45.y = g[5];
     }
     else if constexpr (FLAT)
     {

@@ -43,17 +43,18 @@ struct RestrictLists
 // waves per SIMD the allocation has to leave room for: the column kernel's, with two exceptions.  P = 2: the coarse
 // sums push the workgroup past 80 KB of LDS, so one workgroup per CU is what runs.  P = 3: asked for the four the
 // column kernel reaches, the allocation stays at 128 registers instead of 129.  (P = 6, asked for the column kernel's
-// three: spills.)
-template <int P>
+// three: spills.)  The recomputed form at P = 2 has no hand-over buffer for the flat layout: two workgroups fit again.
+template <int P, int GEO>
 constexpr int restrict_waves_per_simd()
 {
-  return P == 2 ? 2 : P == 3 ? 4 : min_waves_per_simd<P>();
+  return P == 2 ? (GEO == GEO_RECOMPUTE ? 4 : 2) : P == 3 ? 4 : min_waves_per_simd<P>();
 }
 
-template <int P, int PC, bool AFF, bool NT>
-__global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>())
+// (GEO, Gcell, W1: as in stiffness_column_kernel)
+template <int P, int PC, int GEO, bool NT>
+__global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P, GEO>()))
     stiffness_restrict_kernel(const double* __restrict__ z, const double* __restrict__ r, double* __restrict__ coarse,
-                              const double2* __restrict__ G, const double* __restrict__ Gaff,
+                              const double2* __restrict__ G, const double* __restrict__ Gcell,
                               const double* __restrict__ W1, const int32_t* __restrict__ poff,
                               const uint32_t* __restrict__ pdofs, const int32_t* __restrict__ lmap_id,
                               const uint16_t* __restrict__ lmaps, const int32_t* __restrict__ pcell,
@@ -67,6 +68,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
   constexpr int NDC = Rs::NDC, NC = Rs::NC, CM = Rs::CM, CITER = Rs::CITER;
   constexpr int WL = CW * NQ2;
   constexpr bool UNPAIRED = unpaired_slice_reads(P);
+  constexpr bool AFF = GEO == GEO_AFFINE, RCP = GEO == GEO_RECOMPUTE;
   __shared__ double sD[ND * ND];
   __shared__ double sM[ND * NDC];
   __shared__ double sW[AFF ? ND : 1]; // affine mode: the 1-D weights, read per item instead of held per lane
@@ -76,7 +78,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
   __shared__ double sc[CM];   // the patch's coarse sums
   __shared__ unsigned long long sbc[Rs::BCW]; // bit i: patch entry i is a Dirichlet row
   __shared__ double ssl[3 * NG * WL]; // the three slices of every item in flight, in ONE array: one address register
-  constexpr bool FLAT = !AFF && gflat(ND);
+  constexpr bool FLAT = GEO == GEO_STORED && gflat(ND);
   constexpr int FL = 3 * WL, NJ = (FL + 63) / 64, LS = gls(ND);
   __shared__ double2 sgb[FLAT ? NG * NJ * 64 : 1];
 
@@ -201,14 +203,21 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
       lc[k] = clb[clo + (unsigned)k];
     unsigned lcp[(NDC + 1) / 2];
     pack_positions(lc, lcp);
-    TensorStream<double2, ND, WL, AFF, FLAT, LS, NT, 1> gs;
+    TensorStream<double2, ND, WL, GEO, FLAT, LS, NT, 1> gs;
     if constexpr (AFF)
     {
       // (kappa and the column's weights w_a w_b folded into the cell's constant tensor: same value to rounding; the
       // layer's weight w_c scales the three fluxes)
       int av, bv;
       coarse_point(ab, av, bv, ND);
-      gs.prime_affine(Gaff + ((size_t)p * K + slotc) * 6, skap[slotc] * (sW[av] * sW[bv]));
+      gs.prime_affine(Gcell + ((size_t)p * K + slotc) * 6, skap[slotc] * (sW[av] * sW[bv]));
+    }
+    else if constexpr (RCP)
+    {
+      // (the column's weights and nodes read per item, as the affine mode's weights; kappa scales the fluxes)
+      int av, bv;
+      coarse_point(ab, av, bv, ND);
+      gs.prime_recompute(Gcell + ((size_t)p * K + slotc) * 24, W1[ND + av], W1[ND + bv], W1[av] * W1[bv], W1 + ND);
     }
     else if constexpr (FLAT)
       gs.prime_flat(G + (size_t)p * gpatch(ND, K) + (size_t)__builtin_amdgcn_readfirstlane(it) * ND * LS,
@@ -230,7 +239,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, restrict_waves_per_simd<P>
     for (int k = 0; k < ND; ++k)
     {
       double2 g01, g23, g45;
-      gs.take(k, 1.0, g01, g23, g45);
+      gs.take(k, RCP ? W1[k] : 1.0, g01, g23, g45); // (W1[k] is wave-uniform, a scalar load)
       double fr, fs, ft;
       // (affine cells: W1[k] is wave-uniform, a scalar load)
       layer_forward<ND, UNPAIRED, false>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, AFF ? W1[k] : kap, fr, fs, ft);

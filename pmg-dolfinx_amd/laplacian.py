@@ -340,6 +340,16 @@ class MatFreeLaplacian:
         (one constant tensor per cell; needs ``is_affine()``)."""
         call("pmg_laplacian_set_geometry_mode", self._handle, {"stored": 0, "affine": 1}[mode])
 
+    def set_tensor_recompute(self, mode):
+        """Recomputed tensor of a trilinear operator of degree 1 or 2 (include/pmg_amd.h): ``None`` / -1 automatic,
+        ``False`` / 0 always stream G, ``True`` / 1 recompute it in the kernel (``PmgError`` on an operator that
+        cannot)."""
+        call("pmg_laplacian_set_tensor_recompute", self._handle, -1 if mode is None else int(mode))
+
+    def tensor_recomputed(self) -> bool:
+        """Does the next application form G in the kernel instead of streaming it?"""
+        return bool(call("pmg_laplacian_tensor_recomputed", self._handle))
+
     def launches_per_apply(self) -> int:
         return call("pmg_laplacian_launches_per_apply", self._handle)
 

@@ -18,13 +18,20 @@ for line in out.splitlines():
         rows[cur] = {}
     elif cur:
         rows[cur][k.strip()] = v.strip()
-print("| kernel | VGPRs | SGPRs | spills V/S | LDS bytes | waves/SIMD (registers) |")
-print("|---|---|---|---|---|---|")
-for name, r in sorted(rows.items()):
-    m = re.search(r"stiffness_column_kernelILi(\d)ELb(\d)", name)
-    if not m:
-        continue
-    mode = "affine" if m.group(2) == "1" else "stored"
-    print(f"| stiffness_column_kernel<{m.group(1)}, {mode}> | {r.get('VGPRs')} | {r.get('SGPRs')} | "
-          f"{r.get('VGPRs Spill')}/{r.get('SGPRs Spill')} | {r.get('LDS Size [bytes/block]')} | "
-          f"{r.get('Occupancy [waves/SIMD]')} |")
+GEO = {"0": "stored", "1": "affine", "2": "recomputed"}  # GEO_* of stiffness_layer.hpp
+print("| kernel | VGPRs | SGPRs | spills V/S | scratch B/lane | LDS bytes | waves/SIMD (registers) |")
+print("|---|---|---|---|---|---|---|")
+table = []
+for name, r in rows.items():
+    m = re.search(r"stiffness_column_kernelILi(\d)ELi(\d)ELb(\d)", name)
+    if m:
+        label = f"stiffness_column_kernel<{m.group(1)}, {GEO[m.group(2)]}, nt={m.group(3)}>"
+    else:
+        m = re.search(r"stiffness_restrict_kernelILi(\d)ELi(\d)ELi(\d)ELb(\d)", name)
+        if not m:
+            continue
+        label = f"stiffness_restrict_kernel<{m.group(1)}, {m.group(2)}, {GEO[m.group(3)]}, nt={m.group(4)}>"
+    table.append(f"| {label} | {r.get('VGPRs')} | {r.get('SGPRs')} | "
+                 f"{r.get('VGPRs Spill')}/{r.get('SGPRs Spill')} | {r.get('ScratchSize [bytes/lane]')} | "
+                 f"{r.get('LDS Size [bytes/block]')} | {r.get('Occupancy [waves/SIMD]')} |")
+print("\n".join(sorted(table)))

@@ -1,5 +1,5 @@
 """Time the stiffness kernel alone (HIP events) for one degree / mesh size.
-usage: python tools/time_apply.py P n [reps]"""
+usage: [PMG_GEOMETRY=affine] [PMG_TENSOR_RECOMPUTE=0|1] python tools/time_apply.py P n [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -20,4 +20,8 @@ if os.environ.get("PMG_GEOMETRY") == "affine":
     op.set_geometry_mode("affine")
     op.time_kernel(x, v, 3)
     ms = op.time_kernel(x, v, reps) * op.launches_per_apply()
-print(f"geom={os.environ.get('PMG_GEOMETRY','stored')} lib={os.environ.get('PMG_AMD_LIB','default')} P={P} n={n} kernel {ms*1e3:.1f} us  algorithmic {alg/ms/1e6:.0f} GB/s  ({alg/ms/1e6/8000:.3f} of 8 TB/s)")
+try:
+    rc = int(op.tensor_recomputed())
+except AttributeError:  # a library from before the form (A/B runs through PMG_AMD_LIB)
+    rc = 0
+print(f"geom={os.environ.get('PMG_GEOMETRY','stored')} recomputed={rc} lib={os.environ.get('PMG_AMD_LIB','default')} P={P} n={n} kernel {ms*1e3:.1f} us  algorithmic {alg/ms/1e6:.0f} GB/s  ({alg/ms/1e6/8000:.3f} of 8 TB/s)")
