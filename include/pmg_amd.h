@@ -601,6 +601,22 @@ int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode);
  * pmg_laplacian_tensor_recomputed: 1 if the next application recomputes, 0 if it streams, -1 for NULL. */
 int pmg_laplacian_set_tensor_recompute(pmg_laplacian op, int mode);
 int pmg_laplacian_tensor_recomputed(pmg_laplacian op);
+/* The recomputed tensor at degree 4.  The same form, in the degree-4 apply kernel and the fused (4, 2) restriction;
+ * the 15 values of a column's Jacobian fit beside the layer march because these two kernels take their transposed
+ * contractions by the barycentric identity (D^T f as the forward contraction of the scaled fluxes) instead of holding
+ * the transposed table.  Same result to rounding.  It has a switch of its own: the pair above keeps its contract, under
+ * which a degree-4 operator reports 0 and refuses mode 1.  Neither switch moves the other.
+ * Eligible is a degree-4 operator that meets the conditions above and is not in the chain form
+ * (pmg_laplacian_set_chain_form); evaluated at every application.  The FP32 cycle keeps the float tensor.
+ * mode -1 (default): automatic -- on (profiles/tensor_recompute_p4.md); 0: always stream; 1: recompute where
+ * eligible -- PMG_ERR_INVALID with the reason if the operator is not eligible now, nothing changes.
+ * PMG_TENSOR_RECOMPUTE_IDENTITY=0 / 1 in the environment, read at creation, sets mode 0 / 1 (1 without the error).
+ * The choice is part of what a captured graph is keyed by, and the first choice builds the cell coefficients on the
+ * default stream, as above.
+ * pmg_laplacian_tensor_recomputed_identity: 1 if the next application of a degree-4 operator recomputes, 0 if it
+ * streams (every other degree: 0), -1 for NULL. */
+int pmg_laplacian_set_tensor_recompute_identity(pmg_laplacian op, int mode);
+int pmg_laplacian_tensor_recomputed_identity(pmg_laplacian op);
 /* Geometry batching (src/laplacian.hpp:383-396; examples/mat_free/main.cpp:34-50 --batch_size):
  * with batch_cells > 0 the tensor G is not kept; every application recomputes it for about
  * batch_cells cells at a time (rounded up to whole patches) into a buffer of that size, right

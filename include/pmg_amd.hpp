@@ -810,6 +810,14 @@ public:
       throw std::runtime_error("MatFreeLaplacian: set_tensor_recompute before the operator has seen an index map");
     check(pmg_laplacian_set_tensor_recompute(_op, mode));
   }
+  /// The same switch for the degree-4 form (pmg_laplacian_set_tensor_recompute_identity).
+  void set_tensor_recompute_identity(int mode)
+  {
+    if (!_op)
+      throw std::runtime_error(
+          "MatFreeLaplacian: set_tensor_recompute_identity before the operator has seen an index map");
+    check(pmg_laplacian_set_tensor_recompute_identity(_op, mode));
+  }
   int degree() const { return _degree; }
   int geometry_degree() const { return _geom_degree; }
 

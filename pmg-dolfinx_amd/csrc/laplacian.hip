@@ -113,24 +113,37 @@ int rebuild_affine_tensor(pmg_laplacian op, hipStream_t s)
 
 // ---- the recomputed tensor (GEO_RECOMPUTE, stiffness_layer.hpp) ----
 // Degrees whose column kernel (and fused pair) has the form, and those where it is the automatic choice: decided by
-// measurement, profiles/tensor_recompute.md.  From P = 3 the 15 values per lane do not fit beside the march.
+// measurement, profiles/tensor_recompute.md.  From P = 3 the 15 values per lane do not fit beside the march as it is
+// written for these degrees.
 constexpr bool recompute_form(int P) { return P == 1 || P == 2; }
 constexpr bool recompute_default(int P) { return P == 1 || P == 2; }
+// Degree 4 has the form with its transposes by identity (transposes_by_identity, stiffness_column.hpp), which is what
+// makes the 15 values fit.  It has a switch of its own (pmg_laplacian_set_tensor_recompute_identity): the first one
+// keeps its contract, under which a degree-4 operator has no form.  Automatic = on, by measurement
+// (profiles/tensor_recompute_p4.md).
+constexpr bool recompute_identity_form(int P) { return P == 4; }
+constexpr bool recompute_identity_default(int P) { return P == 4; }
+constexpr bool recompute_kernel(int P) { return recompute_form(P) || recompute_identity_form(P); }
 
 // Could this operator's apply recompute its tensor at all?  What never changes after creation: a trilinear coordinate
 // element with the library's own tabulation and weights, at a degree that has the form.
-bool recompute_possible(pmg_laplacian op) { return op->geom_degree == 1 && op->own_tables && recompute_form(op->P); }
+bool recompute_possible(pmg_laplacian op) { return op->geom_degree == 1 && op->own_tables && recompute_kernel(op->P); }
+// (each degree listens to its own switch)
 bool recompute_wanted(pmg_laplacian op)
 {
+  if (recompute_identity_form(op->P))
+    return op->recompute_identity_request == 1
+           || (op->recompute_identity_request < 0 && recompute_identity_default(op->P));
   return op->recompute_request == 1 || (op->recompute_request < 0 && recompute_default(op->P));
 }
 // ... and does its next application?  The one place that decides: resident geometry in the stored mode, no nodal field
-// and no per-cell tensor (both are folded into G where it is built, and the form carries neither).  Evaluated at every
-// use, so it follows a field or tensor that is set or removed, the geometry mode and the batching.
+// and no per-cell tensor (both are folded into G where it is built, and the form carries neither), not the chain form
+// (degree 4: the chain kernel streams).  Evaluated at every use, so it follows a field or tensor that is set or
+// removed, the geometry mode, the batching and the chain form.
 bool recomputes_tensor(pmg_laplacian op)
 {
   return recompute_possible(op) && recompute_wanted(op) && op->Ccell && op->batch_patches == 0
-         && op->geometry_mode == 0 && !op->kfield && !op->ktensor;
+         && op->geometry_mode == 0 && !op->kfield && !op->ktensor && !op->chain_on;
 }
 // Ccell, built once when the form is first chosen (the geometry never changes)
 int ensure_cell_coefficients(pmg_laplacian op, hipStream_t s)
@@ -176,7 +189,7 @@ using geo_constant = std::integral_constant<int, G>;
 template <int P, bool AFFINE_NT, typename F>
 void apply_variant(pmg_laplacian op, F launch)
 {
-  if constexpr (recompute_form(P))
+  if constexpr (recompute_kernel(P))
   {
     if (recomputes_tensor(op))
       return launch(geo_constant<GEO_RECOMPUTE>{}, std::bool_constant<AFFINE_NT>{}, (const double*)op->Ccell);
@@ -720,6 +733,9 @@ extern "C" int pmg_laplacian_create_curved(
   // PMG_TENSOR_RECOMPUTE=0 / 1 forces the streamed / (where eligible) the recomputed form (measurements)
   if (const char* e = std::getenv("PMG_TENSOR_RECOMPUTE"))
     op->recompute_request = e[0] != '0' ? 1 : 0;
+  // ... and PMG_TENSOR_RECOMPUTE_IDENTITY=0 / 1 the same for the degree-4 form, which listens to this one alone
+  if (const char* e = std::getenv("PMG_TENSOR_RECOMPUTE_IDENTITY"))
+    op->recompute_identity_request = e[0] != '0' ? 1 : 0;
   PMG_TRY(ensure_cell_coefficients(op, s));
   PMG_HIP(hipMalloc(&op->Gaff, sizeof(double) * 6 * (nslots ? nslots : 1)));
   PMG_TRY(rebuild_affine_tensor(op, s));
@@ -857,27 +873,33 @@ extern "C" int pmg_laplacian_set_geometry_mode(pmg_laplacian op, int mode)
   return PMG_OK;
 }
 
-extern "C" int pmg_laplacian_set_tensor_recompute(pmg_laplacian op, int mode)
+// The two switches of the recomputed tensor: pmg_laplacian_set_tensor_recompute for the degrees of recompute_form,
+// pmg_laplacian_set_tensor_recompute_identity for those of recompute_identity_form.  Neither moves the other.
+static int set_recompute_request(pmg_laplacian op, int mode, bool identity, const char* who)
 {
-  PMG_REQUIRE(op && mode >= -1 && mode <= 1, "pmg_laplacian_set_tensor_recompute: bad argument");
+  PMG_REQUIRE(op && mode >= -1 && mode <= 1, "%s: bad argument", who);
   hipStream_t s = nullptr; // (the first choice of the form builds the cell coefficients: not inside a stream capture)
-  const int before = op->recompute_request;
-  op->recompute_request = mode;
+  int& request = identity ? op->recompute_identity_request : op->recompute_request;
+  const int before = request;
+  request = mode;
   if (mode == 1)
   {
+    const bool form = identity ? recompute_identity_form(op->P) : recompute_form(op->P);
     const char* why = op->geom_degree != 1           ? "the coordinate element is not trilinear"
                       : !op->own_tables              ? "the operator was created with the caller's tables"
-                      : !recompute_form(op->P)       ? "the form exists at degrees 1 and 2 only"
+                      : !form                        ? (identity ? "the form with the transposes by identity exists at "
+                                                                   "degree 4 only"
+                                                                 : "the form exists at degrees 1 and 2 only")
                       : op->batch_patches != 0       ? "the geometry is batched"
                       : op->geometry_mode != 0       ? "the operator is in the affine mode"
                       : op->kfield                   ? "a nodal coefficient field is set"
                       : op->ktensor                  ? "a per-cell coefficient tensor is set"
+                      : op->chain_on                 ? "the operator is in the chain form"
                                                      : nullptr;
     if (why)
     {
-      op->recompute_request = before;
-      return fail(PMG_ERR_INVALID, "pmg_laplacian_set_tensor_recompute: this operator cannot recompute its tensor: %s",
-                  why);
+      request = before;
+      return fail(PMG_ERR_INVALID, "%s: this operator cannot recompute its tensor: %s", who, why);
     }
   }
   PMG_TRY(ensure_cell_coefficients(op, s));
@@ -885,7 +907,25 @@ extern "C" int pmg_laplacian_set_tensor_recompute(pmg_laplacian op, int mode)
   return PMG_OK;
 }
 
-extern "C" int pmg_laplacian_tensor_recomputed(pmg_laplacian op) { return op ? (recomputes_tensor(op) ? 1 : 0) : -1; }
+extern "C" int pmg_laplacian_set_tensor_recompute(pmg_laplacian op, int mode)
+{
+  return set_recompute_request(op, mode, false, "pmg_laplacian_set_tensor_recompute");
+}
+
+extern "C" int pmg_laplacian_tensor_recomputed(pmg_laplacian op)
+{
+  return op ? (recompute_form(op->P) && recomputes_tensor(op) ? 1 : 0) : -1;
+}
+
+extern "C" int pmg_laplacian_set_tensor_recompute_identity(pmg_laplacian op, int mode)
+{
+  return set_recompute_request(op, mode, true, "pmg_laplacian_set_tensor_recompute_identity");
+}
+
+extern "C" int pmg_laplacian_tensor_recomputed_identity(pmg_laplacian op)
+{
+  return op ? (recompute_identity_form(op->P) && recomputes_tensor(op) ? 1 : 0) : -1;
+}
 
 extern "C" int pmg_laplacian_apply(pmg_laplacian op, double* in, double* out, pmg_stream stream)
 {

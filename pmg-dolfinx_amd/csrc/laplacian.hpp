@@ -64,6 +64,7 @@ struct pmg_laplacian_s
   double* Ccell = nullptr;     // [nslots][8][3] monomial coefficients c_ijk of x = sum c_ijk xi^i eta^j zeta^k, m = 4i+2j+k
   bool own_tables = false;     // the library built the coordinate element's tabulation and the weights itself
   int recompute_request = -1;  // -1 = automatic (per degree), 0 = always stream, 1 = recompute where eligible
+  int recompute_identity_request = -1; // the same for degree 4 (pmg_laplacian_set_tensor_recompute_identity)
   bool all_affine = false;     // every listed cell is a parallelepiped
   int geometry_mode = 0;       // 0 = stored G (reference data structure), 1 = affine cells
   double* D = nullptr;         // [nd*nd]

@@ -2,7 +2,8 @@
 // geometry_kernels.hpp): Shape<P> and its policies, the write-back shared with the diagnostic stamps, and the column
 // form of the stiffness kernel.  The layer march, the lane's table rows, the tensor stream, the fences and the loads
 // are those of stiffness_layer.hpp, shared with the restrict, chain and FP32 kernels; what is written out here is the
-// gather, the cell loop and the transposition by identity (P = 5, its one user).
+// gather, the cell loop and the transposition by identity of P = 5 (P = 4 takes it beside the recomputed tensor, through
+// layer_backward_identity of stiffness_layer.hpp).
 
 template <int P>
 struct Shape
@@ -151,20 +152,24 @@ constexpr bool list_in_lds(int P) { return P == 5 || P == 7 || P == 8; }
 // P = 5 is the one degree where the identity pays: 129 registers instead of 164, and asked for four wavefronts per SIMD
 // the allocator finds 128 without a spill -- four workgroups per unit instead of three (33 KB of LDS each): 432 - 444
 // against 452 - 459 us at 51^3, 223 - 225 against 230 - 232 us at 40^3 (profiles/kernel_tuning_r04.md section 12).
-constexpr bool transposes_by_identity(int P) { return P == 5; }
+// P = 4 takes the identity in the recomputed form only (GEO_RECOMPUTE, stiffness_layer.hpp): there the lane holds the 15
+// values of its column's Jacobian beside the march, and the ten registers of DTa, DTb are what does not fit -- with them
+// the column kernel spills 62 registers at 128, with rho, 1 / rho in their place none (profiles/tensor_recompute_p4.md).
+// The streamed and the affine kernel of P = 4 keep their tables: their code objects are unchanged.
+constexpr bool transposes_by_identity(int P, int GEO) { return P == 5 || (P == 4 && GEO == GEO_RECOMPUTE); }
 // minimum waves per SIMD the register allocation has to leave room for: two workgroups per CU up to
 // P = 4; the register-heavy degrees take what they need (profiles/kernel_resources_r02.md)
-template <int P>
+template <int P, int GEO>
 constexpr int min_waves_per_simd()
 {
   // (P = 5 with the identity: the allocator lands on 129 registers; asked for four wavefronts per SIMD it has to find 128)
-  return P <= 4 ? (2 * Shape<P>::NW + 3) / 4 : transposes_by_identity(P) ? 4 : 1;
+  return P <= 4 ? (2 * Shape<P>::NW + 3) / 4 : transposes_by_identity(P, GEO) ? 4 : 1;
 }
 // GEO: where the tensor comes from (stiffness_layer.hpp).  Gcell: the per-slot data of the two forms without a stream,
 // [slot][6] constant tensors (GEO_AFFINE) or [slot][24] trilinear coefficients (GEO_RECOMPUTE).  W1 [2][nd]: the 1-D GLL
 // weights, then the nodes.
 template <int P, int GEO, bool NT>
-__global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
+__global__ void __launch_bounds__(Shape<P>::WTHREADS, (min_waves_per_simd<P, GEO>()))
     stiffness_column_kernel(const double* __restrict__ x, double* __restrict__ y,
                             const double2* __restrict__ G, const double* __restrict__ Gcell,
                             const double* __restrict__ W1, const int32_t* __restrict__ poff,
@@ -181,7 +186,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   constexpr int WL = CW * NQ2; // columns of one item (a wave, or WPC waves sharing a cell)
   // NT: streaming cache policy for G and the y write-back (chosen per operator, launch_stiffness)
   constexpr bool AFF = GEO == GEO_AFFINE, RCP = GEO == GEO_RECOMPUTE;
-  static_assert(!RCP || (WPC == 1 && !transposes_by_identity(P)), "the recomputed form covers the low degrees only");
+  static_assert(!RCP || WPC == 1, "the recomputed form covers the one-wave-per-item shapes only");
   constexpr bool UNPAIRED = unpaired_slice_reads(P);
   constexpr bool SHARED = WPC > 1; // the item's wavefronts exchange their slices through workgroup barriers
   __shared__ double sD[ND * ND];
@@ -266,7 +271,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   // them, so the fences inside the layer loop become workgroup barriers and every
   // wave runs the same number of items)
   const int wave = (t >> 6) / WPC, lane = (t & 63) + 64 * ((t >> 6) % WPC);
-  constexpr bool IDT = transposes_by_identity(P);
+  constexpr bool IDT = transposes_by_identity(P, GEO);
   // the lanes past the item's columns idle on a copy of the last column
   const bool lane_ok = lane < WL;
   const int lw = lane_ok ? lane : WL - 1;
@@ -276,6 +281,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   LaneTables<double, ND> T;
   T.fill((const __attribute__((address_space(3))) double*)sD, a, b);
   // the identity's constants (see transposes_by_identity): rho, 1 / rho, 2 D_ii for the lane's a and b
+  // (beside the recomputed tensor 2 D_ii is not held: layer_backward_identity picks it per layer)
   double rho_a = 1.0, irho_a = 1.0, d2a = 0.0, rho_b = 1.0, irho_b = 1.0, d2b = 0.0;
   if constexpr (IDT)
   {
@@ -290,7 +296,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
   double* q_s = sq + wave * WL + cw * NQ2;  // this cell's slices
   double* gr_s = RCP ? q_s + NG * WL : sgr + wave * WL + cw * NQ2;
   double* gs_s = RCP ? q_s + 2 * NG * WL : sgs + wave * WL + cw * NQ2;
-  double* gr_w = gr_s + ab; // where the lane writes its x flux (the identity path, P = 5)
+  double* gr_w = gr_s + ab; // where the lane writes its x flux (the identity path of P = 5)
   const int items = WPC > 1 ? (((nc + CW - 1) / CW + NG - 1) / NG) * NG : (nc + CW - 1) / CW;
 
   for (int it = wave; it < items; it += NG)
@@ -352,7 +358,10 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, min_waves_per_simd<P>())
       gs.take(k, AFF ? wab * W1[k] : RCP ? W1[k] : 0.0, g01, g23, g45);
       double fr, fs, ft;
       layer_forward<ND, UNPAIRED, SHARED>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, kap, fr, fs, ft);
-      if constexpr (IDT)
+      if constexpr (IDT && RCP)
+        layer_backward_identity<ND, UNPAIRED, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, rho_a, irho_a, rho_b,
+                                                      irho_b, Aq);
+      else if constexpr (IDT)
       {
         // the transposes as forward contractions of the scaled fluxes (see transposes_by_identity)
         *gr_w = fr * irho_a;

@@ -167,6 +167,43 @@ __device__ __forceinline__ void layer_backward(int k, T fr, T fs, T ft, const La
   slice_sync<SHARED>();
 }
 
+// Backward by the barycentric identity beside the recomputed tensor (transposes_by_identity, stiffness_column.hpp: the
+// identity and what it is worth are stated there): the transposed contractions as forward ones of the scaled fluxes,
+//     (D^T f)_i = 2 D_ii f_i - rho_i sum_j D_ij (f_j / rho_j),
+// so the lane needs rho and 1 / rho for its a and b instead of the columns D[.][a], D[.][b].  2 D_aa and 2 D_bb are
+// not held either: they are picked per layer out of the rows D[a][.], D[b][.] the lane holds anyway, by ND - 1 selects
+// each on an opaque copy of the column index (the copy keeps the picked values from being formed ahead of the layer
+// loop and held through it).
+template <int ND, bool UNPAIRED, bool SHARED, typename T>
+__device__ __forceinline__ void layer_backward_identity(int k, T fr, T fs, T ft, const LaneTables<T, ND>& D,
+                                                        const T* Dg, T* gr_s, T* gs_s, int a, int b, int ab, T rho_a,
+                                                        T irho_a, T rho_b, T irho_b, T (&Aq)[ND])
+{
+  gr_s[ab] = fr * irho_a;
+  gs_s[ab] = fs * irho_b;
+  slice_sync<SHARED>();
+  T sx_ = 0, sy_ = 0;
+#pragma unroll
+  for (int mm = 0; mm < ND; ++mm)
+  {
+    sx_ += D.Da[mm] * slice_load<UNPAIRED>(gr_s[mm * ND + b]); // :246-251
+    sy_ += D.Db[mm] * slice_load<UNPAIRED>(gs_s[a * ND + mm]); // :255-259
+    Aq[mm] += Dg[k * ND + mm] * ft;                            // :263-267
+  }
+  int abv = ab;
+  asm volatile("" : "+v"(abv));
+  const int av = abv / ND, bv = abv - av * ND;
+  T daa = D.Da[0], dbb = D.Db[0];
+#pragma unroll
+  for (int mm = 1; mm < ND; ++mm)
+  {
+    daa = av == mm ? D.Da[mm] : daa;
+    dbb = bv == mm ? D.Db[mm] : dbb;
+  }
+  Aq[k] += 2 * (daa * fr + dbb * fs) - (rho_a * sx_ + rho_b * sy_);
+  slice_sync<SHARED>();
+}
+
 // ---- patch positions, two to a register -------------------------------------------------------------------------
 // Positions in a patch list are 16-bit.  Where a kernel needs a column's positions again behind the layer loop it
 // holds them packed through it, and opaque, so that the unpacked values are not kept alongside.

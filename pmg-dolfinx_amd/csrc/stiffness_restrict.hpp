@@ -12,7 +12,8 @@
 // and so is a Robin term (pmg_laplacian_set_robin; the two arrive summed in one vector):
 // r - (A + D) z = (r - d z) - A z, so the unmarked rows' share is (r - d z) / mult and nothing else moves.
 //
-// The gather and the cell loop follow stiffness_column_kernel (WPC == 1 shapes without the transposition identity); the
+// The gather and the cell loop follow stiffness_column_kernel (WPC == 1 shapes; the transposition identity at P = 4 with
+// the recomputed tensor only); the
 // layer march, the lane's table rows, the tensor stream and the packed positions are the shared ones of
 // stiffness_layer.hpp.  `sy` holds the residual shares instead of the output sums.  Behind the layer
 // loop the lane owns w(a, b, .) = share - A_cell z of its column: z is contracted in registers with the 1-D
@@ -23,7 +24,7 @@ template <int P, int PC>
 struct RestrictShape
 {
   using Sh = Shape<P>;
-  static_assert(Sh::WPC == 1 && !transposes_by_identity(P), "the fused form covers the one-wave-per-item shapes only");
+  static_assert(Sh::WPC == 1, "the fused form covers the one-wave-per-item shapes only");
   static constexpr int NDC = PC + 1, NC = NDC * NDC * NDC;
   static constexpr int CM = Sh::K * NC < Sh::MAXM ? Sh::K * NC : Sh::MAXM; // coarse dofs of a patch: never more
   static constexpr int CITER = (CM + Sh::WTHREADS - 1) / Sh::WTHREADS;
@@ -47,7 +48,7 @@ struct RestrictLists
 template <int P, int GEO>
 constexpr int restrict_waves_per_simd()
 {
-  return P == 2 ? (GEO == GEO_RECOMPUTE ? 4 : 2) : P == 3 ? 4 : min_waves_per_simd<P>();
+  return P == 2 ? (GEO == GEO_RECOMPUTE ? 4 : 2) : P == 3 ? 4 : min_waves_per_simd<P, GEO>();
 }
 
 // (GEO, Gcell, W1: as in stiffness_column_kernel)
@@ -71,7 +72,10 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P
   constexpr bool AFF = GEO == GEO_AFFINE, RCP = GEO == GEO_RECOMPUTE;
   __shared__ double sD[ND * ND];
   __shared__ double sM[ND * NDC];
-  __shared__ double sW[AFF ? ND : 1]; // affine mode: the 1-D weights, read per item instead of held per lane
+  // (P = 4 with the recomputed tensor: the transposes by identity, as in the column kernel)
+  constexpr bool IDT = transposes_by_identity(P, GEO);
+  // affine mode: the 1-D weights, read per item instead of held per lane; identity: 1 / rho_i, read per layer
+  __shared__ double sW[AFF || IDT ? ND : 1];
   __shared__ double skap[K];
   __shared__ double sx[MAXM];
   __shared__ double sy[MAXM]; // the residual shares r / mult ((r - z) / mult on Dirichlet rows)
@@ -150,6 +154,11 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P
       if (t < ND)
         sW[t] = W1[t];
     }
+    if constexpr (IDT) // 1 / rho_i = -D_i0 / D_0i
+    {
+      if (t < ND)
+        sW[t] = t == 0 ? 1.0 : -Dg[t * ND] / Dg[t];
+    }
     for (int i = t; i < K; i += THREADS)
       skap[i] = (i == t) ? kapk : kappa[pcell[(size_t)p * K + i] >= 0 ? pcell[(size_t)p * K + i] : 0];
     for (int i = t; i < CM; i += THREADS)
@@ -166,6 +175,13 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P
   const int a = ab / ND, b = ab - a * ND;
   LaneTables<double, ND> T;
   T.fill((const __attribute__((address_space(3))) double*)sD, a, b);
+  // the identity's rho for the lane's a and b (1 / rho is read per layer from sW: the kernel has no registers for it)
+  double rho_a = 1.0, rho_b = 1.0;
+  if constexpr (IDT)
+  {
+    rho_a = a == 0 ? 1.0 : -sD[a] / sD[a * ND];
+    rho_b = b == 0 ? 1.0 : -sD[b] / sD[b * ND];
+  }
   double* q_s = ssl + wave * WL + cw * NQ2; // this cell's slices
   double* gr_s = q_s + NG * WL;
   double* gs_s = q_s + 2 * NG * WL;
@@ -224,13 +240,17 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P
                     sgb + wave * (NJ * 64), lane, lw);
     else
       gs.prime(G + (size_t)p * ((long long)K * 3 * N), (unsigned)(slotc * 3 * N + ab));
-    const double kap = AFF ? 1.0 : skap[slotc];
+    // (identity: kappa multiplies the cell's input once, as in the column kernel -- same value to rounding)
+    const double kap = AFF || IDT ? 1.0 : skap[slotc];
     double u[ND], Aq[ND];
-#pragma unroll
-    for (int k = 0; k < ND; ++k)
     {
-      u[k] = sx[l[k]];
-      Aq[k] = 0.0;
+      const double kin = IDT ? skap[slotc] : 1.0;
+#pragma unroll
+      for (int k = 0; k < ND; ++k)
+      {
+        u[k] = IDT ? kin * sx[l[k]] : sx[l[k]];
+        Aq[k] = 0.0;
+      }
     }
     // (the fine positions as well: the epilogue needs them again)
     unsigned lp[(ND + 1) / 2];
@@ -243,7 +263,15 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P
       double fr, fs, ft;
       // (affine cells: W1[k] is wave-uniform, a scalar load)
       layer_forward<ND, UNPAIRED, false>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, AFF ? W1[k] : kap, fr, fs, ft);
-      layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
+      if constexpr (IDT)
+      {
+        int av, bv;
+        coarse_point(ab, av, bv, ND);
+        layer_backward_identity<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, rho_a, sW[av], rho_b,
+                                                     sW[bv], Aq);
+      }
+      else
+        layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
     }
     // ---- the cell's share of the restricted residual.  w = share - A_cell z down the lane's column; the product is
     // dropped on Dirichlet rows (a select, no branch: see the column kernel's epilogue).

@@ -350,6 +350,15 @@ class MatFreeLaplacian:
         """Does the next application form G in the kernel instead of streaming it?"""
         return bool(call("pmg_laplacian_tensor_recomputed", self._handle))
 
+    def set_tensor_recompute_identity(self, mode):
+        """The same switch for the degree-4 form, whose kernels take their transposes by identity
+        (``pmg_laplacian_set_tensor_recompute_identity``): ``None`` / -1 automatic, ``False`` / 0, ``True`` / 1."""
+        call("pmg_laplacian_set_tensor_recompute_identity", self._handle, -1 if mode is None else int(mode))
+
+    def tensor_recomputed_identity(self) -> bool:
+        """Does the next application of this degree-4 operator form G in the kernel?"""
+        return bool(call("pmg_laplacian_tensor_recomputed_identity", self._handle))
+
     def launches_per_apply(self) -> int:
         return call("pmg_laplacian_launches_per_apply", self._handle)
 

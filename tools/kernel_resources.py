@@ -31,7 +31,7 @@ for name, r in rows.items():
         if not m:
             continue
         label = f"stiffness_restrict_kernel<{m.group(1)}, {m.group(2)}, {GEO[m.group(3)]}, nt={m.group(4)}>"
-    table.append(f"| {label} | {r.get('VGPRs')} | {r.get('SGPRs')} | "
+    table.append(f"| {label} | {r.get('VGPRs')} | {r.get('TotalSGPRs')} | "
                  f"{r.get('VGPRs Spill')}/{r.get('SGPRs Spill')} | {r.get('ScratchSize [bytes/lane]')} | "
                  f"{r.get('LDS Size [bytes/block]')} | {r.get('Occupancy [waves/SIMD]')} |")
 print("\n".join(sorted(table)))

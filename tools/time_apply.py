@@ -1,5 +1,8 @@
 """Time the stiffness kernel alone (HIP events) for one degree / mesh size.
-usage: [PMG_GEOMETRY=affine] [PMG_TENSOR_RECOMPUTE=0|1] python tools/time_apply.py P n [reps]"""
+usage: [PMG_GEOMETRY=affine] [PMG_TENSOR_RECOMPUTE=0|1] [PMG_TENSOR_RECOMPUTE_IDENTITY=0|1]
+       python tools/time_apply.py P n [reps]
+(PMG_TENSOR_RECOMPUTE switches the recomputed tensor of degrees 1 and 2, PMG_TENSOR_RECOMPUTE_IDENTITY that of
+degree 4; both reports are printed.)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -24,4 +27,8 @@ try:
     rc = int(op.tensor_recomputed())
 except AttributeError:  # a library from before the form (A/B runs through PMG_AMD_LIB)
     rc = 0
-print(f"geom={os.environ.get('PMG_GEOMETRY','stored')} recomputed={rc} lib={os.environ.get('PMG_AMD_LIB','default')} P={P} n={n} kernel {ms*1e3:.1f} us  algorithmic {alg/ms/1e6:.0f} GB/s  ({alg/ms/1e6/8000:.3f} of 8 TB/s)")
+try:
+    rci = int(op.tensor_recomputed_identity())
+except AttributeError:  # a library from before the degree-4 form
+    rci = 0
+print(f"geom={os.environ.get('PMG_GEOMETRY','stored')} recomputed={rc} recomputed_identity={rci} lib={os.environ.get('PMG_AMD_LIB','default')} P={P} n={n} kernel {ms*1e3:.1f} us  algorithmic {alg/ms/1e6:.0f} GB/s  ({alg/ms/1e6/8000:.3f} of 8 TB/s)")
