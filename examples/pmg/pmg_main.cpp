@@ -247,8 +247,9 @@ void solve(const Options& o)
       if (!o.csr_levels.empty() && std::find(o.csr_levels.begin(), o.csr_levels.end(), (int)i) == o.csr_levels.end())
         continue;
       matrices[i] = std::make_shared<acc::MatrixOperator<T>>(*operators[i], maps[i]);
+      const T a_norm = matrices[i]->norm(); // over all ranks: every rank calls
       if (root)
-        std::printf("Level %zu: CSR nnz = %zu, A norm = %.15e\n", i, matrices[i]->nnz(), matrices[i]->norm());
+        std::printf("Level %zu: CSR nnz = %zu, A norm = %.15e\n", i, matrices[i]->nnz(), a_norm);
     }
 
   // ---------------------------------------------------------------------------------------------

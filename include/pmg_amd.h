@@ -749,23 +749,51 @@ int pmg_cg_residual(pmg_cg s, double* rnorm);
  * `op` must outlive the matrix.  Degrees 1..PMG_MAX_DEGREE.
  * Refused with PMG_ERR_INVALID (message in pmg_last_error; *out stays NULL): a layout with ghosts or a communicator
  * (single-domain only; the distributed diag / off-diag form of :114-126 is a follow-up), an operator in
- * batched-geometry mode (G is not resident), a pattern whose nnz does not fit int32 (the message states the nnz). */
+ * batched-geometry mode (G is not resident), a pattern whose nnz does not fit int32 (the message states the nnz).
+ * (This entry point keeps its single-domain contract; pmg_matrix_create_distributed below takes any layout.) */
 int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian op, pmg_stream stream);
+/* The same matrix on ANY layout, several ranks included (the reference's operator is distributed by construction,
+ * src/csr.hpp:114-126,252-270).  On a layout without ghosts and without a communicator the arrays are those of
+ * pmg_matrix_create_from_laplacian.
+ *   rows:    the size_local owned dofs.  A ghost dof is a column, never a row.
+ *   columns: local indices in [0, size_local + num_ghosts), sorted, so the ghost columns of a row come last.
+ *   pattern: row i couples to every dof of every local cell, ghost cells included, that contains i.  Every rank holds
+ *            the ghost-cell layer, so its owned rows are complete locally: no matrix value is exchanged.  Dirichlet
+ *            rows and columns (ghost columns included) stay as explicit zeros with a unit diagonal.
+ *   split:   off_diag_offset[i] = the position of row i's first column >= size_local (the reference's array), and the
+ *            ascending list of the boundary rows, the rows with at least one ghost column (pmg_matrix_export_split).
+ * The product is scatter begin / owned columns of all rows / scatter end / ghost columns of the boundary rows; a level
+ * whose operator takes its exchange whole (halo windows, merged plan) does so here as well, in front of one launch.
+ * The remaining refusals are those above: batched geometry, nnz above int32, a row that does not fit LDS. */
+int pmg_matrix_create_distributed(pmg_matrix* out, pmg_laplacian op, pmg_stream stream);
 int pmg_matrix_destroy(pmg_matrix M);
 int pmg_matrix_update_values(pmg_matrix M, pmg_stream stream);
-/* operator()(x, y), src/csr.hpp:220-260: out = A in, one launch; `out` is overwritten (no zero-fill needed).  No
- * transpose variant: the operator is symmetric. */
+/* operator()(x, y), src/csr.hpp:220-260: out = A in; the owned entries of `out` are overwritten (no zero-fill needed).
+ * No transpose variant: the operator is symmetric.  On a distributed matrix the call exchanges the halo of `in`: it
+ * REFRESHES THE GHOST ENTRIES OF `in` (the const of the signature covers the owned entries only) and leaves the ghost
+ * entries of `out` alone.  Collective over the layout's ranks. */
 int pmg_matrix_apply(pmg_matrix M, const double* in, double* out, pmg_stream stream);
+/* The same product where the ghost entries of `in` are current already (the caller has exchanged them): no exchange,
+ * ONE launch over whole rows; `in` is not written.  What the V-cycle issues for the first product of a post-smooth.  On
+ * a matrix without ghost columns this is pmg_matrix_apply. */
+int pmg_matrix_apply_ghosts_current(pmg_matrix M, const double* in, double* out, pmg_stream stream);
 /* get_diag_inverse, src/csr.hpp:100-110,205-209: the owned entries; BC rows give 1. */
 int pmg_matrix_get_diag_inverse(pmg_matrix M, double* diag_inv, pmg_stream stream);
 /* num_rows and nnz of src/csr.hpp:91-93 (the reference's nnz() accessor); device bytes held by the handle. */
 long long pmg_matrix_rows(pmg_matrix M);
+long long pmg_matrix_cols(pmg_matrix M); /* size_local + num_ghosts */
 long long pmg_matrix_nnz(pmg_matrix M);
 long long pmg_matrix_bytes(pmg_matrix M);
-/* The "A norm" logged at src/csr.hpp:95-99: sqrt(sum of squared values). */
+/* The "A norm" logged at src/csr.hpp:95-99: sqrt(sum of squared values), over all ranks (every owned row lives on
+ * exactly one rank; the local sum of squares goes through the layout's all-reduce: collective). */
 int pmg_matrix_frobenius_norm(pmg_matrix M, double* norm);
-/* Host copy of the device arrays the reference uploads at src/csr.hpp:114-130 (tests).  NULL arrays: sizes only. */
+/* Host copy of the device arrays the reference uploads at src/csr.hpp:114-130 (tests): this rank's rows with local
+ * column numbers.  NULL arrays: sizes only. */
 int pmg_matrix_export(pmg_matrix M, long long* rows, long long* nnz, int32_t* row_ptr, int32_t* cols, double* values);
+/* ... and the split: off_diag_offset[rows] (positions in cols) and boundary_rows[*n_boundary_rows], ascending.  NULL
+ * arrays: sizes only.  A matrix on a layout without ghosts has off_diag_offset[i] = row_ptr[i + 1] and no boundary
+ * row. */
+int pmg_matrix_export_split(pmg_matrix M, int32_t* off_diag_offset, long long* n_boundary_rows, int32_t* boundary_rows);
 /* Chebyshev::solve / CGSolver::solve with an acc::MatrixOperator as the operator (src/chebyshev.hpp:46-91,
  * src/cg.hpp:147-222 are templated on it): the semantics of pmg_chebyshev_solve / pmg_cg_solve with the matrix's
  * product and the matrix's own inverse diagonal. */
@@ -1002,6 +1030,9 @@ int pmg_multigrid_set_precision(pmg_multigrid mg, int precision);
  * form ran them.  The set of level matrices is part of the graph key (a cached graph is never replayed after it
  * changes).  Refused with PMG_ERR_INVALID: a matrix on another layout than the level's; a matrix together with
  * PMG_PRECISION_FP32, in either order (there is no FP32 matrix).  A coarse AMG / CG / callback solver is unaffected.
+ * On a level of several ranks `M` is a distributed matrix (pmg_matrix_create_distributed); the cycle's exchange
+ * bookkeeping then holds as on a matrix-free level: where the iterate's ghosts are current the post-smooth's first
+ * product runs without an exchange, so a cycle issues the same number of forward scatters in either form.
  * `M` must outlive `mg` or be removed first. */
 int pmg_multigrid_set_level_matrix(pmg_multigrid mg, int level, pmg_matrix M);
 int pmg_multigrid_precision(pmg_multigrid mg);

@@ -235,7 +235,7 @@ public:
            std::span<const std::int32_t> recv_indices = {}, pmg_exchange_fn exchange = nullptr,
            pmg_allreduce_fn allreduce_sum = nullptr, void* user = nullptr, pmg_allreduce_fn allreduce_max = nullptr)
       : _size_local(size_local), _num_ghosts(num_ghosts), _send_idx(send_indices), _recv_idx(recv_indices),
-        _send(send_indices.size()), _recv(recv_indices.size())
+        _send(send_indices.size()), _recv(recv_indices.size()), _callbacks(exchange || allreduce_sum)
   {
     check(pmg_layout_create(&_layout, size_local, num_ghosts, (std::int32_t)send_indices.size(), _send_idx.data(),
                             _send.data(), (std::int32_t)recv_indices.size(), _recv_idx.data(), _recv.data(),
@@ -273,6 +273,8 @@ public:
   std::int32_t size_local() const { return _size_local; }
   std::int32_t num_ghosts() const { return _num_ghosts; }
   pmg_layout layout() const { return _layout; }
+  /// Does a vector on this map have a halo to exchange: ghosts, a communicator or the caller's callbacks?
+  bool distributed() const { return _num_ghosts > 0 || _comm || _callbacks; }
   /// The packed send / receive staging buffers (device), for an exchange callback.
   std::span<double> send_buffer() { return _send.span(); }
   std::span<double> recv_buffer() { return _recv.span(); }
@@ -355,6 +357,7 @@ private:
   std::int32_t _size_local, _num_ghosts;
   device_array<std::int32_t> _send_idx, _recv_idx;
   device_array<double> _send, _recv;
+  bool _callbacks = false;
   std::shared_ptr<const Communicator> _comm;
   pmg_layout _layout = nullptr;
   void *_window = nullptr, *_flags = nullptr;
@@ -863,7 +866,9 @@ private:
 /// acc::MatrixOperator<T> (src/csr.hpp:58-260): the BC-treated stiffness matrix assembled into CSR on the device
 /// and applied by SpMV.  Where the reference assembles from the form (MatrixOperator(a, bcs), :66-131) this one
 /// assembles from the matrix-free operator of the same form -- its geometry tensor, dofmap, coefficient and BC
-/// marker -- on the index map of the level.  Single domain only.  `A` must outlive the matrix.
+/// marker -- on the index map of the level.  A map with ghosts or a communicator gives the distributed form (rows =
+/// owned dofs, ghost columns last, src/csr.hpp:114-126): operator() then exchanges the halo of x -- it refreshes x's
+/// ghost entries and leaves y's alone -- and norm() is global.  `A` must outlive the matrix.
 template <typename T>
 class MatrixOperator
 {
@@ -874,7 +879,10 @@ public:
 
   MatrixOperator(MatFreeLaplacian<T>& A, std::shared_ptr<const IndexMap> map) : _A(&A), _map(std::move(map))
   {
-    check(pmg_matrix_create_from_laplacian(&_m, A.handle(_map), nullptr));
+    if (_map->distributed())
+      check(pmg_matrix_create_distributed(&_m, A.handle(_map), nullptr));
+    else
+      check(pmg_matrix_create_from_laplacian(&_m, A.handle(_map), nullptr));
   }
   MatrixOperator(const MatrixOperator&) = delete;
   MatrixOperator& operator=(const MatrixOperator&) = delete;
@@ -896,7 +904,8 @@ public:
   void update_values() { check(pmg_matrix_update_values(_m, nullptr)); }
   std::size_t nnz() const { return (std::size_t)pmg_matrix_nnz(_m); } // :92-93
   std::size_t rows() const { return (std::size_t)pmg_matrix_rows(_m); }
-  T norm() const // the "A norm" of :95-99
+  std::size_t cols() const { return (std::size_t)pmg_matrix_cols(_m); }
+  T norm() const // the "A norm" of :95-99 (over all ranks: collective)
   {
     double r = 0;
     check(pmg_matrix_frobenius_norm(_m, &r));

@@ -207,15 +207,19 @@ _SIGS = {
     "pmg_multigrid_set_fused_restriction": (C.c_int, [vp, C.c_int]),
     "pmg_multigrid_fused_restrictions": (C.c_int, [vp]),
     "pmg_matrix_create_from_laplacian": (C.c_int, [C.POINTER(vp), vp, vp]),
+    "pmg_matrix_create_distributed": (C.c_int, [C.POINTER(vp), vp, vp]),
     "pmg_matrix_destroy": (C.c_int, [vp]),
     "pmg_matrix_update_values": (C.c_int, [vp, vp]),
     "pmg_matrix_apply": (C.c_int, [vp, vp, vp, vp]),
+    "pmg_matrix_apply_ghosts_current": (C.c_int, [vp, vp, vp, vp]),
     "pmg_matrix_get_diag_inverse": (C.c_int, [vp, vp, vp]),
     "pmg_matrix_rows": (C.c_longlong, [vp]),
+    "pmg_matrix_cols": (C.c_longlong, [vp]),
     "pmg_matrix_nnz": (C.c_longlong, [vp]),
     "pmg_matrix_bytes": (C.c_longlong, [vp]),
     "pmg_matrix_frobenius_norm": (C.c_int, [vp, c_dp]),
     "pmg_matrix_export": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_ip, c_ip, c_dp]),
+    "pmg_matrix_export_split": (C.c_int, [vp, c_ip, C.POINTER(C.c_longlong), c_ip]),
     "pmg_chebyshev_solve_matrix": (C.c_int, [vp, vp, vp, vp, vp]),
     "pmg_cg_solve_matrix": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
     "pmg_multigrid_set_level_matrix": (C.c_int, [vp, C.c_int, vp]),
@@ -244,7 +248,7 @@ _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplac
                 "pmg_laplacian_has_coefficient_field", "pmg_laplacian_has_coefficient_tensor", "pmg_laplacian_has_reaction", "pmg_laplacian_has_robin", "pmg_laplacian_lift_cell_count",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_laplacian_geometry_degree", "pmg_layout_forward_scatters",
-                "pmg_matrix_rows", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions",
+                "pmg_matrix_rows", "pmg_matrix_cols", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions",
                 "pmg_chebyshev_recomputed", "pmg_cg_nullspace", "pmg_amg_nullspace"}
 
 _lib = None

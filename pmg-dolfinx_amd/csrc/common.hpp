@@ -363,6 +363,7 @@ int laplacian_apply(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_zeroed(pmg_laplacian op, double* in, double* out, hipStream_t s);
 int laplacian_apply_ghosts_current(pmg_laplacian op, double* in, double* out, hipStream_t s);
 bool laplacian_wants_zeroed_output(pmg_laplacian op);
+bool laplacian_single_launch(pmg_laplacian op); // a small level on halo windows: the exchange whole, then one launch
 const double* laplacian_diag_inv(pmg_laplacian op);
 const double* laplacian_reaction(pmg_laplacian op); // the diagonal term, d_sigma + d_R; nullptr = none
 // An input of the operator was set or removed -- the nodal field, the per-cell tensor, a component of the diagonal term
@@ -404,7 +405,9 @@ int amg_solve(pmg_amg amg, double* x, const double* b, hipStream_t s);
 pmg_layout amg_layout(pmg_amg amg);
 long long amg_capture_state(pmg_amg amg);
 // matrix.hip -- the assembled form of a level's operator
-int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s);
+// (a distributed matrix refreshes the ghost entries of `in`; _ghosts_current trusts them: no exchange, one launch)
+int matrix_apply(pmg_matrix M, double* in, double* out, hipStream_t s);
+int matrix_apply_ghosts_current(pmg_matrix M, const double* in, double* out, hipStream_t s);
 const double* matrix_diag_inv(pmg_matrix M);
 pmg_layout matrix_layout(pmg_matrix M);
 

@@ -12,8 +12,14 @@
 //                         No atomics, no zero-fill, the same bits on every assembly.
 //   product (device)      matrix_product_kernel: one launch, a sub-wavefront per row, width from the mean row length.
 //
-// Single domain only: the distributed form (diag / off-diag split of src/csr.hpp:114-126, ghost columns) is a follow-up.
+// Several ranks (pmg_matrix_create_distributed): rows are the owned dofs, columns local indices with the ghosts behind
+// the owned ones, so the ghost columns of a row come last and off_diag_offset[i] (src/csr.hpp:114-126) splits it.
+// Every rank holds the ghost-cell layer, so its owned rows are complete locally and no matrix value travels.  The product
+// follows src/csr.hpp:252-270: scatter begin, the diag part of all rows, scatter end, the off-diag part of the boundary
+// rows (matrix_range_product_kernel), with the routing of the matrix-free operator's apply_impl.  The host pattern and
+// the split are in matrix_pattern.hpp.
 #include "laplacian.hpp"
+#include "matrix_pattern.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -26,7 +32,8 @@ struct pmg_matrix_s
   pmg_laplacian op = nullptr; // source of G, kappa, the BC marker and the dofmap; must outlive the matrix
   pmg_layout layout = nullptr;
   int nd = 0, N = 0;
-  int32_t n = 0; // rows = columns = size_local
+  int32_t n = 0;     // rows = size_local
+  int32_t ncols = 0; // columns = size_local + num_ghosts
   long long nnz = 0;
   int32_t* rp = nullptr; // [n + 1]
   int32_t* ci = nullptr; // [nnz], sorted within a row
@@ -40,6 +47,12 @@ struct pmg_matrix_s
   int cap = 0;  // longest row (the LDS copy of a row in the values kernel)
   int tpr = 16; // lanes per row of the product
   double* partials = nullptr; // [NORM_BLOCKS] of the Frobenius norm
+  // the distributed form: does a product exchange the halo of its input (the layout has ghosts or a communicator)?
+  bool exchanges = false;
+  int32_t* od = nullptr;    // [n] off_diag_offset: the position of the row's first ghost column
+  int32_t* brows = nullptr; // [n_brows] the rows with a ghost column, ascending
+  int32_t n_brows = 0;
+  int tpr_diag = 16, tpr_off = 4; // lanes per row of the two phases, each from its own mean range length
 };
 
 namespace
@@ -190,6 +203,40 @@ __global__ void __launch_bounds__(256)
     y[row] = acc;
 }
 
+// The range form of the product, the two phases of a distributed product (src/csr.hpp:252-270): TPR lanes share a row
+// and walk the columns [first[row], last[row]) only.
+//   LISTED = false  the diag phase: every row i < count over [rp[i], od[i]); y[i] is STORED (an empty range stores 0)
+//   LISTED = true   the off-diag phase: the rows rows[i], i < count, over [od[r], rp[r + 1]); the sum is ADDED to y[r]
+// One group writes a row per phase and the phases are stream-ordered: no atomics.
+template <int TPR, bool LISTED>
+__global__ void __launch_bounds__(256)
+    matrix_range_product_kernel(int count, const int32_t* __restrict__ rows, const int32_t* __restrict__ first,
+                                const int32_t* __restrict__ last, const int32_t* __restrict__ ci,
+                                const double* __restrict__ v, const double* __restrict__ x, double* __restrict__ y)
+{
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = gid / TPR, sub = gid % TPR;
+  double acc = 0.0;
+  int row = 0;
+  if (i < count)
+  {
+    row = LISTED ? rows[i] : i;
+    const int e = last[row];
+    for (int k = first[row] + sub; k < e; k += TPR)
+      acc += v[k] * x[ci[k]];
+  }
+#pragma unroll
+  for (int off = TPR / 2; off > 0; off >>= 1)
+    acc += __shfl_down(acc, off, TPR);
+  if (i < count && sub == 0)
+  {
+    if (LISTED)
+      y[row] += acc;
+    else
+      y[row] = acc;
+  }
+}
+
 // block partials of sum v^2, each block over a fixed contiguous share: the same bits on every call
 __global__ void __launch_bounds__(256)
     matrix_square_sum_kernel(long long nnz, const double* __restrict__ v, double* __restrict__ partials)
@@ -221,13 +268,53 @@ void launch_values(pmg_matrix M, int W, int groups, size_t lds, const double* Gc
       op->bc, op->D, laplacian_reaction(op));
 }
 
-int check_source(pmg_laplacian op, const char* who)
+// one phase of the distributed product: the diag part of all rows (stored), or the off-diag part of the boundary rows
+// (added); a rank without boundary rows launches nothing in the second
+int launch_range(pmg_matrix M, bool off_diag, const double* in, double* out, hipStream_t s)
 {
-  pmg_layout l = op->layout;
-  PMG_REQUIRE(l->num_ghosts == 0 && !l->multi_rank() && !l->win && !l->exchange,
+  const int count = off_diag ? M->n_brows : M->n;
+  if (count == 0)
+    return PMG_OK;
+  const int tpr = off_diag ? M->tpr_off : M->tpr_diag;
+  const unsigned blocks = (unsigned)(((long long)count * tpr + 255) / 256);
+#define PMG_RANGE_(T)                                                                                                  \
+  case T:                                                                                                              \
+    if (off_diag)                                                                                                      \
+      matrix_range_product_kernel<T, true><<<blocks, 256, 0, s>>>(count, M->brows, M->od, M->rp + 1, M->ci, M->v, in,  \
+                                                                  out);                                                \
+    else                                                                                                               \
+      matrix_range_product_kernel<T, false><<<blocks, 256, 0, s>>>(count, nullptr, M->rp, M->od, M->ci, M->v, in,      \
+                                                                   out);                                               \
+    break;
+  switch (tpr)
+  {
+    PMG_RANGE_(4)
+    PMG_RANGE_(8)
+    PMG_RANGE_(16)
+    PMG_RANGE_(32)
+  default:
+    PMG_RANGE_(64)
+  }
+#undef PMG_RANGE_
+  PMG_HIP(hipGetLastError());
+  return PMG_OK;
+}
+
+// does a vector of this layout have a halo to exchange?
+bool layout_is_distributed(pmg_layout l) { return l->num_ghosts > 0 || l->multi_rank() || l->win || l->exchange; }
+
+// pmg_matrix_create_from_laplacian keeps its contract: one domain (pmg_matrix_create_distributed takes any layout)
+int check_single_domain(pmg_laplacian op, const char* who)
+{
+  PMG_REQUIRE(!layout_is_distributed(op->layout),
               "%s: the assembled operator is single-domain only (the layout has ghosts or a communicator); the "
               "distributed form with its diag / off-diag split is a follow-up",
               who);
+  return PMG_OK;
+}
+
+int check_source(pmg_laplacian op, const char* who)
+{
   PMG_REQUIRE(op->batch_patches == 0,
               "%s: the operator is in batched-geometry mode, its tensor G is not resident "
               "(pmg_laplacian_set_geometry_batch(op, 0) keeps it)",
@@ -270,7 +357,8 @@ int assemble_values(pmg_matrix M, hipStream_t s)
 namespace pmg
 {
 // used by solvers.hip
-int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s)
+// out = A in over whole rows, one launch: a single domain, or the ghost entries of `in` are current
+int matrix_apply_ghosts_current(pmg_matrix M, const double* in, double* out, hipStream_t s)
 {
   if (M->n == 0)
     return PMG_OK;
@@ -287,75 +375,37 @@ int matrix_apply(pmg_matrix M, const double* in, double* out, hipStream_t s)
   PMG_HIP(hipGetLastError());
   return PMG_OK;
 }
+
+// operator()(x, y), src/csr.hpp:252-270, with the routing of the matrix-free operator's apply_impl (laplacian.hip).  On
+// a distributed matrix the ghost entries of `in` are refreshed and those of `out` are not touched.
+int matrix_apply(pmg_matrix M, double* in, double* out, hipStream_t s)
+{
+  if (!M->exchanges)
+    return matrix_apply_ghosts_current(M, in, out, s);
+  pmg_layout l = M->layout;
+  // a small level on halo windows (the operator's own rule): the exchange whole, in one launch, then whole rows
+  if (laplacian_single_launch(M->op))
+  {
+    PMG_TRY(scatter_fwd_whole(l, in, s));
+    return matrix_apply_ghosts_current(M, in, out, s);
+  }
+  PMG_TRY(pmg_scatter_fwd_begin(l, in, (pmg_stream)s)); // :254
+  PMG_TRY(launch_range(M, false, in, out, s));          // :256-261 the owned columns of every row
+  PMG_TRY(pmg_scatter_fwd_end(l, in, (pmg_stream)s));   // :263
+  PMG_TRY(launch_range(M, true, in, out, s));           // :265-269 the ghost columns of the boundary rows
+  return PMG_OK;
+}
 const double* matrix_diag_inv(pmg_matrix M) { return M->dinv; }
 pmg_layout matrix_layout(pmg_matrix M) { return M->layout; }
 pmg_laplacian matrix_source(pmg_matrix M) { return M->op; }
-
-// The pattern of dolfinx's create_sparsity_pattern from a dofmap (host): dof -> (cell, local node) incidences in
-// ascending cell order, then per row the sorted distinct dofs of its cells (a row no listed cell touches keeps its
-// diagonal).  Returns the nnz; the arrays are filled only while it fits int32.
-long long matrix_pattern(int32_t n, int N, const std::vector<int32_t>& cells, const int32_t* dofmap,
-                         std::vector<int32_t>& inc_off, std::vector<int32_t>& inc_cell, std::vector<int32_t>& inc_loc,
-                         std::vector<int32_t>& rp, std::vector<int32_t>& ci, int* longest)
-{
-  inc_off.assign((size_t)n + 1, 0);
-  for (int32_t c : cells)
-    for (int t = 0; t < N; ++t)
-      inc_off[(size_t)dofmap[(size_t)c * N + t] + 1]++;
-  for (int32_t i = 0; i < n; ++i)
-    inc_off[i + 1] += inc_off[i];
-  inc_cell.resize(inc_off[n]);
-  inc_loc.resize(inc_off[n]);
-  {
-    std::vector<int32_t> at(inc_off.begin(), inc_off.end() - 1);
-    for (int32_t c : cells) // ascending: the order of the sums
-      for (int t = 0; t < N; ++t)
-      {
-        const int32_t k = at[dofmap[(size_t)c * N + t]]++;
-        inc_cell[k] = c;
-        inc_loc[k] = t;
-      }
-  }
-  rp.assign((size_t)n + 1, 0);
-  ci.clear();
-  std::vector<int32_t> seen(n, -1), row;
-  long long nnz = 0;
-  *longest = 0;
-  for (int32_t i = 0; i < n; ++i)
-  {
-    row.clear();
-    row.push_back(i);
-    seen[i] = i;
-    for (int32_t m = inc_off[i]; m < inc_off[i + 1]; ++m)
-    {
-      const int32_t* dm = dofmap + (size_t)inc_cell[m] * N;
-      for (int t = 0; t < N; ++t)
-        if (seen[dm[t]] != i)
-        {
-          seen[dm[t]] = i;
-          row.push_back(dm[t]);
-        }
-    }
-    nnz += (long long)row.size();
-    *longest = std::max(*longest, (int)row.size());
-    if (nnz <= INT32_MAX)
-    {
-      std::sort(row.begin(), row.end());
-      ci.insert(ci.end(), row.begin(), row.end());
-      rp[i + 1] = (int32_t)nnz;
-    }
-  }
-  return nnz;
-}
 } // namespace pmg
 
-// MatrixOperator(a, bcs), src/csr.hpp:66-131
-extern "C" int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian op, pmg_stream stream)
+namespace
 {
-  PMG_REQUIRE(out && op, "pmg_matrix_create_from_laplacian: NULL argument");
-  *out = nullptr;
-  PMG_TRY(check_source(op, "pmg_matrix_create_from_laplacian"));
-  hipStream_t s = S(stream);
+// MatrixOperator(a, bcs), src/csr.hpp:66-131: the body of both constructors, in `who`'s name
+int matrix_create(pmg_matrix* out, pmg_laplacian op, hipStream_t s, const char* who)
+{
+  PMG_TRY(check_source(op, who));
   auto* M = new pmg_matrix_s;
   HandleGuard<pmg_matrix> guard(M, pmg_matrix_destroy);
   M->op = op;
@@ -363,6 +413,8 @@ extern "C" int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian o
   M->nd = op->nd;
   M->N = op->N;
   M->n = op->layout->size_local;
+  M->ncols = op->layout->total();
+  M->exchanges = layout_is_distributed(op->layout);
   const int N = M->N;
   // the operator's own dofmap (ascending node order) and the cells it applies
   std::vector<int32_t> h_dofmap((size_t)op->ncells * N);
@@ -378,21 +430,30 @@ extern "C" int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian o
     for (int t = 0; t < N; ++t)
     {
       const int32_t d = h_dofmap[(size_t)c * N + t];
-      PMG_REQUIRE(d >= 0 && d < M->n, "pmg_matrix_create_from_laplacian: dofmap entry %d out of range", d);
+      PMG_REQUIRE(d >= 0 && d < M->ncols, "%s: dofmap entry %d out of range", who, d);
     }
-  std::vector<int32_t> inc_off, inc_cell, inc_loc, rp, ci;
-  const long long nnz = matrix_pattern(M->n, N, cells, h_dofmap.data(), inc_off, inc_cell, inc_loc, rp, ci, &M->cap);
-  PMG_REQUIRE(nnz <= INT32_MAX,
-              "pmg_matrix_create_from_laplacian: the pattern has %lld non-zeros, more than int32 indices hold", nnz);
+  std::vector<int32_t> inc_off, inc_cell, inc_loc, rp, ci, od, brows;
+  const long long nnz =
+      matrix_pattern(M->n, M->ncols, N, cells, h_dofmap.data(), inc_off, inc_cell, inc_loc, rp, ci, &M->cap);
+  PMG_REQUIRE(nnz <= INT32_MAX, "%s: the pattern has %lld non-zeros, more than int32 indices hold", who, nnz);
   PMG_REQUIRE(sizeof(double) * ((size_t)M->cap + M->nd * M->nd) <= LDS_LIMIT,
-              "pmg_matrix_create_from_laplacian: a row of %d entries exceeds the %zu the assembly holds in LDS", M->cap,
+              "%s: a row of %d entries exceeds the %zu the assembly holds in LDS", who, M->cap,
               LDS_LIMIT / sizeof(double) - M->nd * M->nd);
   M->nnz = nnz;
   M->n_inc = (long long)inc_cell.size();
-  const double mean = M->n ? (double)nnz / M->n : 1.0;
-  M->tpr = mean > 96 ? 64 : mean > 48 ? 32 : mean > 20 ? 16 : mean > 10 ? 8 : 4;
+  M->tpr = matrix_lanes_per_row(M->n ? (double)nnz / M->n : 1.0);
+  // the split: each phase of the product takes its lanes from its own mean range length
+  matrix_split(M->n, rp, ci, od, brows);
+  M->n_brows = (int32_t)brows.size();
+  long long n_off = 0;
+  for (int32_t r : brows)
+    n_off += rp[r + 1] - od[r];
+  M->tpr_diag = matrix_lanes_per_row(M->n ? (double)(nnz - n_off) / M->n : 1.0);
+  M->tpr_off = matrix_lanes_per_row(M->n_brows ? (double)n_off / M->n_brows : 1.0);
   PMG_TRY(to_device(&M->rp, rp.data(), rp.size()));
   PMG_TRY(to_device(&M->ci, ci.data(), ci.size()));
+  PMG_TRY(to_device(&M->od, od.data(), od.size()));
+  PMG_TRY(to_device(&M->brows, brows.data(), brows.size()));
   PMG_TRY(to_device(&M->inc_off, inc_off.data(), inc_off.size()));
   PMG_TRY(to_device(&M->inc_cell, inc_cell.data(), inc_cell.size()));
   PMG_TRY(to_device(&M->inc_loc, inc_loc.data(), inc_loc.size()));
@@ -403,6 +464,24 @@ extern "C" int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian o
   *out = guard.release();
   return PMG_OK;
 }
+} // namespace
+
+// MatrixOperator(a, bcs) on one domain
+extern "C" int pmg_matrix_create_from_laplacian(pmg_matrix* out, pmg_laplacian op, pmg_stream stream)
+{
+  PMG_REQUIRE(out && op, "pmg_matrix_create_from_laplacian: NULL argument");
+  *out = nullptr;
+  PMG_TRY(check_single_domain(op, "pmg_matrix_create_from_laplacian"));
+  return matrix_create(out, op, S(stream), "pmg_matrix_create_from_laplacian");
+}
+
+// ... and on any layout: rows = the owned dofs, columns = owned and ghost dofs, split per row
+extern "C" int pmg_matrix_create_distributed(pmg_matrix* out, pmg_laplacian op, pmg_stream stream)
+{
+  PMG_REQUIRE(out && op, "pmg_matrix_create_distributed: NULL argument");
+  *out = nullptr;
+  return matrix_create(out, op, S(stream), "pmg_matrix_create_distributed");
+}
 
 extern "C" int pmg_matrix_destroy(pmg_matrix M)
 {
@@ -410,6 +489,8 @@ extern "C" int pmg_matrix_destroy(pmg_matrix M)
     return PMG_OK;
   (void)hipFree(M->rp);
   (void)hipFree(M->ci);
+  (void)hipFree(M->od);
+  (void)hipFree(M->brows);
   (void)hipFree(M->v);
   (void)hipFree(M->dinv);
   (void)hipFree(M->inc_off);
@@ -426,12 +507,20 @@ extern "C" int pmg_matrix_update_values(pmg_matrix M, pmg_stream stream)
   return assemble_values(M, S(stream));
 }
 
-// operator()(x, y), src/csr.hpp:220-260 (no transpose: the operator is symmetric)
+// operator()(x, y), src/csr.hpp:220-260 (no transpose: the operator is symmetric).  The signature is the single-domain
+// one; a distributed matrix writes the ghost entries of `in`, as the reference's operator does through its scatter.
 extern "C" int pmg_matrix_apply(pmg_matrix M, const double* in, double* out, pmg_stream stream)
 {
   PMG_REQUIRE(M && in && out, "pmg_matrix_apply: NULL argument");
   PMG_REQUIRE(in != out, "pmg_matrix_apply: in and out alias");
-  return matrix_apply(M, in, out, S(stream));
+  return matrix_apply(M, const_cast<double*>(in), out, S(stream));
+}
+
+extern "C" int pmg_matrix_apply_ghosts_current(pmg_matrix M, const double* in, double* out, pmg_stream stream)
+{
+  PMG_REQUIRE(M && in && out, "pmg_matrix_apply_ghosts_current: NULL argument");
+  PMG_REQUIRE(in != out, "pmg_matrix_apply_ghosts_current: in and out alias");
+  return matrix_apply_ghosts_current(M, in, out, S(stream));
 }
 
 // get_diag_inverse, src/csr.hpp:205-209
@@ -445,15 +534,19 @@ extern "C" int pmg_matrix_get_diag_inverse(pmg_matrix M, double* diag_inv, pmg_s
 
 extern "C" long long pmg_matrix_rows(pmg_matrix M) { return M ? (long long)M->n : -1; }
 
+extern "C" long long pmg_matrix_cols(pmg_matrix M) { return M ? (long long)M->ncols : -1; }
+
 extern "C" long long pmg_matrix_nnz(pmg_matrix M) { return M ? M->nnz : -1; }
 
-// device bytes held: row pointers, columns, values, inverse diagonal and the incidence lists of update_values
+// device bytes held: row pointers, columns, values, inverse diagonal, the incidence lists of update_values and the
+// split (off_diag_offset, boundary rows)
 extern "C" long long pmg_matrix_bytes(pmg_matrix M)
 {
   if (!M)
     return -1;
   return (long long)sizeof(int32_t) * 2 * ((long long)M->n + 1) + (long long)(sizeof(int32_t) + sizeof(double)) * M->nnz
-         + (long long)sizeof(double) * M->n + 2LL * sizeof(int32_t) * M->n_inc;
+         + (long long)sizeof(double) * M->n + 2LL * sizeof(int32_t) * M->n_inc
+         + (long long)sizeof(int32_t) * ((long long)M->n + M->n_brows);
 }
 
 // the "A norm" of src/csr.hpp:95-99
@@ -470,7 +563,30 @@ extern "C" int pmg_matrix_frobenius_norm(pmg_matrix M, double* norm)
     for (double p : h)
       sum += p;
   }
+  // several ranks: every owned row lives on exactly one rank, so the global norm is the all-reduced sum of squares
+  // (collective; result slot 7, no solver's)
+  if (pmg_layout l = M->layout; l->multi_rank())
+  {
+    PMG_HIP(hipMemcpy(red_slot(l, 7), &sum, sizeof(double), hipMemcpyHostToDevice));
+    PMG_TRY(reduce_slots_async(l, 7, 1, false, nullptr));
+    PMG_TRY(fetch_slots(l, 7, 1, &sum, nullptr));
+  }
   *norm = std::sqrt(sum);
+  return PMG_OK;
+}
+
+// the split of the rows: off_diag_offset[rows] and the boundary-row list; NULL arrays: sizes only
+extern "C" int pmg_matrix_export_split(pmg_matrix M, int32_t* off_diag_offset, long long* n_boundary_rows,
+                                       int32_t* boundary_rows)
+{
+  PMG_REQUIRE(M, "pmg_matrix_export_split: NULL argument");
+  if (n_boundary_rows)
+    *n_boundary_rows = M->n_brows;
+  PMG_HIP(hipDeviceSynchronize());
+  if (off_diag_offset && M->n)
+    PMG_HIP(hipMemcpy(off_diag_offset, M->od, sizeof(int32_t) * (size_t)M->n, hipMemcpyDeviceToHost));
+  if (boundary_rows && M->n_brows)
+    PMG_HIP(hipMemcpy(boundary_rows, M->brows, sizeof(int32_t) * (size_t)M->n_brows, hipMemcpyDeviceToHost));
   return PMG_OK;
 }
 

@@ -194,18 +194,20 @@ int recompute_buffers(pmg_chebyshev sm, hipStream_t s)
 }
 
 // The call of smoother `sm`: the one place where a SmoothCall is read off the library's objects.  A = the matrix-free
-// operator it runs on, nullptr for a plain product (an assembled matrix, the float apply): single domain, no output
-// rule, no recomputed form.  track_ghosts / ghosts_current: the exchange bookkeeping of the V-cycle (local_correction).
+// operator it runs on, nullptr for a plain product (an assembled matrix, the float apply): no output rule, no
+// recomputed form.  track_ghosts / ghosts_current: the exchange bookkeeping of the V-cycle (local_correction); it holds
+// for every operator that refreshes the ghosts of its input -- the matrix-free one and a distributed matrix
+// (`exchanging`) --, not for the float apply, which is single-domain.
 SmoothCall smoother_call(pmg_chebyshev sm, pmg_laplacian A, int need_r, bool x_zero, bool track_ghosts = false,
-                         bool ghosts_current = false)
+                         bool ghosts_current = false, bool exchanging = false)
 {
   SmoothCall c;
   c.k = sm->max_iter;
   c.need_r = need_r;
   c.x_zero = x_zero;
   c.zeroed_output = A && laplacian_wants_zeroed_output(A);
-  c.ghosts = A && track_ghosts ? sm->layout->num_ghosts : 0;
-  c.ghosts_current = A && ghosts_current;
+  c.ghosts = (A || exchanging) && track_ghosts ? sm->layout->num_ghosts : 0;
+  c.ghosts_current = (A || exchanging) && ghosts_current;
   c.allow_recompute = A && wants_recompute(sm);
   return c;
 }
@@ -235,8 +237,9 @@ int cheb_solve(pmg_chebyshev sm, pmg_laplacian A, double* x, const double* b, Sm
   return PMG_OK;
 }
 
-// the same smoother on the assembled operator `M`: its product, its own inverse diagonal (single domain: no ghosts);
-// *applies (optional) counts the products issued
+// the same smoother on the assembled operator `M`: its product (on several ranks with its halo exchange, or without
+// where the call's bookkeeping says the ghosts are current), its own inverse diagonal; *applies (optional) counts the
+// products issued
 int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b, const SmoothCall& call, hipStream_t s,
                       long long* applies = nullptr)
 {
@@ -245,6 +248,8 @@ int cheb_solve_matrix(pmg_chebyshev sm, pmg_matrix M, double* x, const double* b
   SmoothData<double> d;
   d.w = {sm->r, sm->z, sm->q};
   d.apply[SmoothStep::PLAIN] = [M, s](double* in, double* out) { return matrix_apply(M, in, out, s); };
+  d.apply[SmoothStep::GHOSTS_CURRENT] = [M, s](double* in, double* out)
+  { return matrix_apply_ghosts_current(M, in, out, s); };
   d.dinv = matrix_diag_inv(M);
   d.n = l->size_local, d.n_total = l->total();
   d.lmax = sm->eig_max;
@@ -396,7 +401,7 @@ SmoothCall level_call(pmg_multigrid mg, int i, SmoothRole role, bool y_zero)
   const bool x_zero = role != PostSmooth && (i == mg->L - 1 ? y_zero : true);
   const bool local = local_correction(mg, i);
   return smoother_call(sm, mg->mats[i] ? nullptr : mg->ops[i], need_r, x_zero, local && role == PreSmooth,
-                       local && role == PostSmooth);
+                       local && role == PostSmooth, mg->mats[i] != nullptr);
 }
 
 // the smoother of level i on whichever form of the operator the level has (pmg_multigrid_set_level_matrix)

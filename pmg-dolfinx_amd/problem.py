@@ -177,7 +177,9 @@ class PoissonHierarchy:
         self.matrices = {}
         for i in assembled_levels:
             i = int(i) % len(self.orders)
-            self.matrices[i] = MatrixOperator(self.operators[i])
+            # on several ranks the distributed form (ghost columns, diag / off-diag split)
+            several = self.levels[i].num_ghosts > 0 or comm is not None or group is not None
+            self.matrices[i] = MatrixOperator(self.operators[i], distributed=several)
             self.mg.set_level_matrix(i, self.matrices[i])
 
     @property
