@@ -10,6 +10,9 @@
 //   --amg            coarse solver on the degree-1 level (:331-335): CG <= 60 iterations, rtol 1e-5,
 //                    preconditioned by the library's algebraic multigrid (hypre's role)
 //   --amg-cycles N   the same hierarchy as N stationary AMG cycles instead of the Krylov solve
+//   --amg-renew      (implies --amg) the AMG is created on the degree-1 operator BEFORE --kappa-field, --kappa-tensor,
+//                    --reaction and --robin are applied to it and renewed in place after them (pmg_amg_update_values);
+//                    one line reports levels, rows and the renewal's milliseconds; everything else as without the flag
 //   --csr [LEVELS]   the listed levels (comma-separated indices; default all) as assembled CSR matrices
 //   --coarse-cg      Jacobi-preconditioned CG (60 iterations) as the coarse solver
 //   --pcg            additionally solve with CG preconditioned by the cycle (random right-hand side
@@ -103,6 +106,7 @@ struct Options : examples::RankOptions
   std::string output;
   pmg_amd::NodeOrder node_order = pmg_amd::NodeOrder::ascending; // of the dofmaps handed to the library
   bool amg_gather = false; // --amg-setup gathered
+  bool amg_renew = false;  // --amg-renew: the AMG created before the coefficient options, renewed in place after them
   bool kappa_field = false;    // --kappa-field: the smooth nodal coefficient 1 + 0.5 sin(2 pi x) cos(2 pi y) + z
   bool kappa_tensor = false;   // --kappa-tensor: per-cell tensor, eigenvalues (1, 2 + x, 4) rotated by Rz(0.6 + 0.8 y) Rx(0.4 + 0.5 z)
   double reaction = 0.0;       // --reaction S: sigma_c = S (1 + x_c); 0 = no term
@@ -186,12 +190,15 @@ void solve(const Options& o)
   const bool manufactured = o.neumann && !o.curved && !o.kappa_field && !o.kappa_tensor;
   std::vector<std::shared_ptr<FineOperator>> operators(V.size());
   std::vector<std::shared_ptr<DeviceVector>> bs(V.size());
+  std::shared_ptr<CoarseSolverType<T>> coarse_solver; // :331-335
   for (std::size_t i = 0; i < V.size(); i++)
   {
     operators[i] = std::make_shared<acc::MatFreeLaplacian<T>>(
         order[i], device_constants, device_dofmaps[i], geom_x, geom_x_dofmap, geometry_dphi_d_span[i],
         Gweights_d_span[i], lcells, bcells, bc_marker_d_span[i], 0, o.node_order); // :270-272
     const examples::PartitionLevel& lv = V[i]->lv;
+    if (i == 0 && o.amg_renew) // the hierarchy of the operator as created (constant kappa, no term); renewed below
+      coarse_solver = std::make_shared<CoarseSolverType<T>>(*operators[0], maps[0]);
     if (o.kappa_field) // -div(kappa kq(x) grad u): the field at this level's dof coordinates, before the diagonal
     {
       std::vector<T> kh(lv.ndofs());
@@ -222,6 +229,14 @@ void solve(const Options& o)
       operators[i]->set_robin(rb.cells, rb.local_facets, alpha.span()); // (collective: a rank without a facet calls too)
     }
     operators[i]->compute_diag_inverse(maps[i]);                  // replaces :274-279 (no CSR)
+    if (i == 0 && o.amg_renew) // pmg_amg_update_values: every value from the operator's current data, aggregates kept
+    {
+      auto t0 = std::chrono::steady_clock::now();
+      coarse_solver->update_values();
+      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      std::printf("AMG renewed in place: %d levels, %lld rows, %.2f ms\n", coarse_solver->num_levels(),
+                  (long long)lv.size_local, ms);
+    }
 
     std::vector<T> fh(lv.ndofs());
     const double pi = M_PI, c2 = (4.0 + 9.0 + 16.0) * pi * pi;
@@ -291,11 +306,12 @@ void solve(const Options& o)
         device_dofmaps[i + 1], lcells, bcells, o.node_order);
   }
 
-  std::shared_ptr<CoarseSolverType<T>> coarse_solver; // :331-335
   if (o.use_amg)
   {
     auto t0 = std::chrono::steady_clock::now();
-    if (size > 1) // first coarsening per rank, level 1 gathered on every rank (--amg-setup gathered: the global
+    if (coarse_solver) // --amg-renew: created and renewed above
+      ;
+    else if (size > 1) // first coarsening per rank, level 1 gathered on every rank (--amg-setup gathered: the global
                   // degree-1 matrix on every rank instead); one all-reduce of a level-1 vector per cycle
       coarse_solver = std::make_shared<CoarseSolverType<T>>(*operators[0], maps[0], V[0]->lv.local_to_global,
                                                            mesh.global_ndofs(order[0]), o.amg_gather);
@@ -557,6 +573,8 @@ int main(int argc, char** argv)
       }
       else if (!std::strcmp(argv[i], "--id-file"))
         o.id_file = next();
+      else if (!std::strcmp(argv[i], "--amg-renew"))
+        o.use_amg = o.amg_renew = true;
       else if (!std::strcmp(argv[i], "--amg-setup"))
       {
         const std::string v = next();
@@ -581,7 +599,7 @@ int main(int argc, char** argv)
       else
       {
         std::cout << "usage: pmg [--n cells_per_direction | --ndofs N_per_rank] [--orders 1,2,4] [--smoother-its K]\n"
-                     "           [--cycles C] [--pcg [--random-rhs]] [--amg | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
+                     "           [--cycles C] [--pcg [--random-rhs]] [--amg [--amg-renew] | --amg-cycles N | --coarse-cg] [--graph] [--fp32-cycle] [--csr [LEVELS]]\n"
                      "           [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--neumann]\n"
                      "           [--ranks px,py,pz [--rank r] [--id-file F]] [--native-comm] [--halo exchange|windows]\n"
                      "           [--comm rccl|windows]\n"
@@ -601,6 +619,8 @@ int main(int argc, char** argv)
     if (o.neumann && (o.reaction > 0.0 || o.robin > 0.0))
       throw std::runtime_error("--neumann with --reaction or --robin: the operator is then not singular, and "
                                "projecting out the constants would be wrong");
+    if (o.amg_renew && size > 1)
+      throw std::runtime_error("--amg-renew on several ranks: pmg_amg_update_values serves the single-domain hierarchy");
     if (o.neumann && o.use_amg && size > 1)
       throw std::runtime_error("--neumann with --amg on several ranks: the replicated and distributed AMG take no "
                                "null space");

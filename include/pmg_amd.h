@@ -413,7 +413,8 @@ int pmg_laplacian_get_geometry(pmg_laplacian op, double* G_out, pmg_stream strea
  * geometry mode every application folds the field in as it recomputes its batch), the float tensor if it has been
  * built, and the inverse diagonal if it came from pmg_laplacian_compute_diag_inverse (a diagonal installed with
  * pmg_laplacian_set_diag_inverse is left alone).  An assembled matrix follows with pmg_matrix_update_values; a
- * smoother's eigenvalue bound and an AMG hierarchy are the caller's to renew.  All buffers are rebuilt in place and
+ * smoother's eigenvalue bound and an AMG hierarchy are the caller's to renew (the hierarchy in place, with
+ * pmg_amg_update_values).  All buffers are rebuilt in place and
  * keep their addresses, so a captured V-cycle graph over the resident tensor stays valid (an FP32 cycle re-captures
  * because the diagonal changed; in batched-geometry mode the captured geometry launches carry the field's address,
  * and setting the first field or removing it re-captures).  Like the other set-up calls it allocates and
@@ -441,7 +442,8 @@ int pmg_laplacian_has_coefficient_field(pmg_laplacian op);
  * its batch), the float tensor if it has been built, the per-cell tensor of the affine mode (it becomes
  * adj(J) K adj(J)^T / detJ), and the inverse diagonal if it came from pmg_laplacian_compute_diag_inverse (a diagonal
  * installed with pmg_laplacian_set_diag_inverse is left alone).  An assembled matrix follows with
- * pmg_matrix_update_values; a smoother's eigenvalue bound and an AMG hierarchy are the caller's to renew.  A captured
+ * pmg_matrix_update_values; a smoother's eigenvalue bound and an AMG hierarchy are the caller's to renew (the hierarchy
+ * in place, with pmg_amg_update_values).  A captured
  * V-cycle graph over the resident tensor stays valid (an FP32 cycle re-captures because the diagonal changed; in
  * batched-geometry mode the captured geometry launches carry the tensor's address, and setting the first tensor or
  * removing it re-captures).  Like the other set-up calls it allocates and synchronises the stream: not inside a stream
@@ -478,7 +480,8 @@ int pmg_laplacian_has_coefficient_tensor(pmg_laplacian op);
  * pmg_laplacian_set_diag_inverse is left alone).  d is summed with atomics: two sets of the same values agree to
  * rounding, not bit for bit.  An assembled matrix follows with pmg_matrix_update_values (d on the diagonal of the
  * unmarked rows); a smoother's eigenvalue bound and an AMG hierarchy (d on the diagonal of its level 0) are the
- * caller's to renew.  The first set and the removal change a kernel argument, so cached V-cycle graphs re-capture; a
+ * caller's to renew (the hierarchy in place, with pmg_amg_update_values).  The first set and the removal change a
+ * kernel argument, so cached V-cycle graphs re-capture; a
  * second set with other values keeps them valid.  Like the other set-up calls it allocates and synchronises the
  * stream: not inside a stream capture (refused).  pmg_laplacian_apply_lifting, pmg_laplacian_set_bc,
  * pmg_laplacian_assemble_rhs and pmg_laplacian_assemble_neumann do not change: a diagonal term couples no unmarked row
@@ -549,7 +552,8 @@ int pmg_laplacian_lift_cell_count(pmg_laplacian op);
  * chain form is bypassed while either term is set (pmg_laplacian_launches_per_apply counts the column launches), the
  * float copy and an inverse diagonal computed by pmg_laplacian_compute_diag_inverse -- 1 / (diag(A) + d_sigma + d_R)
  * -- follow the call, pmg_matrix_update_values and pmg_amg_create* read the summed vector, and the smoother's
- * eigenvalue bound and an AMG hierarchy are the caller's to renew.  Setting either term a second time, or adding the
+ * eigenvalue bound and an AMG hierarchy are the caller's to renew (the hierarchy in place, with
+ * pmg_amg_update_values).  Setting either term a second time, or adding the
  * second term beside the first, rewrites the vector in place: cached V-cycle graphs stay valid.  The first term set and
  * the last term removed change a kernel argument: they re-capture.  pmg_laplacian_set_reaction(op, NULL) while a Robin
  * term is set leaves the vector equal to d_R.
@@ -959,6 +963,29 @@ int pmg_amg_level_info(pmg_amg amg, int level, long long* rows, long long* nnz, 
  * level + 1 to `level`; CSR.  Call with NULL arrays first to learn the sizes. */
 int pmg_amg_export(pmg_amg amg, int level, int which, long long* rows, long long* cols, long long* nnz,
                    int32_t* rowptr, int32_t* colidx, double* values);
+/* Renew the hierarchy in place after the operator's data changed (pmg_laplacian_set_coefficient_field, _tensor,
+ * set_reaction, set_robin): every value -- A_0 from the operator's stored tensor, kappa, the marker and the diagonal
+ * vector; per level the inverse diagonal, the bound 1.05 x 20 power steps, P_l = (I - 4/(3 rho_l) D^-1 A_l) T_l, its
+ * transpose, A_l P_l and A_{l+1} -- is recomputed on the device; the coarsest inverse (both, with the null-space mode
+ * on) is the host's Cholesky of the downloaded A_c, uploaded in place.  The aggregates, the tentative weights and the
+ * level sizes stay those of the creation, and so does the handle: a multigrid object keeps it (its cached V-cycle
+ * graphs re-capture: the bounds are kernel arguments).  The first call plans on the host: the structural patterns of
+ * P_l (every aggregate that an entry of the row of A_l reaches which some coefficient can make non-zero, stored zeros
+ * of the current values included -- the created P_l stores no exact zero, so its pattern depends on the coefficient it
+ * was created for; left out are only the entries of A_0 between the two ends of a cell's body diagonal, which no
+ * quadrature point couples), of its transpose and of the two products on the stored patterns; a level whose structural pattern is larger than the created one gets new device arrays, and a scratch copy
+ * of the tensor (48 doubles per cell) is kept.  Later calls allocate nothing.  Sums are in a fixed order and there are
+ * no atomics: two updates from the same data give the same bytes.  Afterwards pmg_amg_level_info reports the new
+ * bounds and the structural entry counts, pmg_amg_export downloads the current values on the structural patterns
+ * (explicit zeros are possible) and pmg_amg_updates is one higher.  Refused with PMG_ERR_INVALID, nothing touched:
+ * NULL; a replicated or distributed hierarchy or a layout with several ranks; an operator in batched-geometry mode;
+ * a row of a product longer than the 8192 entries of the kernels' row copy (first call); a call inside a stream
+ * capture -- the call synchronises the stream.  A level without a positive diagonal returns PMG_ERR_NUMERIC naming
+ * the level; pmg_amg_solve and pmg_amg_cycle then refuse the hierarchy until an update succeeds.  The p-levels'
+ * smoother bounds and pmg_laplacian_compute_diag_inverse stay the caller's business. */
+int pmg_amg_update_values(pmg_amg amg, pmg_stream stream);
+/* successful pmg_amg_update_values calls since the creation (0 after it); -1 for NULL */
+long long pmg_amg_updates(pmg_amg amg);
 /* set_coarse_solver (src/pmg.hpp:46) with the library's AMG; NULL restores the smoother. */
 int pmg_multigrid_set_coarse_amg(pmg_multigrid mg, pmg_amg amg);
 

@@ -1076,6 +1076,10 @@ public:
   {
     check(pmg_amg_set_nullspace(_a, constant ? PMG_NULLSPACE_CONSTANT : PMG_NULLSPACE_NONE));
   }
+  /// Renew the hierarchy in place after the operator's coefficients, reaction or Robin term changed: every value
+  /// recomputed on the device, the aggregates kept (pmg_amg_update_values; single-domain hierarchies).
+  void update_values() { check(pmg_amg_update_values(_a, nullptr)); }
+  long long updates() const { return pmg_amg_updates(_a); }
   void solve(Vector& x, Vector& y) // src/amg.hpp:67-68
   {
     check(pmg_amg_solve(_a, x.mutable_array().data(), y.array().data(), &_its, nullptr));

@@ -228,6 +228,8 @@ _SIGS = {
     "pmg_cg_nullspace": (C.c_int, [vp]),
     "pmg_amg_set_nullspace": (C.c_int, [vp, C.c_int]),
     "pmg_amg_nullspace": (C.c_int, [vp]),
+    "pmg_amg_update_values": (C.c_int, [vp, vp]),
+    "pmg_amg_updates": (C.c_longlong, [vp]),
 }
 
 NULLSPACE_MODES = {None: 0, "none": 0, "constant": 1}  # PMG_NULLSPACE_NONE / PMG_NULLSPACE_CONSTANT
@@ -249,7 +251,7 @@ _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplac
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_laplacian_geometry_degree", "pmg_layout_forward_scatters",
                 "pmg_matrix_rows", "pmg_matrix_cols", "pmg_matrix_nnz", "pmg_matrix_bytes", "pmg_multigrid_fused_restrictions",
-                "pmg_chebyshev_recomputed", "pmg_cg_nullspace", "pmg_amg_nullspace"}
+                "pmg_chebyshev_recomputed", "pmg_cg_nullspace", "pmg_amg_nullspace", "pmg_amg_updates"}
 
 _lib = None
 

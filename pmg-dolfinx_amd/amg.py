@@ -61,6 +61,15 @@ class AmgSolver:
     def nullspace(self):
         return "constant" if call("pmg_amg_nullspace", self._handle) == 1 else None
 
+    def update_values(self):
+        """Renew the hierarchy in place after the operator's coefficients, reaction or Robin term changed: every value
+        recomputed on the device from the operator's current data, the aggregates kept (``pmg_amg_update_values``)."""
+        call("pmg_amg_update_values", self._handle, current_stream())
+
+    def updates(self) -> int:
+        """Successful ``update_values`` calls since the creation."""
+        return call("pmg_amg_updates", self._handle)
+
     def solve(self, x: Vector, b: Vector) -> int:
         its = C.c_int()
         call("pmg_amg_solve", self._handle, ptr(x.data), ptr(b.data), C.byref(its), current_stream())

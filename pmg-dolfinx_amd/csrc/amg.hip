@@ -9,6 +9,8 @@
 //   set-up (host, once): smoothed aggregation on the assembled degree-1 stiffness matrix -- the algorithm and
 //     all of its host code are in amg_setup.hpp (free of HIP, checked on the CPU); this file downloads the
 //     operator's data for it, moves its tables between the ranks and uploads what it built.
+//   renewal (device, after a coefficient change): pmg_amg_update_values recomputes every value of the hierarchy on
+//     the aggregates of the set-up -- plan and row routines in amg_renew.hpp, kernels and sequence below.
 //   cycle (device): V(k, k) with the same 4th-kind Chebyshev / Jacobi smoother as the p-levels
 //     (cheb_iterate), lean form (the pre-smoother leaves the residual, the post-smoother skips its
 //     last product), CSR products one sub-wavefront per row.  Nothing synchronises the host.
@@ -30,9 +32,13 @@
 // Parity: unpinned by the reference (third-party arithmetic, no fixture).  The tests compare the
 // device cycle with a numpy restatement of the same hierarchy (oracle/amg_oracle.py) and check the
 // solver's defining properties (symmetry, contraction, h-independent iteration counts).
+#include "amg_renew.hpp"
 #include "amg_setup.hpp"
 #include "common.hpp"
+#include "laplacian.hpp"
 #include "patches.hpp"
+
+#include <memory>
 
 using namespace pmg;
 using namespace pmg::amg_setup;
@@ -180,6 +186,8 @@ struct AmgLevel
   long long nnz = 0;
 };
 
+struct AmgRenewal; // what pmg_amg_update_values plans on its first call (below)
+
 struct pmg_amg_s
 {
   pmg_laplacian op = nullptr; // the degree-1 operator (Krylov mode applies it)
@@ -220,6 +228,13 @@ struct pmg_amg_s
   // host copy of the hierarchy for pmg_amg_export (tests)
   std::vector<HostCsr> hA, hP;
   std::vector<double> hlmax;
+  // Renewal (pmg_amg_update_values): the plan and its device arrays, made by the first call; the number of successful
+  // calls; the values of hA and hP are behind the device's (pmg_amg_export downloads them); an update stopped half-way
+  // (a non-positive diagonal, a failed call), after which the solves refuse the hierarchy until one succeeds; the plain
+  // coarsest inverse is that of the current A_c (false: its Cholesky stopped in the last update)
+  AmgRenewal* renewal = nullptr;
+  long long updates = 0;
+  bool host_stale = false, unusable = false, plain_valid = true;
 };
 
 namespace
@@ -467,14 +482,17 @@ long long amg_capture_state(pmg_amg amg)
 {
   if (amg->cycles <= 0 || (amg->replicated && !amg->layout->comm && amg->layout->allreduce))
     return -1;
+  // (a renewal changes what a captured cycle has in its kernel arguments: the bounds, the coarsest inverse in use)
   return ((long long)amg->cycles << 16) ^ amg->smoother_its ^ (amg->replicated ? 1 << 30 : 0) ^ (amg->dist0 ? 1 << 29 : 0) ^
-         (amg->nullspace ? 1 << 28 : 0);
+         (amg->nullspace ? 1 << 28 : 0) ^ (amg->updates << 32);
 }
 
 // x = (approximately) A^-1 b on the coarsest p-level, x zero on entry is not assumed
 int amg_solve(pmg_amg amg, double* x, const double* b, hipStream_t s)
 {
   Range range("pmg:amg_solve");
+  PMG_REQUIRE(!amg->unusable, "pmg_amg_solve: the last pmg_amg_update_values of this hierarchy did not finish; it is "
+                              "unusable until an update succeeds");
   pmg_layout l = amg->layout;
   const int n = l->size_local;
   if (amg->replicated && amg->dist0)
@@ -974,10 +992,470 @@ extern "C" int pmg_amg_create_distributed(pmg_amg* out, pmg_laplacian op, const 
   return amg_create(out, op, global_index, n_global, stream, true);
 }
 
+// ---- renewal: every value of the hierarchy recomputed on the device, the aggregates kept ---------------------------
+// pmg_amg_update_values.  The plan and the row routines are in amg_renew.hpp (free of HIP, run whole on the CPU by
+// tests/host/amg_update_check.cpp); here are the kernels around the routines -- a sub-wavefront per output row, the row
+// in an LDS copy -- the power method with its sums in a fixed order (grid partials, a one-block finish), and the
+// sequence of a call.  A level's bound goes to the host once per call (omega = 4 / (3 rho) and the smoother's bound are
+// kernel arguments); the coarsest inverse stays the host's Cholesky.
+struct AmgRenewal
+{
+  amg_renew::RenewPlan plan;
+  int *inc_off = nullptr, *inc_cell = nullptr, *inc_loc = nullptr; // level 0: the rows' incidences
+  int cap0 = 1;
+  double* Gc = nullptr; // [cells][8][6]: the operator's tensor in the order the row routine reads it, refilled per call
+  struct Level
+  {
+    int* agg = nullptr;
+    double* t = nullptr;
+    DevCsr AP;
+    int* rperm = nullptr;
+    double* x0 = nullptr;
+    int wP = 2, wAP = 2, wA = 2, capAP = 1, capA = 1; // lanes per row and longest row of the three kernels
+  };
+  std::vector<Level> lv;
+  double* partials = nullptr; // [3][blocks of the largest level's power step]
+  double* scal = nullptr;     // lambda, norm, rows without a positive diagonal, stopped
+  double* h_scal = nullptr;   // pinned copy
+  AmgRenewal() = default;
+  AmgRenewal(const AmgRenewal&) = delete;
+  ~AmgRenewal()
+  {
+    for (void* p : {(void*)inc_off, (void*)inc_cell, (void*)inc_loc, (void*)Gc, (void*)partials, (void*)scal})
+      (void)hipFree(p);
+    if (h_scal)
+      (void)hipHostFree(h_scal);
+    for (Level& l : lv)
+    {
+      (void)hipFree(l.agg);
+      (void)hipFree(l.t);
+      (void)hipFree(l.rperm);
+      (void)hipFree(l.x0);
+      free_csr(l.AP);
+    }
+  }
+};
+
+static int nullspace_inverse(pmg_amg amg, std::vector<double>& inv);
+
+namespace
+{
+// W lanes (a power of two <= 32) share a row, blockDim.x / W rows per block, one LDS copy of `cap` doubles per row
+struct RowLaunch
+{
+  int W = 2, cap = 1;
+  unsigned blocks = 0, threads = 0;
+  size_t lds = 0;
+};
+RowLaunch row_launch(int n, int W, int cap)
+{
+  RowLaunch r;
+  r.W = W;
+  r.cap = std::max(cap, 1);
+  const int groups =
+      (int)std::max<size_t>(1, std::min<size_t>(256 / W, amg_renew::ROW_COPY_BYTES / (sizeof(double) * r.cap)));
+  r.threads = (unsigned)(W * groups);
+  r.blocks = (unsigned)((n + groups - 1) / groups);
+  r.lds = sizeof(double) * (size_t)r.cap * groups;
+  return r;
+}
+
+__global__ void __launch_bounds__(256)
+    renew_level0_kernel(int n, int W, int cap, const int* __restrict__ rp, const int* __restrict__ ci,
+                        double* __restrict__ vals, double* __restrict__ dinv, const int* __restrict__ inc_off,
+                        const int* __restrict__ inc_cell, const int* __restrict__ inc_loc,
+                        const int32_t* __restrict__ dofmap, const double* __restrict__ Gc,
+                        const double* __restrict__ kappa, const int8_t* __restrict__ bc, const double* __restrict__ react)
+{
+  extern __shared__ double renew_rows[];
+  const int groups = blockDim.x / W, g = threadIdx.x / W, sub = threadIdx.x - g * W;
+  const int row = blockIdx.x * groups + g;
+  if (row >= n)
+    return;
+  double* acc = renew_rows + (size_t)g * cap;
+  amg_renew::level0_row(row, sub, W, rp, ci, inc_off, inc_cell, inc_loc, dofmap, Gc, kappa, bc, react, acc);
+  amg_renew::store_row(row, sub, W, rp, ci, acc, vals, dinv);
+}
+
+// C = A B on the pattern of C; dinv (optional): the inverse diagonal of C
+__global__ void __launch_bounds__(256)
+    renew_product_kernel(int n, int W, int cap, const int* __restrict__ Arp, const int* __restrict__ Aci,
+                         const double* __restrict__ Av, const int* __restrict__ Brp, const int* __restrict__ Bci,
+                         const double* __restrict__ Bv, const int* __restrict__ Crp, const int* __restrict__ Cci,
+                         double* __restrict__ Cv, double* __restrict__ dinv)
+{
+  extern __shared__ double renew_rows[];
+  const int groups = blockDim.x / W, g = threadIdx.x / W, sub = threadIdx.x - g * W;
+  const int row = blockIdx.x * groups + g;
+  if (row >= n)
+    return;
+  double* acc = renew_rows + (size_t)g * cap;
+  amg_renew::product_row(row, sub, W, Arp, Aci, Av, Brp, Bci, Bv, Crp, Cci, acc);
+  amg_renew::store_row(row, sub, W, Crp, Cci, acc, Cv, dinv);
+}
+
+__global__ void __launch_bounds__(256)
+    renew_prolongator_kernel(int n, int W, const int* __restrict__ Arp, const int* __restrict__ Aci,
+                             const double* __restrict__ Av, const int* __restrict__ agg, const double* __restrict__ t,
+                             double omega, const int* __restrict__ Prp, const int* __restrict__ Pci,
+                             double* __restrict__ Pv)
+{
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int row = (int)(gid / W), sub = (int)(gid - (long long)row * W);
+  if (row < n)
+    amg_renew::prolongator_row(row, sub, W, Arp, Aci, Av, agg, t, omega, Prp, Pci, Pv);
+}
+
+// R = P^T: its values through the planned permutation
+__global__ void __launch_bounds__(256)
+    renew_gather_kernel(long long nnz, const int* __restrict__ from, const double* __restrict__ Pv, double* __restrict__ Rv)
+{
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < nnz)
+    Rv[k] = Pv[from[k]];
+}
+
+// One step of the power method on D^-1 A: y = D^-1 A x and the block's partials of y . y, x . x and of the number of
+// rows without a positive diagonal (dinv = 0), each a tree over the block's 256 slots: a fixed order.
+template <int TPR>
+__global__ void __launch_bounds__(256)
+    renew_power_kernel(int n, const int* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v,
+                       const double* __restrict__ dinv, const double* __restrict__ x, double* __restrict__ y,
+                       double* __restrict__ partials)
+{
+  __shared__ double red[3][256];
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int row = gid / TPR, sub = gid % TPR;
+  double acc = row < n ? amg_renew::row_dot(row, sub, TPR, rp, ci, v, x) : 0.0;
+#pragma unroll
+  for (int off = TPR / 2; off > 0; off >>= 1)
+    acc += __shfl_down(acc, off, TPR);
+  double yy = 0.0, xx = 0.0, bad = 0.0;
+  if (row < n && sub == 0)
+  {
+    const double di = dinv[row], yi = acc * di, xi = x[row];
+    y[row] = yi;
+    yy = yi * yi;
+    xx = xi * xi;
+    bad = di > 0.0 ? 0.0 : 1.0;
+  }
+  red[0][threadIdx.x] = yy;
+  red[1][threadIdx.x] = xx;
+  red[2][threadIdx.x] = bad;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1)
+  {
+    if ((int)threadIdx.x < off)
+      for (int c = 0; c < 3; ++c)
+        red[c][threadIdx.x] += red[c][threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3)
+    partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0];
+}
+
+// ... the finish, one block: scal = {lambda = |y| / |x|, |y|, bad rows, stopped}.  Where |y| is not positive the
+// iteration stops with lambda = 1 (lambda_max_jacobi's answer) and the later steps leave scal alone.
+__global__ void __launch_bounds__(256)
+    renew_power_finish_kernel(int nb, const double* __restrict__ partials, double* __restrict__ scal)
+{
+  __shared__ double red[3][256];
+  for (int c = 0; c < 3; ++c)
+  {
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 256)
+      a += partials[(size_t)c * nb + b];
+    red[c][threadIdx.x] = a;
+  }
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1)
+  {
+    if ((int)threadIdx.x < off)
+      for (int c = 0; c < 3; ++c)
+        red[c][threadIdx.x] += red[c][threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && scal[3] == 0.0)
+  {
+    const double nrm = sqrt(red[0][0]);
+    scal[2] = red[2][0];
+    if (!(nrm > 0.0))
+    {
+      scal[0] = 1.0;
+      scal[3] = 1.0;
+    }
+    else
+    {
+      scal[0] = nrm / sqrt(red[1][0]);
+      scal[1] = nrm;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256)
+    renew_power_scale_kernel(int n, const double* __restrict__ y, const double* __restrict__ scal, double* __restrict__ x)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && scal[3] == 0.0)
+    x[i] = y[i] / scal[1];
+}
+
+unsigned power_blocks(const DevCsr& A) { return (unsigned)(((long long)A.n * A.tpr + 255) / 256); }
+
+// 20 power steps on D^-1 A_l from the level's start vector, in the level's own work vectors
+int renew_power_bound(pmg_amg amg, int l, double* lam, hipStream_t s)
+{
+  AmgRenewal& R = *amg->renewal;
+  AmgLevel& lv = amg->levels[l];
+  const DevCsr& A = lv.A;
+  *lam = 1.0;
+  if (A.n == 0)
+    return PMG_OK;
+  double *x = lv.z, *y = lv.q;
+  const unsigned nb = power_blocks(A), nv = (unsigned)((A.n + 255) / 256);
+  PMG_HIP(hipMemcpyAsync(x, R.lv[l].x0, sizeof(double) * A.n, hipMemcpyDeviceToDevice, s));
+  PMG_HIP(hipMemsetAsync(R.scal, 0, sizeof(double) * 4, s));
+  for (int it = 0; it < 20; ++it)
+  {
+    switch (A.tpr)
+    {
+    case 2: renew_power_kernel<2><<<nb, 256, 0, s>>>(A.n, A.rp, A.ci, A.v, lv.dinv, x, y, R.partials); break;
+    case 4: renew_power_kernel<4><<<nb, 256, 0, s>>>(A.n, A.rp, A.ci, A.v, lv.dinv, x, y, R.partials); break;
+    case 8: renew_power_kernel<8><<<nb, 256, 0, s>>>(A.n, A.rp, A.ci, A.v, lv.dinv, x, y, R.partials); break;
+    case 16: renew_power_kernel<16><<<nb, 256, 0, s>>>(A.n, A.rp, A.ci, A.v, lv.dinv, x, y, R.partials); break;
+    default: renew_power_kernel<32><<<nb, 256, 0, s>>>(A.n, A.rp, A.ci, A.v, lv.dinv, x, y, R.partials); break;
+    }
+    renew_power_finish_kernel<<<1, 256, 0, s>>>((int)nb, R.partials, R.scal);
+    renew_power_scale_kernel<<<nv, 256, 0, s>>>(A.n, y, R.scal, x);
+  }
+  PMG_HIP(hipGetLastError());
+  PMG_HIP(hipMemcpyAsync(R.h_scal, R.scal, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+  PMG_HIP(hipStreamSynchronize(s));
+  if (R.h_scal[2] > 0.0)
+    return fail(PMG_ERR_NUMERIC, "pmg_amg_update_values: non-positive diagonal entry on level %d", l);
+  *lam = R.h_scal[0];
+  return PMG_OK;
+}
+
+// the values of hA and hP as the device has them (their patterns are the device's)
+int refresh_host(pmg_amg amg)
+{
+  for (size_t l = 0; l < amg->hA.size(); ++l)
+    if (amg->hA[l].nnz() > 0)
+      PMG_HIP(hipMemcpy(amg->hA[l].v.data(), amg->levels[l].A.v, sizeof(double) * amg->hA[l].v.size(),
+                        hipMemcpyDeviceToHost));
+  for (size_t l = 0; l < amg->hP.size(); ++l)
+    if (amg->hP[l].nnz() > 0)
+      PMG_HIP(hipMemcpy(amg->hP[l].v.data(), amg->levels[l].P.v, sizeof(double) * amg->hP[l].v.size(),
+                        hipMemcpyDeviceToHost));
+  amg->host_stale = false;
+  return PMG_OK;
+}
+
+// a device matrix on a new (larger) pattern: the old arrays are freed
+int replace_csr(DevCsr& d, const HostCsr& pattern)
+{
+  free_csr(d);
+  return upload_csr(d, pattern);
+}
+
+// The first call: the plan (host), its device arrays, and the hierarchy's matrices moved to the structural patterns
+// where those are larger than the created ones.
+int renewal_plan(pmg_amg amg)
+{
+  pmg_laplacian op = amg->op;
+  const LaplacianInputs in = laplacian_inputs(op);
+  std::vector<int32_t> dofmap((size_t)in.ncells * 8), cells;
+  if (in.ncells > 0)
+    PMG_HIP(hipMemcpy(dofmap.data(), in.dofmap, sizeof(int32_t) * dofmap.size(), hipMemcpyDeviceToHost));
+  for (int32_t c : *laplacian_patches(op).pcell_h)
+    if (c >= 0)
+      cells.push_back(c);
+  std::unique_ptr<AmgRenewal> R(new AmgRenewal);
+  PMG_TRY(accepted(amg_renew::plan_renewal(amg->hA, dofmap, cells, R->plan)));
+  const amg_renew::RenewPlan& plan = R->plan;
+  const int L = (int)plan.A.size();
+  PMG_REQUIRE(L == (int)amg->levels.size(), "pmg_amg_update_values: internal: the plan has %d levels", L);
+  PMG_TRY(to_device(&R->inc_off, plan.inc_off));
+  PMG_TRY(to_device(&R->inc_cell, plan.inc_cell));
+  PMG_TRY(to_device(&R->inc_loc, plan.inc_loc));
+  R->cap0 = longest_row(plan.A[0]);
+  PMG_HIP(hipMalloc(&R->Gc, sizeof(double) * 48 * std::max<size_t>((size_t)in.ncells, 1)));
+  R->lv.resize(L);
+  for (int l = 0; l < L; ++l)
+  {
+    AmgRenewal::Level& rl = R->lv[l];
+    PMG_TRY(to_device(&rl.x0, plan.x0[l]));
+    if (l + 1 == L)
+      break;
+    const amg_renew::RenewLevel& pl = plan.lv[l];
+    PMG_TRY(to_device(&rl.agg, pl.agg));
+    PMG_TRY(to_device(&rl.t, pl.t));
+    PMG_TRY(to_device(&rl.rperm, pl.rperm));
+    PMG_TRY(upload_csr(rl.AP, pl.AP));
+    rl.wP = amg_renew::lanes_for(pl.P);
+    rl.wAP = amg_renew::lanes_for(pl.P); // lanes take the entries of a row of the right factor
+    rl.wA = amg_renew::lanes_for(pl.AP);
+    rl.capAP = longest_row(pl.AP);
+    rl.capA = longest_row(plan.A[l + 1]);
+  }
+  PMG_HIP(hipMalloc(&R->scal, sizeof(double) * 4));
+  PMG_HIP(hipHostMalloc(&R->h_scal, sizeof(double) * 4, hipHostMallocDefault));
+  // the hierarchy on the structural patterns (a level whose pattern the creation already had keeps its arrays)
+  for (int l = 0; l < L; ++l)
+  {
+    AmgLevel& lv = amg->levels[l];
+    if (plan.A[l].nnz() != amg->hA[l].nnz())
+      PMG_TRY(replace_csr(lv.A, plan.A[l]));
+    amg->hA[l] = plan.A[l];
+    lv.nnz = plan.A[l].nnz();
+    if (l + 1 < L)
+    {
+      if (plan.lv[l].P.nnz() != amg->hP[l].nnz())
+      {
+        PMG_TRY(replace_csr(lv.P, plan.lv[l].P));
+        PMG_TRY(replace_csr(lv.R, plan.lv[l].R));
+      }
+      amg->hP[l] = plan.lv[l].P;
+    }
+  }
+  amg->host_stale = true;
+  unsigned nb = 1;
+  for (const AmgLevel& lv : amg->levels)
+    nb = std::max(nb, power_blocks(lv.A));
+  PMG_HIP(hipMalloc(&R->partials, sizeof(double) * 3 * nb));
+  amg->renewal = R.release();
+  return PMG_OK;
+}
+
+// every call: the values, level by level
+int renewal_values(pmg_amg amg, hipStream_t s)
+{
+  AmgRenewal& R = *amg->renewal;
+  const amg_renew::RenewPlan& plan = R.plan;
+  pmg_laplacian op = amg->op;
+  const int L = (int)amg->levels.size();
+  StageTimer tm;
+  tm.tag = "update";
+  auto lap = [&](const char* what) {
+    if (tm.on)
+      (void)hipStreamSynchronize(s);
+    tm.lap(what);
+  };
+  {
+    AmgLevel& l0 = amg->levels[0];
+    PMG_TRY(laplacian_geometry_ascending(op, R.Gc, s));
+    lap("tensor in point order");
+    if (l0.n > 0)
+    {
+      const RowLaunch k = row_launch(l0.n, 8, R.cap0);
+      renew_level0_kernel<<<k.blocks, k.threads, k.lds, s>>>(l0.n, k.W, k.cap, l0.A.rp, l0.A.ci, l0.A.v, l0.dinv,
+                                                             R.inc_off, R.inc_cell, R.inc_loc, op->dofmap, R.Gc,
+                                                             op->kappa, op->bc, laplacian_reaction(op));
+      PMG_HIP(hipGetLastError());
+    }
+    lap("level-0 values");
+  }
+  for (int l = 0; l < L; ++l)
+  {
+    AmgLevel& lv = amg->levels[l];
+    double lam = 1.0;
+    PMG_TRY(renew_power_bound(amg, l, &lam, s));
+    lv.lmax = amg->hlmax[l] = 1.05 * lam;
+    lap("power method");
+    if (l + 1 == L)
+      break;
+    AmgLevel& lc = amg->levels[l + 1];
+    const AmgRenewal::Level& rl = R.lv[l];
+    const double omega = 4.0 / (3.0 * lv.lmax);
+    if (lv.n > 0)
+    {
+      const unsigned blocks = (unsigned)(((long long)lv.n * rl.wP + 255) / 256);
+      renew_prolongator_kernel<<<blocks, 256, 0, s>>>(lv.n, rl.wP, lv.A.rp, lv.A.ci, lv.A.v, rl.agg, rl.t, omega,
+                                                      lv.P.rp, lv.P.ci, lv.P.v);
+      const long long nnz = plan.lv[l].P.nnz();
+      if (nnz > 0)
+        renew_gather_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, rl.rperm, lv.P.v, lv.R.v);
+      PMG_HIP(hipGetLastError());
+      lap("smoothed prolongator, transpose");
+      const RowLaunch k = row_launch(lv.n, rl.wAP, rl.capAP);
+      renew_product_kernel<<<k.blocks, k.threads, k.lds, s>>>(lv.n, k.W, k.cap, lv.A.rp, lv.A.ci, lv.A.v, lv.P.rp,
+                                                              lv.P.ci, lv.P.v, rl.AP.rp, rl.AP.ci, rl.AP.v, nullptr);
+      PMG_HIP(hipGetLastError());
+      lap("A P");
+    }
+    if (lc.n > 0)
+    {
+      const RowLaunch k = row_launch(lc.n, rl.wA, rl.capA);
+      renew_product_kernel<<<k.blocks, k.threads, k.lds, s>>>(lc.n, k.W, k.cap, lv.R.rp, lv.R.ci, lv.R.v, rl.AP.rp,
+                                                              rl.AP.ci, rl.AP.v, lc.A.rp, lc.A.ci, lc.A.v, lc.dinv);
+      PMG_HIP(hipGetLastError());
+      lap("R (A P)");
+    }
+  }
+  // the coarsest inverse(s): the host's Cholesky of the downloaded A_c, uploaded into the allocations that exist
+  PMG_HIP(hipStreamSynchronize(s));
+  amg->host_stale = true;
+  HostCsr& Ac = amg->hA.back();
+  if (Ac.n <= 4096)
+  {
+    if (amg->dense_inv_null)
+      PMG_TRY(refresh_host(amg)); // the restricted ones go through every renewed transfer
+    else if (Ac.nnz() > 0)
+      PMG_HIP(hipMemcpy(Ac.v.data(), amg->levels.back().A.v, sizeof(double) * Ac.v.size(), hipMemcpyDeviceToHost));
+    std::vector<double> inv;
+    amg->plain_valid = dense_spd_inverse(Ac, inv);
+    if (amg->plain_valid)
+    {
+      amg->n_coarsest = Ac.n;
+      if (!amg->dense_inv_plain)
+        PMG_TRY(to_device(&amg->dense_inv_plain, inv));
+      else if (!inv.empty())
+        PMG_HIP(hipMemcpy(amg->dense_inv_plain, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice));
+    }
+    if (amg->dense_inv_null)
+    {
+      PMG_TRY(nullspace_inverse(amg, inv));
+      if (!inv.empty())
+        PMG_HIP(hipMemcpy(amg->dense_inv_null, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice));
+    }
+    amg->dense_inv = amg->nullspace == PMG_NULLSPACE_CONSTANT ? amg->dense_inv_null
+                     : amg->plain_valid                       ? amg->dense_inv_plain
+                                                              : nullptr;
+  }
+  lap("coarsest inverse");
+  return PMG_OK;
+}
+} // namespace
+
+extern "C" int pmg_amg_update_values(pmg_amg amg, pmg_stream stream)
+{
+  PMG_REQUIRE(amg, "pmg_amg_update_values: NULL argument");
+  PMG_REQUIRE(!amg->replicated, "pmg_amg_update_values: the replicated and distributed hierarchies are not renewed in "
+                                "place; the single-domain form (pmg_amg_create) only");
+  PMG_REQUIRE(!amg->layout->multi_rank() && amg->layout->num_ghosts == 0,
+              "pmg_amg_update_values: the layout has several ranks or ghosts; the single-domain form only");
+  PMG_REQUIRE(amg->op->batch_patches == 0, "pmg_amg_update_values: the operator is in batched-geometry mode, its tensor "
+                                           "G is not resident (pmg_laplacian_set_geometry_batch(op, 0) keeps it)");
+  hipStream_t s = S(stream);
+  PMG_TRY(not_capturing(s, "pmg_amg_update_values: the stream is being captured; the call synchronises it"));
+  PMG_HIP(hipStreamSynchronize(s));
+  if (!amg->renewal)
+    PMG_TRY(renewal_plan(amg));
+  amg->unusable = true; // until every level is through
+  PMG_TRY(renewal_values(amg, s));
+  amg->unusable = false;
+  ++amg->updates;
+  return PMG_OK;
+}
+
+extern "C" long long pmg_amg_updates(pmg_amg amg) { return amg ? amg->updates : -1; }
+
 extern "C" int pmg_amg_destroy(pmg_amg amg)
 {
   if (!amg)
     return PMG_OK;
+  delete amg->renewal;
   for (AmgLevel& lv : amg->levels)
   {
     free_csr(lv.A);
@@ -1064,6 +1542,8 @@ extern "C" int pmg_amg_cycle(pmg_amg amg, double* x, const double* b, pmg_stream
 {
   PMG_REQUIRE(amg && x && b && x != b, "pmg_amg_cycle: bad argument");
   PMG_REQUIRE(!amg->replicated, "pmg_amg_cycle: a replicated hierarchy works on gathered vectors; use pmg_amg_solve");
+  PMG_REQUIRE(!amg->unusable, "pmg_amg_cycle: the last pmg_amg_update_values of this hierarchy did not finish; it is "
+                              "unusable until an update succeeds");
   if (amg->nullspace == PMG_NULLSPACE_CONSTANT)
     PMG_TRY(laplacian_require_singular(amg->op, "pmg_amg_cycle", S(stream)));
   PMG_TRY(amg_cycle(amg, csr_front(&amg->levels[0], S(stream)), 0, x, b, S(stream)));
@@ -1103,6 +1583,8 @@ extern "C" int pmg_amg_set_nullspace(pmg_amg amg, int mode)
     PMG_TRY(laplacian_require_singular(amg->op, "pmg_amg_set_nullspace", nullptr));
     if (!amg->dense_inv_null && !amg->hA.empty() && amg->hA.back().n <= 4096)
     {
+      if (amg->host_stale)
+        PMG_TRY(refresh_host(amg));
       std::vector<double> inv;
       PMG_TRY(nullspace_inverse(amg, inv));
       PMG_TRY(to_device(&amg->dense_inv_null, inv));
@@ -1111,7 +1593,7 @@ extern "C" int pmg_amg_set_nullspace(pmg_amg amg, int mode)
     amg->dense_inv = amg->dense_inv_null; // (nullptr: a coarsest level too large to invert keeps smoothing)
   }
   else
-    amg->dense_inv = amg->dense_inv_plain;
+    amg->dense_inv = amg->plain_valid ? amg->dense_inv_plain : nullptr;
   amg->nullspace = mode;
   PMG_TRY(pmg_cg_set_nullspace(amg->cg, mode)); // the Krylov mode's work object
   return PMG_OK;
@@ -1138,6 +1620,8 @@ extern "C" int pmg_amg_export(pmg_amg amg, int level, int which, long long* rows
                               int32_t* rowptr, int32_t* colidx, double* values)
 {
   PMG_REQUIRE(amg && level >= 0 && (which == 0 || which == 1), "pmg_amg_export: bad argument");
+  if (amg->host_stale) // after pmg_amg_update_values: the device's current values, on the structural patterns
+    PMG_TRY(refresh_host(amg));
   const std::vector<HostCsr>& src = which == 0 ? amg->hA : amg->hP;
   PMG_REQUIRE(level < (int)src.size(), "pmg_amg_export: no such level");
   const HostCsr& M = src[level];

@@ -37,12 +37,13 @@ struct StageTimer
 {
   bool on = std::getenv("PMG_AMG_TIMING") != nullptr;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  const char* tag = "set-up"; // ("update": the laps of pmg_amg_update_values)
   void lap(const char* what)
   {
     if (!on)
       return;
     const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[pmg_amg set-up] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+    std::fprintf(stderr, "[pmg_amg %s] %-28s %8.1f ms\n", tag, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
     t0 = t1;
   }
 };

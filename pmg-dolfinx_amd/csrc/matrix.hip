@@ -18,6 +18,7 @@
 // follows src/csr.hpp:252-270: scatter begin, the diag part of all rows, scatter end, the off-diag part of the boundary
 // rows (matrix_range_product_kernel), with the routing of the matrix-free operator's apply_impl.  The host pattern and
 // the split are in matrix_pattern.hpp.
+#include "amg_renew.hpp"
 #include "laplacian.hpp"
 #include "matrix_pattern.hpp"
 
@@ -69,20 +70,7 @@ int to_device(T** dst, const T* src, size_t count)
   return PMG_OK;
 }
 
-// first position k in the sorted cols[0 .. len) with cols[k] >= col (the pattern holds col: that is its position)
-__device__ __forceinline__ int row_position(const int32_t* __restrict__ cols, int len, int32_t col)
-{
-  int lo = 0, hi = len;
-  while (lo < hi)
-  {
-    const int mid = (lo + hi) >> 1;
-    if (cols[mid] < col)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
+// (row_position, the search of a column in a sorted row: amg_renew.hpp, shared with the AMG's renewal)
 
 // Values of the rows [0, n) on the existing pattern, and the inverse diagonal.
 // W lanes (a power of two <= 64, so a group never spans two wavefronts) share a row; blockDim.x / W rows per block.
