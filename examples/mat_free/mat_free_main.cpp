@@ -25,6 +25,10 @@
 // --lift restates the right-hand side the reference's driver has commented out (:252-255): u = the assembled load of
 // f = 0 (:133,143: the interpolation of f is commented out as well), lifted with the boundary value 1.3 (:165) and
 // set_bc -- pmg_laplacian_assemble_rhs, _apply_lifting, _set_bc on the one operator -- instead of u = 1.
+// --cell-form prints, after the apply y = A u, the sum over the cells of the per-cell bilinear form e_c(u, u)
+// (pmg_laplacian_cell_form with kappa, marked dofs read as zero; not in the reference) beside u_m . y, u_m = u with its
+// marked entries zeroed, and their relative difference: the two are the same number, computed by two kernels.  It
+// combines with --kappa-field, --kappa-tensor and --curved (the reaction and Robin terms are not part of the form).
 // Single rank.
 #include "../common/box_mesh.hpp"
 #include "../common/rotating_tensor.hpp"
@@ -45,7 +49,7 @@ int main(int argc, char** argv)
 {
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
-  bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false;
+  bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false, cell_form = false;
   bool neumann = false; // --neumann: no Dirichlet marker (the singular, pure Neumann operator)
   double reaction = 0.0; // S of --reaction; 0 = no term
   double robin = 0.0;    // A of --robin; 0 = no term
@@ -78,12 +82,14 @@ int main(int argc, char** argv)
       curved = std::atoi(next());
     else if (!std::strcmp(argv[i], "--lift"))
       lift = true;
+    else if (!std::strcmp(argv[i], "--cell-form"))
+      cell_form = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
       batch_size = std::strtoull(next(), nullptr, 10);
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift] [--neumann]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift] [--neumann] [--cell-form]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -202,6 +208,25 @@ int main(int argc, char** argv)
                 V.ndofs / per * 1e-9, bytes / per * 1e-9);
     std::printf("Norm of u = %.15e\n", acc::norm(u));
     std::printf("Norm of y = %.15e\n", acc::norm(y));
+
+    if (cell_form)
+    {
+      // sum_c e_c(u, u) with kappa and the marked dofs read as zero = u_m . (A u_m) = u_m . y (marked columns of A are
+      // masked, and u_m is zero on the marked rows)
+      device_array<double> e(mesh.ncells());
+      op.cell_form(u, u, e.span(), true, true);
+      hip_check(hipDeviceSynchronize(), "sync");
+      const std::vector<double> eh = e.to_host(), uh = u.data_copy(), yh = y.data_copy();
+      double energy = 0.0, dot = 0.0;
+      for (double v : eh)
+        energy += v;
+      for (std::size_t d = 0; d < (std::size_t)V.ndofs; ++d)
+        if (!V.bc_marker[d])
+          dot += uh[d] * yh[d];
+      std::printf("Cell form: sum_c e_c(u, u) = %.15e\n", energy);
+      std::printf("Cell form: u_m . y = %.15e\n", dot);
+      std::printf("Cell form: relative difference = %.3e\n", std::fabs(energy - dot) / std::fabs(dot));
+    }
 
     if (mat_comp)
     {

@@ -576,6 +576,35 @@ int pmg_laplacian_lift_cell_count(pmg_laplacian op);
 int pmg_laplacian_set_robin(pmg_laplacian op, int32_t nfacets, const int32_t* facet_cells,
                             const int8_t* facet_local, const double* alpha, pmg_stream stream);
 int pmg_laplacian_has_robin(pmg_laplacian op);
+/* ---- per-cell bilinear form: cell energies and the gradient with respect to kappa (not in the reference) ----
+ * The diffusion term's bilinear form, cell by cell:
+ *     out_cells[c] = sum over the quadrature points q of cell c of  (grad_ref v)_q^T G_q (grad_ref u)_q   [ x kappa[c] ]
+ * with G_q = adj(J) K_c adj(J)^T w_q / |det J| kq[dof(c, q)], the tensor the apply uses (the nodal field kq and the
+ * per-cell tensor K_c where they are set, curved cells included), WITHOUT kappa unless PMG_CELL_FORM_KAPPA is given;
+ * with it, kappa[c] is read at call time, as the apply reads it.  The sum over the listed cells of the value with both
+ * flags is v_m . (A u_m) of the operator (u_m, v_m: the vectors with their marked entries zeroed); the value with
+ * PMG_CELL_FORM_CONSTRAINED alone is v^T (dA/dkappa_c) u of the boundary-treated A, so that for a functional J(x) of
+ * the solution of A x = b the adjoint gradient is dJ/dkappa_c = -out_cells[c] with u = x and v = lambda = A^-1 dJ/dx;
+ * u == v gives the energy of a function, cell by cell.
+ *
+ * `u` and `v` are device arrays of size_local + num_ghosts doubles in the operator's dof numbering; they may be the
+ * same array.  `out_cells` is a device array of `ncells` doubles, one per cell of the operator's dofmap in the caller's
+ * cell numbering: EVERY cell gets a value, ghost cells and cells in neither cell list included.
+ * NO EXCHANGE: unlike pmg_laplacian_apply, the call does not scatter: the ghost entries of u and v must be current
+ * (pmg_scatter_fwd_begin / _end) -- they are read as they are.  The call is not collective.
+ * Only the diffusion form is computed.  The reaction and Robin terms (pmg_laplacian_set_reaction,
+ * pmg_laplacian_set_robin) are not part of it: setting them does not change a bit of the result, and their own
+ * sensitivities (the per-cell mass and the per-facet mass forms) are not provided.
+ * The geometry is formed in place from the mesh, so the call works, with the same code, whatever the tensor's layout,
+ * in batched-geometry mode, in the affine mode, with the chain form and with either recompute switch.  It is ONE kernel
+ * launch on `stream` without host synchronisation or allocation: it can be captured.  A cell's sum is taken in a fixed
+ * order without atomics: two calls on the same data give the same bytes.
+ * Refused with PMG_ERR_INVALID and out_cells untouched: a NULL op, u, v or out_cells; a flag bit other than the two
+ * below; out_cells overlapping u or v. */
+#define PMG_CELL_FORM_KAPPA        1  /* multiply by kappa[cell], read at call time like the apply */
+#define PMG_CELL_FORM_CONSTRAINED  2  /* marked dofs of u and v read as zero: v^T (dA/dkappa_c) u of the BC-treated A */
+int pmg_laplacian_cell_form(pmg_laplacian op, const double* u, const double* v, double* out_cells,
+                            int flags, pmg_stream stream);
 int pmg_laplacian_degree(pmg_laplacian op);
 /* Geometry mode of the apply.  0 (default): the reference's data structure, the
  * stored tensor G[cell][q][6] is streamed (48 bytes per quadrature point).

@@ -805,6 +805,22 @@ public:
       check(pmg_laplacian_set_robin(_op, 0, nullptr, nullptr, nullptr, nullptr));
   }
   bool has_robin() const { return _op && pmg_laplacian_has_robin(_op) == 1; }
+  /// The diffusion term's bilinear form cell by cell (pmg_laplacian_cell_form; not in the reference):
+  /// out[c] = sum_q (grad_ref v)_q^T G_q (grad_ref u)_q, times kappa[c] with `kappa`; with `constrained` the marked
+  /// dofs of u and v read as zero.  out_device is device memory of one value per cell, ghost cells included.  The
+  /// ghosts of u and v must be current: unlike operator(), the call does not exchange.  u and v may be one vector.
+  /// The reaction and Robin terms are not part of the form.  One launch, no atomics: the same bytes every call.
+  template <typename Vector>
+  void cell_form(const Vector& u, const Vector& v, std::span<T> out_device, bool kappa = true,
+                 bool constrained = false)
+  {
+    require_same_map(u, v);
+    if (out_device.size() != _kappa.size())
+      throw std::runtime_error("MatFreeLaplacian::cell_form: the output holds one value per cell");
+    const int flags = (kappa ? PMG_CELL_FORM_KAPPA : 0) | (constrained ? PMG_CELL_FORM_CONSTRAINED : 0);
+    check(pmg_laplacian_cell_form(handle(u.map()), u.array().data(), v.array().data(), out_device.data(), flags,
+                                  nullptr));
+  }
   /// Recomputed tensor (pmg_laplacian_set_tensor_recompute): -1 automatic, 0 always stream, 1 recompute (an error on
   /// an operator that cannot).  The handle must exist.
   void set_tensor_recompute(int mode)

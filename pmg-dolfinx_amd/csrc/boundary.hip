@@ -17,16 +17,6 @@ using namespace pmg;
 
 namespace
 {
-// One thread per node.  Degree >= 3: one cell per workgroup (64 .. 729 nodes, rounded up to whole wavefronts);
-// degree <= 2: several cells, so that a full workgroup has at least 64 busy lanes.
-template <int ND>
-struct LiftShape
-{
-  static constexpr int N = ND * ND * ND;
-  static constexpr int CPW = N >= 64 ? 1 : (64 + N - 1) / N; // 8 cells at degree 1, 3 at degree 2
-  static constexpr int THREADS = ((CPW * N + 63) / 64) * 64;
-};
-
 // b[dof] -= alpha * (A_cell u_cell)[t] for the unmarked owned rows of the listed cells, with
 // u_cell[t] = marked(dof) ? g[dof] - x0[dof] : 0 -- the element kernel of src/laplacian.hpp:143-278 without its row and
 // column treatment, G_q computed in place (src/laplacian.hpp:72-111, as point_tensor: w_q / detJ, times the nodal
@@ -189,15 +179,6 @@ __global__ void robin_kernel(long long npoints, int nd, const int32_t* __restric
   double wdS;
   if (facet_point(gid, nd, fcells, flocal, dofmap, bc, total, xgeom, geom_dofmap, ng, dphi, w1, dof, wdS))
     atomicAdd(&d[dof], wdS * alpha[gid]);
-}
-
-// do p[0, np) and q[0, nq) share memory?
-bool overlaps(const double* p, size_t np, const double* q, size_t nq)
-{
-  if (!p || !q)
-    return false;
-  const uintptr_t a = (uintptr_t)p, c = (uintptr_t)q;
-  return a < c + nq * sizeof(double) && c < a + np * sizeof(double);
 }
 
 // Are the (host) facet lists those of cells the operator holds, and of local facets 0..5?

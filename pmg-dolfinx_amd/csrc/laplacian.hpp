@@ -370,4 +370,24 @@ __device__ __forceinline__ void point_tensor(const double K[3][3], double detJ, 
   else
     metric(K, s, g);
 }
+
+// ---- the cell-local kernels that form G_q in place (boundary.hip: lifting; cell_form.hip: the bilinear form) ----
+// One thread per node.  Degree >= 3: one cell per workgroup (64 .. 729 nodes, rounded up to whole wavefronts);
+// degree <= 2: several cells, so that a full workgroup has at least 64 busy lanes.
+template <int ND>
+struct LiftShape
+{
+  static constexpr int N = ND * ND * ND;
+  static constexpr int CPW = N >= 64 ? 1 : (64 + N - 1) / N; // 8 cells at degree 1, 3 at degree 2
+  static constexpr int THREADS = ((CPW * N + 63) / 64) * 64;
+};
+
+// do p[0, np) and q[0, nq) share memory?
+inline bool overlaps(const double* p, size_t np, const double* q, size_t nq)
+{
+  if (!p || !q)
+    return false;
+  const uintptr_t a = (uintptr_t)p, c = (uintptr_t)q;
+  return a < c + nq * sizeof(double) && c < a + np * sizeof(double);
+}
 } // namespace pmg

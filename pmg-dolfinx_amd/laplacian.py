@@ -327,6 +327,41 @@ class MatFreeLaplacian:
     def has_robin(self) -> bool:
         return bool(call("pmg_laplacian_has_robin", self._handle))
 
+    CELL_FORM_KAPPA = 1  # PMG_CELL_FORM_KAPPA
+    CELL_FORM_CONSTRAINED = 2  # PMG_CELL_FORM_CONSTRAINED
+
+    def cell_form(self, u, v, out=None, kappa: bool = True, constrained: bool = False):
+        """The diffusion term's bilinear form cell by cell (``pmg_laplacian_cell_form``):
+        e_c(u, v) = sum_q (grad_ref v)_q^T G_q (grad_ref u)_q, times ``kappa[c]`` (read now) with ``kappa=True``; with
+        ``constrained=True`` the marked dofs of ``u`` and ``v`` read as zero.  ``u`` and ``v`` are ``Vector``s or
+        contiguous float64 device tensors of the layout's total size and may be the same object; their ghost entries
+        must be current: the call does not exchange.  Returns ``out``, a float64 device tensor ``[ncells]`` (made
+        here when ``None``) with one value per cell of the dofmap, ghost cells included.  One launch; capturable.
+        The reaction and Robin terms are not part of the form."""
+        import torch
+
+        n = self.layout.size_local + self.layout.num_ghosts
+        args = []
+        for name, t in (("u", u), ("v", v)):
+            if isinstance(t, Vector):
+                t = t.data
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous():
+                raise TypeError(f"{name} must be a Vector or a contiguous float64 torch tensor")
+            if t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} entries, the layout {n}")
+            args.append(t)
+        if out is None:
+            out = torch.empty(self.ncells, dtype=torch.float64, device=self.layout.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_contiguous():
+                raise TypeError("out must be a contiguous float64 torch tensor")
+            if out.numel() != self.ncells:
+                raise ValueError(f"out has {out.numel()} entries, the operator {self.ncells} cells")
+        flags = (self.CELL_FORM_KAPPA if kappa else 0) | (self.CELL_FORM_CONSTRAINED if constrained else 0)
+        call("pmg_laplacian_cell_form", self._handle, vp(args[0].data_ptr()), vp(args[1].data_ptr()),
+             vp(out.data_ptr()), flags, current_stream())
+        return out
+
     def lift_cell_count(self) -> int:
         """Cells that hold a marked dof (the lifting's work list); -1 before the first ``apply_lifting``."""
         return int(_lib.lib().pmg_laplacian_lift_cell_count(self._handle))
