@@ -650,6 +650,28 @@ int pmg_laplacian_tensor_recomputed(pmg_laplacian op);
  * streams (every other degree: 0), -1 for NULL. */
 int pmg_laplacian_set_tensor_recompute_identity(pmg_laplacian op, int mode);
 int pmg_laplacian_tensor_recomputed_identity(pmg_laplacian op);
+/* One tensor per column where the Jacobian is constant in the column's direction (not in the reference).  Down a
+ * column of a trilinear cell J depends on the column's coordinate through the cell's coefficients c101, c011, c111
+ * alone.  Where they vanish -- the top face is a translate of the bottom face: boxes, tensor grids, octree cubes,
+ * meshes extruded from arbitrary quadrilaterals -- adj(J) adj(J)^T / |det J| is the same in every layer and only the
+ * layer's weight changes.  With the switch on, the kernels of the recomputed form at degrees 2 and 4 (the fused
+ * restrictions (2, 1) and (4, 2) included; degree 1, with two layers per column, is left out by measurement) decide per
+ * work item -- the cells one wavefront marches through together -- whether every
+ * column's two slopes are exactly zero, and then form the tensor once per item instead of once per layer; every other
+ * item runs the general march unchanged, so a mixed mesh takes both paths.  No promise from the caller and no second
+ * array; same result to rounding.  It is wider than the affine mode, which stays opt-in and separate.
+ * mode -1 (default): automatic -- on (profiles/column_tensor.md); 0: every item forms its tensor per layer; 1: on --
+ * PMG_ERR_INVALID if the operator's next application does not recompute its tensor (the branch has no meaning
+ * outside that form) or its degree is 1, nothing changes.  A request of -1 or 1 stands while the operator's state moves; it takes effect
+ * whenever the apply recomputes.  PMG_COLUMN_TENSOR=0 / 1 in the environment, read at creation, sets mode 0 / 1
+ * (without the error).  The choice is part of what a captured graph is keyed by.
+ * pmg_laplacian_column_tensor: 1 if the next application runs the kernels with the branch, 0 if not, -1 for NULL.
+ * pmg_laplacian_column_tensor_items: how many of the operator's work items qualify, and how many there are, counted
+ * on the device with the kernels' own test; for an operator of degree 2 or 4 that has built the form's cell coefficients
+ * (PMG_ERR_INVALID otherwise).  Allocates and reads back: not inside a stream capture. */
+int pmg_laplacian_set_column_tensor(pmg_laplacian op, int mode);
+int pmg_laplacian_column_tensor(pmg_laplacian op);
+int pmg_laplacian_column_tensor_items(pmg_laplacian op, long long* qualifying, long long* total, pmg_stream stream);
 /* Geometry batching (src/laplacian.hpp:383-396; examples/mat_free/main.cpp:34-50 --batch_size):
  * with batch_cells > 0 the tensor G is not kept; every application recomputes it for about
  * batch_cells cells at a time (rounded up to whole patches) into a buffer of that size, right

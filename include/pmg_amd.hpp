@@ -837,6 +837,13 @@ public:
           "MatFreeLaplacian: set_tensor_recompute_identity before the operator has seen an index map");
     check(pmg_laplacian_set_tensor_recompute_identity(_op, mode));
   }
+  /// The column-constant branch of the recomputed form (pmg_laplacian_set_column_tensor).
+  void set_column_tensor(int mode)
+  {
+    if (!_op)
+      throw std::runtime_error("MatFreeLaplacian: set_column_tensor before the operator has seen an index map");
+    check(pmg_laplacian_set_column_tensor(_op, mode));
+  }
   int degree() const { return _degree; }
   int geometry_degree() const { return _geom_degree; }
 

@@ -130,6 +130,9 @@ _SIGS = {
     "pmg_laplacian_tensor_recomputed": (C.c_int, [vp]),
     "pmg_laplacian_set_tensor_recompute_identity": (C.c_int, [vp, C.c_int]),
     "pmg_laplacian_tensor_recomputed_identity": (C.c_int, [vp]),
+    "pmg_laplacian_set_column_tensor": (C.c_int, [vp, C.c_int]),
+    "pmg_laplacian_column_tensor": (C.c_int, [vp]),
+    "pmg_laplacian_column_tensor_items": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp]),
     "pmg_laplacian_launches_per_apply": (C.c_int, [vp]),
     "pmg_laplacian_apply_streams": (C.c_int, [vp]),
     "pmg_laplacian_chain_available": (C.c_int, [vp]),
@@ -247,7 +250,7 @@ def nullspace_mode(mode) -> int:
 
 # functions whose int return value is a count, not a status
 _COUNT_FUNCS = {"pmg_multigrid_graph_replays", "pmg_amg_num_levels", "pmg_laplacian_geometry_bytes", "pmg_comm_rank", "pmg_comm_size", "pmg_comm_capture_overlaps", "pmg_cg_coefficients", "pmg_cg_compute_eigenvalues", "pmg_multigrid_apply_counts", "pmg_version",
-                "pmg_laplacian_degree", "pmg_multigrid_precision", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine", "pmg_laplacian_tensor_recomputed", "pmg_laplacian_tensor_recomputed_identity",
+                "pmg_laplacian_degree", "pmg_multigrid_precision", "pmg_laplacian_launches_per_apply", "pmg_laplacian_apply_streams", "pmg_laplacian_is_affine", "pmg_laplacian_tensor_recomputed", "pmg_laplacian_tensor_recomputed_identity", "pmg_laplacian_column_tensor",
                 "pmg_laplacian_has_coefficient_field", "pmg_laplacian_has_coefficient_tensor", "pmg_laplacian_has_reaction", "pmg_laplacian_has_robin", "pmg_laplacian_lift_cell_count",
                 "pmg_laplacian_chain_available", "pmg_laplacian_chain_form",
                 "pmg_laplacian_node_order", "pmg_laplacian_geometry_degree", "pmg_layout_forward_scatters",

@@ -145,6 +145,52 @@ bool recomputes_tensor(pmg_laplacian op)
   return recompute_possible(op) && recompute_wanted(op) && op->Ccell && op->batch_patches == 0
          && op->geometry_mode == 0 && !op->kfield && !op->ktensor && !op->chain_on;
 }
+// The column-constant branch of the form (TensorStream::column_constant, stiffness_layer.hpp): items whose Jacobian does
+// not change down their columns form the tensor once per item.  A switch of its own (pmg_laplacian_set_column_tensor),
+// automatic = on by measurement (profiles/column_tensor.md); it only means something where the apply recomputes.
+bool hoists_column_tensor(pmg_laplacian op)
+{
+  return column_branch(op->P) && recomputes_tensor(op) && op->column_tensor_request != 0;
+}
+// The kernels of the form read the request from W1's last entry (stiffness_column.hpp): written at creation and by the
+// setter.  Synchronous, on the default stream: not inside a stream capture.
+int store_column_switch(pmg_laplacian op)
+{
+  const double on = op->column_tensor_request != 0 ? 1.0 : 0.0;
+  PMG_HIP(hipMemcpy(op->W1 + 2 * op->nd, &on, sizeof(on), hipMemcpyHostToDevice));
+  return PMG_OK;
+}
+
+// How many of the operator's items qualify, by the predicate the apply evaluates (TensorStream::column_constant on the
+// lanes' values of an item, formed as the kernels form them): one wavefront per item, count[0] += qualifies,
+// count[1] += 1.
+template <int P>
+__global__ void __launch_bounds__(64)
+    column_items_kernel(const double* __restrict__ Ccell, const double* __restrict__ W1,
+                        const int32_t* __restrict__ pncell, unsigned long long* __restrict__ count)
+{
+  using Sh = Shape<P>;
+  constexpr int ND = Sh::ND, K = Sh::K, NQ2 = Sh::NQ2, CW = Sh::CW, ITEMS = Sh::ITEMS, WL = CW * NQ2;
+  static_assert(Sh::WPC == 1, "the recomputed form covers the one-wave-per-item shapes only");
+  const int p = blockIdx.x / ITEMS, it = blockIdx.x - p * ITEMS;
+  if (it >= (pncell[p] + CW - 1) / CW)
+    return;
+  const int lane = threadIdx.x;
+  const int lw = lane < WL ? lane : WL - 1; // (the lane's column, cell and slot: stiffness_column_kernel)
+  const int cw = lw / NQ2, ab = lw - cw * NQ2;
+  const int a = ab / ND, b = ab - a * ND;
+  const int slot = it * CW + cw;
+  const int slotc = slot < K ? slot : K - 1;
+  TensorStream<double2, ND, WL, GEO_RECOMPUTE, false, 0, false, 1> gs;
+  gs.prime_recompute(Ccell + ((size_t)p * K + slotc) * 24, W1[ND + a], W1[ND + b], W1[a] * W1[b], W1 + ND);
+  const bool constant = gs.column_constant();
+  if (lane == 0)
+  {
+    atomicAdd(&count[0], constant ? 1ull : 0ull);
+    atomicAdd(&count[1], 1ull);
+  }
+}
+
 // Ccell, built once when the form is first chosen (the geometry never changes)
 int ensure_cell_coefficients(pmg_laplacian op, hipStream_t s)
 {
@@ -362,10 +408,11 @@ long long laplacian_capture_state(pmg_laplacian op)
   // epoch counts both; the resident tensor is rebuilt in place, as everything else that follows the operator's data
   // (laplacian_data_changed states what follows what), so a graph over it stays valid)
   const long long field = op->batch_patches > 0 ? (op->kfield_epoch & 0x3fff) << 44 : 0;
-  // (recomputed tensor: another kernel, reading another array)
+  // (recomputed tensor: another kernel, reading another array; its column-constant branch: a value the kernels read, and
+  // keyed all the same, so that a graph is captured under the setting it replays)
   return ((long long)op->geometry_mode << 40) ^ ((long long)op->batch_patches << 8) ^ (long long)(op->have_diag ? 1 : 0)
          ^ (long long)(op->chain_on ? 2 : 0) ^ (long long)(op->react ? 4 : 0) ^ (long long)(recomputes_tensor(op) ? 8 : 0)
-         ^ field;
+         ^ (long long)(hoists_column_tensor(op) ? 16 : 0) ^ field;
 }
 
 PatchView laplacian_patches(pmg_laplacian op)
@@ -727,6 +774,10 @@ extern "C" int pmg_laplacian_create_curved(
   {
     std::vector<double> w1(wts);
     w1.insert(w1.end(), pts.begin(), pts.end());
+    // ... and the switch of the column-constant branch; PMG_COLUMN_TENSOR=0 / 1 sets it (measurements)
+    if (const char* e = std::getenv("PMG_COLUMN_TENSOR"))
+      op->column_tensor_request = e[0] != '0' ? 1 : 0;
+    w1.push_back(op->column_tensor_request != 0 ? 1.0 : 0.0);
     PMG_TRY(upload(&op->W1, w1.data(), w1.size(), s));
     PMG_HIP(hipStreamSynchronize(s)); // w1 goes out of scope
   }
@@ -925,6 +976,61 @@ extern "C" int pmg_laplacian_set_tensor_recompute_identity(pmg_laplacian op, int
 extern "C" int pmg_laplacian_tensor_recomputed_identity(pmg_laplacian op)
 {
   return op ? (recompute_identity_form(op->P) && recomputes_tensor(op) ? 1 : 0) : -1;
+}
+
+// The column-constant branch of the recomputed form.  The request stands while the operator's state moves: whether an
+// application takes the branch is decided where the form is (hoists_column_tensor).
+extern "C" int pmg_laplacian_set_column_tensor(pmg_laplacian op, int mode)
+{
+  PMG_REQUIRE(op && mode >= -1 && mode <= 1, "pmg_laplacian_set_column_tensor: bad argument");
+  if (mode == 1 && recomputes_tensor(op) && !column_branch(op->P))
+    return fail(PMG_ERR_INVALID, "pmg_laplacian_set_column_tensor: the recomputed form of degree %d has no "
+                                 "column-constant branch (degrees 2 and 4 have it)", op->P);
+  if (mode == 1 && !recomputes_tensor(op))
+    return fail(PMG_ERR_INVALID, "pmg_laplacian_set_column_tensor: the column-constant tensor is a branch of the "
+                                 "recomputed form, and this operator's apply does not recompute its tensor "
+                                 "(pmg_laplacian_set_tensor_recompute, pmg_laplacian_set_tensor_recompute_identity)");
+  const int before = op->column_tensor_request;
+  op->column_tensor_request = mode;
+  if ((before != 0) != (mode != 0))
+    PMG_TRY(store_column_switch(op));
+  return PMG_OK;
+}
+
+extern "C" int pmg_laplacian_column_tensor(pmg_laplacian op) { return op ? (hoists_column_tensor(op) ? 1 : 0) : -1; }
+
+extern "C" int pmg_laplacian_column_tensor_items(pmg_laplacian op, long long* qualifying, long long* total,
+                                                 pmg_stream stream)
+{
+  PMG_REQUIRE(op && qualifying && total, "pmg_laplacian_column_tensor_items: NULL argument");
+  PMG_REQUIRE(recompute_possible(op) && column_branch(op->P) && op->Ccell,
+              "pmg_laplacian_column_tensor_items: the operator has no recomputed form with the column-constant branch, "
+              "or has not chosen the form yet");
+  hipStream_t s = S(stream);
+  PMG_TRY(not_capturing(s, "pmg_laplacian_column_tensor_items: allocates and reads back, not inside a stream capture"));
+  unsigned long long* count = nullptr;
+  unsigned long long host[2] = {0, 0};
+  PMG_HIP(hipMalloc(&count, sizeof(host)));
+  int err = PMG_OK;
+  if (hipMemsetAsync(count, 0, sizeof(host), s) != hipSuccess)
+    err = fail(PMG_ERR_HIP, "pmg_laplacian_column_tensor_items: hipMemsetAsync failed");
+  if (err == PMG_OK && op->npatch > 0)
+    err = with_degree(op->P, [&](auto P) {
+      constexpr int p = decltype(P)::value;
+      if constexpr (recompute_kernel(p) && column_branch(p))
+        column_items_kernel<p><<<(unsigned)op->npatch * Shape<p>::ITEMS, 64, 0, s>>>(op->Ccell, op->W1, op->pncell, count);
+      return PMG_OK;
+    });
+  if (err == PMG_OK
+      && (hipGetLastError() != hipSuccess
+          || hipMemcpyAsync(host, count, sizeof(host), hipMemcpyDeviceToHost, s) != hipSuccess
+          || hipStreamSynchronize(s) != hipSuccess))
+    err = fail(PMG_ERR_HIP, "pmg_laplacian_column_tensor_items: the count failed");
+  (void)hipFree(count);
+  PMG_TRY(err);
+  *qualifying = (long long)host[0];
+  *total = (long long)host[1];
+  return PMG_OK;
 }
 
 extern "C" int pmg_laplacian_apply(pmg_laplacian op, double* in, double* out, pmg_stream stream)

@@ -57,7 +57,7 @@ struct pmg_laplacian_s
   bool has_sigma = false, has_robin = false;
   bool diag_computed = false;  // diag_inv came from pmg_laplacian_compute_diag_inverse (it follows a change of field)
   double* Gaff = nullptr;      // [nslots][6] constant tensor K K^T / detJ of each (affine) cell (K Kc K^T / detJ with a coefficient tensor)
-  double* W1 = nullptr;        // [2][nd] 1-D GLL weights, then the nodes on [0,1]
+  double* W1 = nullptr;        // [2][nd] + 1: 1-D GLL weights, the nodes on [0,1], the column-tensor switch (1 = on)
   // Recomputed tensor (pmg_laplacian_set_tensor_recompute, laplacian_recomputes_tensor): the apply of a trilinear
   // operator forms G in its layer march from Ccell instead of streaming it.  Ccell follows the geometry alone; it is
   // built when the form is first chosen (at creation where it is the default) and kept.
@@ -65,6 +65,7 @@ struct pmg_laplacian_s
   bool own_tables = false;     // the library built the coordinate element's tabulation and the weights itself
   int recompute_request = -1;  // -1 = automatic (per degree), 0 = always stream, 1 = recompute where eligible
   int recompute_identity_request = -1; // the same for degree 4 (pmg_laplacian_set_tensor_recompute_identity)
+  int column_tensor_request = -1;      // the column-constant branch of either form (pmg_laplacian_set_column_tensor): 0 = off
   bool all_affine = false;     // every listed cell is a parallelepiped
   int geometry_mode = 0;       // 0 = stored G (reference data structure), 1 = affine cells
   double* D = nullptr;         // [nd*nd]

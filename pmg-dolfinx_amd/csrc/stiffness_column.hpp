@@ -157,6 +157,11 @@ constexpr bool list_in_lds(int P) { return P == 5 || P == 7 || P == 8; }
 // the column kernel spills 62 registers at 128, with rho, 1 / rho in their place none (profiles/tensor_recompute_p4.md).
 // The streamed and the affine kernel of P = 4 keep their tables: their code objects are unchanged.
 constexpr bool transposes_by_identity(int P, int GEO) { return P == 5 || (P == 4 && GEO == GEO_RECOMPUTE); }
+// Degrees whose recomputed form has the column-constant branch (TensorStream::column_constant, stiffness_layer.hpp; the
+// fused kernels follow their fine degree).  Degree 1 is left out by measurement: two layers per column leave one tensor
+// to save, and with the branch its kernel was 2 us per cycle slower on a mesh where every item takes it (20.0 against
+// 19.1 us per launch, profiles/column_tensor.md) -- it keeps the code object it had.
+constexpr bool column_branch(int P) { return P == 2 || P == 4; }
 // minimum waves per SIMD the register allocation has to leave room for: two workgroups per CU up to
 // P = 4; the register-heavy degrees take what they need (profiles/kernel_resources_r02.md)
 template <int P, int GEO>
@@ -166,8 +171,8 @@ constexpr int min_waves_per_simd()
   return P <= 4 ? (2 * Shape<P>::NW + 3) / 4 : transposes_by_identity(P, GEO) ? 4 : 1;
 }
 // GEO: where the tensor comes from (stiffness_layer.hpp).  Gcell: the per-slot data of the two forms without a stream,
-// [slot][6] constant tensors (GEO_AFFINE) or [slot][24] trilinear coefficients (GEO_RECOMPUTE).  W1 [2][nd]: the 1-D GLL
-// weights, then the nodes.
+// [slot][6] constant tensors (GEO_AFFINE) or [slot][24] trilinear coefficients (GEO_RECOMPUTE).  W1 [2][nd] + 1: the 1-D
+// GLL weights, then the nodes, then the switch of the column-constant branch (non-zero = on).
 template <int P, int GEO, bool NT>
 __global__ void __launch_bounds__(Shape<P>::WTHREADS, (min_waves_per_simd<P, GEO>()))
     stiffness_column_kernel(const double* __restrict__ x, double* __restrict__ y,
@@ -350,6 +355,44 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (min_waves_per_simd<P, GEO
     unsigned lp[IDT || RCP ? (ND + 1) / 2 : 1];
     if constexpr (IDT || RCP)
       pack_positions(l, lp);
+    // Recomputed tensor: the wavefront decides for its item whether J is constant down every column (column_constant),
+    // outside the unrolled loop (inside it every layer holds both forms' operands).  hoisted: the item's tensor is formed
+    // once, ahead of the loop and without w_k, which multiplies the fluxes instead (beside the identity kap is the
+    // constant 1: no instruction more); otherwise the march is the one below.  The switch of the branch
+    // (pmg_laplacian_set_column_tensor) is one more entry of W1, behind the weights and the nodes: a scalar load per
+    // item from an array the march reads anyway, no kernel argument held through the loop (the null-ness of G, tried
+    // first, cost the degree-4 kernels 44 and 56 bytes of scratch).
+    if constexpr (RCP && column_branch(P))
+    {
+      auto march = [&](auto hoisted) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k)
+        {
+          double2 g01, g23, g45;
+          if constexpr (decltype(hoisted)::value)
+            gs.take_column(g01, g23, g45);
+          else
+            gs.take(k, W1[k], g01, g23, g45);
+          double fr, fs, ft;
+          layer_forward<ND, UNPAIRED, SHARED>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45,
+                                              decltype(hoisted)::value ? kap * W1[k] : kap, fr, fs, ft);
+          if constexpr (IDT)
+            layer_backward_identity<ND, UNPAIRED, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, rho_a, irho_a,
+                                                          rho_b, irho_b, Aq);
+          else
+            layer_backward<ND, UNPAIRED, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
+        }
+      };
+      if (W1[2 * ND] != 0.0 && gs.column_constant())
+      {
+        gs.hoist_column();
+        march(std::true_type{});
+      }
+      else
+        march(std::false_type{});
+    }
+    else
+    {
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
@@ -358,10 +401,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (min_waves_per_simd<P, GEO
       gs.take(k, AFF ? wab * W1[k] : RCP ? W1[k] : 0.0, g01, g23, g45);
       double fr, fs, ft;
       layer_forward<ND, UNPAIRED, SHARED>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, kap, fr, fs, ft);
-      if constexpr (IDT && RCP)
-        layer_backward_identity<ND, UNPAIRED, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, rho_a, irho_a, rho_b,
-                                                      irho_b, Aq);
-      else if constexpr (IDT)
+      if constexpr (IDT)
       {
         // the transposes as forward contractions of the scaled fluxes (see transposes_by_identity)
         *gr_w = fr * irho_a;
@@ -380,6 +420,7 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (min_waves_per_simd<P, GEO
       }
       else
         layer_backward<ND, UNPAIRED, SHARED>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
+    }
     }
     // Every lane adds (no branch: a conditional here lets the compiler sink the
     // whole accumulation into it and keep every layer's operands live); lanes

@@ -231,6 +231,8 @@ __device__ __forceinline__ unsigned packed_position(const unsigned* lp, int k)
 // dx/dzeta is constant: 15 values per lane, from which layer k forms J(zeta_k), adj(J), |det J| and the six entries
 // w_a w_b w_k adj(J) adj(J)^T / |det J| with the geometry kernels' own adjugate() and metric() -- the stored tensor to
 // rounding, no stream.  adj adj^T / det is homogeneous of degree one in J, so w_a w_b is folded into the 15 values.
+// Where the two slopes vanish in every lane of an item the tensor is formed once, ahead of the march (column_constant,
+// hoist_column, take_column; the callers branch, stiffness_column.hpp column_branch).
 template <typename T2, int ND, int WL, int GEO, bool FLAT, int LS, bool NT, int GD>
 struct TensorStream
 {
@@ -302,6 +304,55 @@ struct TensorStream
       jc[3][i] = fold * e1;
       jc[4][i] = fold * (c001 + c101 * xi + e1 * eta);
     }
+  }
+  // Trilinear cells: is J constant down every column of the item?  The slopes jc[1], jc[3] of
+  // every lane are exactly zero where the cells' zeta-cross coefficients c101, c011, c111 vanish: the top face is a
+  // translate of the bottom face (boxes, tensor grids, extruded meshes).  J, adj(J), det J, the reciprocal and
+  // adj adj^T / |det J| are then those of layer 0 in every layer, and only w_k changes.  Six compares and one ballot,
+  // wave-uniform; idle lanes and clamped slots hold copies of real columns, empty slots zeros: they decide with the rest.
+  __device__ __forceinline__ bool column_constant() const
+  {
+    static_assert(RCP);
+    bool varies = false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      varies = varies || jc[1][i] != 0 || jc[3][i] != 0;
+    return __builtin_amdgcn_ballot_w64(varies) == 0;
+  }
+  // ... then the tensor without w_k once per item, ahead of the march and in the storage of jc; the layers take it as
+  // it is (take_column) and w_k rides on the scale of the fluxes.  J is what take() forms with the slopes at zero, bit
+  // for bit; against take() the six entries differ by where w_k multiplies.
+  __device__ __forceinline__ void hoist_column()
+  {
+    static_assert(RCP);
+    T J[3][3], g[6];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+    {
+      J[i][0] = jc[0][i];
+      J[i][1] = jc[2][i];
+      J[i][2] = jc[4][i];
+    }
+    // (take()'s expressions, with its reciprocal and its guard: an empty slot still gives G = 0)
+    T K[3][3], detJ;
+    adjugate(J, K, detJ);
+    T r = __builtin_amdgcn_rcp(detJ);
+    r = fma(fma(-detJ, r, 1.0), r, r);
+    r = fma(fma(-detJ, r, 1.0), r, r);
+    metric(K, detJ > 0 ? r : 0, g);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+    {
+      jc[0][i] = g[i];
+      jc[1][i] = g[3 + i];
+    }
+  }
+  __device__ __forceinline__ void take_column(T2& g01, T2& g23, T2& g45) const
+  {
+    static_assert(RCP);
+    g01.x = jc[0][0], g01.y = jc[0][1];
+    g23.x = jc[0][2], g23.y = jc[1][0];
+    g45.x = jc[1][1], g45.y = jc[1][2];
   }
   __device__ __forceinline__ void fetch(int slot, int layer)
   {

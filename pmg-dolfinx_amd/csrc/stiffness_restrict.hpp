@@ -255,23 +255,55 @@ __global__ void __launch_bounds__(Shape<P>::WTHREADS, (restrict_waves_per_simd<P
     // (the fine positions as well: the epilogue needs them again)
     unsigned lp[(ND + 1) / 2];
     pack_positions(l, lp);
+    // (recomputed tensor: the item's tensor once, ahead of the loop, where J is constant down its columns; the switch
+    // is W1's last entry -- as in the column kernel)
+    if constexpr (RCP)
+    {
+      static_assert(column_branch(P), "a fused pair with the recomputed form and no column-constant branch");
+      auto march = [&](auto hoisted) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k)
+        {
+          double2 g01, g23, g45;
+          if constexpr (decltype(hoisted)::value)
+            gs.take_column(g01, g23, g45);
+          else
+            gs.take(k, W1[k], g01, g23, g45);
+          double fr, fs, ft;
+          layer_forward<ND, UNPAIRED, false>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45,
+                                             decltype(hoisted)::value ? kap * W1[k] : kap, fr, fs, ft);
+          if constexpr (IDT)
+          {
+            int av, bv;
+            coarse_point(ab, av, bv, ND);
+            layer_backward_identity<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, rho_a, sW[av],
+                                                         rho_b, sW[bv], Aq);
+          }
+          else
+            layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
+        }
+      };
+      if (W1[2 * ND] != 0.0 && gs.column_constant())
+      {
+        gs.hoist_column();
+        march(std::true_type{});
+      }
+      else
+        march(std::false_type{});
+    }
+    else
+    {
 #pragma unroll
     for (int k = 0; k < ND; ++k)
     {
       double2 g01, g23, g45;
-      gs.take(k, RCP ? W1[k] : 1.0, g01, g23, g45); // (W1[k] is wave-uniform, a scalar load)
+      gs.take(k, 1.0, g01, g23, g45);
       double fr, fs, ft;
       // (affine cells: W1[k] is wave-uniform, a scalar load)
       layer_forward<ND, UNPAIRED, false>(k, u, T, Dg, q_s, a, b, ab, g01, g23, g45, AFF ? W1[k] : kap, fr, fs, ft);
-      if constexpr (IDT)
-      {
-        int av, bv;
-        coarse_point(ab, av, bv, ND);
-        layer_backward_identity<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, rho_a, sW[av], rho_b,
-                                                     sW[bv], Aq);
-      }
-      else
-        layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
+      static_assert(!IDT, "the identity is taken beside the recomputed tensor only");
+      layer_backward<ND, UNPAIRED, false>(k, fr, fs, ft, T, Dg, gr_s, gs_s, a, b, ab, Aq);
+    }
     }
     // ---- the cell's share of the restricted residual.  w = share - A_cell z down the lane's column; the product is
     // dropped on Dirichlet rows (a select, no branch: see the column kernel's epilogue).

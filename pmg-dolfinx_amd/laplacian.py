@@ -394,6 +394,24 @@ class MatFreeLaplacian:
         """Does the next application of this degree-4 operator form G in the kernel?"""
         return bool(call("pmg_laplacian_tensor_recomputed_identity", self._handle))
 
+    def set_column_tensor(self, mode):
+        """The column-constant branch of the recomputed form (``pmg_laplacian_set_column_tensor``): items whose
+        Jacobian does not change down their columns form the tensor once instead of once per layer.  ``None`` / -1
+        automatic (on), ``False`` / 0, ``True`` / 1 (``PmgError`` on an operator whose apply does not recompute)."""
+        call("pmg_laplacian_set_column_tensor", self._handle, -1 if mode is None else int(mode))
+
+    def column_tensor(self) -> bool:
+        """Does the next application run the kernels with the column-constant branch?"""
+        return bool(call("pmg_laplacian_column_tensor", self._handle))
+
+    def column_tensor_items(self):
+        """(qualifying, total): the operator's work items that take the branch, counted with the kernels' own test."""
+        import ctypes
+
+        q, n = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        call("pmg_laplacian_column_tensor_items", self._handle, ctypes.byref(q), ctypes.byref(n), None)
+        return int(q.value), int(n.value)
+
     def launches_per_apply(self) -> int:
         return call("pmg_laplacian_launches_per_apply", self._handle)
 
