@@ -29,6 +29,11 @@
 // (pmg_laplacian_cell_form with kappa, marked dofs read as zero; not in the reference) beside u_m . y, u_m = u with its
 // marked entries zeroed, and their relative difference: the two are the same number, computed by two kernels.  It
 // combines with --kappa-field, --kappa-tensor and --curved (the reaction and Robin terms are not part of the form).
+// --form-gradients prints, after the apply, the three Euler sums of pmg_laplacian_form_gradients (marked dofs read as
+// zero; not in the reference) at u and a second vector v -- sum_c kappa_c d_kappa[c], sum_n kq_n d_field[n] and
+// sum_c T_c . d_tensor[c]: A_diff is linear in each coefficient -- beside u_m . (A_diff v_m) from an apply of the
+// operator without its reaction term, and their relative differences; sum_c sigma_c d_sigma[c] is printed beside
+// u_m . ((A - A_diff) v_m).  It combines with --kappa-field, --kappa-tensor, --reaction and --curved.
 // Single rank.
 #include "../common/box_mesh.hpp"
 #include "../common/rotating_tensor.hpp"
@@ -49,7 +54,7 @@ int main(int argc, char** argv)
 {
   int n = 16, degree = 1, nreps = 1000;
   std::size_t ndofs = 0;
-  bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false, cell_form = false;
+  bool mat_comp = false, kappa_field = false, kappa_tensor = false, lift = false, cell_form = false, form_gradients = false;
   bool neumann = false; // --neumann: no Dirichlet marker (the singular, pure Neumann operator)
   double reaction = 0.0; // S of --reaction; 0 = no term
   double robin = 0.0;    // A of --robin; 0 = no term
@@ -84,12 +89,14 @@ int main(int argc, char** argv)
       lift = true;
     else if (!std::strcmp(argv[i], "--cell-form"))
       cell_form = true;
+    else if (!std::strcmp(argv[i], "--form-gradients"))
+      form_gradients = true;
     else if (!std::strcmp(argv[i], "--batch_size"))
       batch_size = std::strtoull(next(), nullptr, 10);
     else
     {
       std::cout << "usage: mat_free [--n cells_per_direction | --ndofs N] [--degree P] [--nreps R] [--mat_comp] "
-                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift] [--neumann] [--cell-form]\n";
+                   "[--batch_size cells] [--kappa-field] [--kappa-tensor] [--reaction S] [--robin A] [--curved G] [--lift] [--neumann] [--cell-form] [--form-gradients]\n";
       return !std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h") ? 0 : 2;
     }
   }
@@ -114,7 +121,8 @@ int main(int argc, char** argv)
       std::fill(V.bc_marker.begin(), V.bc_marker.end(), std::int8_t(0));
 
     auto map = std::make_shared<const IndexMap>(V.ndofs, 0);
-    device_array<double> kappa(std::vector<double>(mesh.ncells(), 2.0)); // :132
+    const double kappa_value = 2.0; // :132
+    device_array<double> kappa(std::vector<double>(mesh.ncells(), kappa_value));
     if (curved < 0 || curved > PMG_MAX_GEOM_DEGREE)
       throw std::runtime_error("--curved takes a geometry degree 1..4");
     std::vector<double> gll_g(curved + 1), w_g(curved + 1);
@@ -135,15 +143,18 @@ int main(int argc, char** argv)
                                 bcells, bc.span(), batch_size);
     DeviceVector u(map, 1), y(map, 1);
     u.set(1.0);
+    std::vector<double> kt_h, sigma_h, kq_h; // host copies of the coefficients that are set (--form-gradients)
     if (kappa_tensor)
     {
-      device_array<double> kt(examples::rotating_tensor(mesh.xgeom, mesh.geom_dofmap));
+      kt_h = examples::rotating_tensor(mesh.xgeom, mesh.geom_dofmap);
+      device_array<double> kt(kt_h);
       op.handle(map); // the handle is created with the first index map the operator sees
       op.set_coefficient_tensor(kt.span()); // the library copies it
     }
     if (reaction > 0.0)
     {
-      device_array<double> sigma(examples::linear_reaction(mesh.xgeom, mesh.geom_dofmap, reaction));
+      sigma_h = examples::linear_reaction(mesh.xgeom, mesh.geom_dofmap, reaction);
+      device_array<double> sigma(sigma_h);
       op.handle(map);
       op.set_reaction(sigma.span()); // the library keeps the vector it builds from it
     }
@@ -172,6 +183,7 @@ int main(int argc, char** argv)
       DeviceVector kq(map, 1);
       kq.copy_from_host(kh);
       op.set_coefficient_field(kq);
+      kq_h = kh;
     }
     if (lift)
     {
@@ -226,6 +238,67 @@ int main(int argc, char** argv)
       std::printf("Cell form: sum_c e_c(u, u) = %.15e\n", energy);
       std::printf("Cell form: u_m . y = %.15e\n", dot);
       std::printf("Cell form: relative difference = %.3e\n", std::fabs(energy - dot) / std::fabs(dot));
+    }
+
+    if (form_gradients)
+    {
+      if (robin > 0.0)
+        throw std::runtime_error("--form-gradients does not combine with --robin");
+      const std::size_t nc = mesh.ncells();
+      std::vector<double> vh(V.ndofs);
+      for (std::size_t d = 0; d < vh.size(); ++d)
+        vh[d] = std::cos(2.0 + 2 * V.x[3 * d] - 3 * V.x[3 * d + 1] + 4 * V.x[3 * d] * V.x[3 * d + 2]);
+      DeviceVector v(map, 1), yv(map, 1), yd(map, 1);
+      v.copy_from_host(vh);
+      device_array<double> dk(nc), df((std::size_t)V.ndofs), dt(6 * nc), ds(nc);
+      op.form_gradients(u, v, dk.span(), df.span(), dt.span(), ds.span(), true);
+      op(v, yv); // A v
+      if (reaction > 0.0)
+        op.clear_reaction();
+      op(v, yd); // A_diff v
+      if (reaction > 0.0)
+      {
+        device_array<double> sigma(sigma_h);
+        op.set_reaction(sigma.span()); // the operator as it was
+      }
+      hip_check(hipDeviceSynchronize(), "sync");
+      const std::vector<double> dkh = dk.to_host(), dfh = df.to_host(), dth = dt.to_host(), dsh = ds.to_host(),
+                                uh = u.data_copy(), yvh = yv.data_copy(), ydh = yd.data_copy();
+      double s_kappa = 0.0, s_field = 0.0, s_tensor = 0.0, s_sigma = 0.0, dot = 0.0, dot_r = 0.0;
+      for (std::size_t c = 0; c < nc; ++c)
+      {
+        s_kappa += kappa_value * dkh[c];
+        if (kappa_tensor)
+          for (int k = 0; k < 6; ++k)
+            s_tensor += kt_h[6 * c + k] * dth[6 * c + k]; // (an off-diagonal entry of d_tensor counts both of the matrix)
+        else
+          s_tensor += dth[6 * c] + dth[6 * c + 3] + dth[6 * c + 5];
+        if (reaction > 0.0)
+          s_sigma += sigma_h[c] * dsh[c];
+      }
+      for (std::size_t d = 0; d < (std::size_t)V.ndofs; ++d)
+      {
+        s_field += (kappa_field ? kq_h[d] : 1.0) * dfh[d];
+        if (!V.bc_marker[d])
+        {
+          dot += uh[d] * ydh[d];
+          dot_r += uh[d] * (yvh[d] - ydh[d]);
+        }
+      }
+      auto rel = [](double a, double b) { return std::fabs(a - b) / std::fabs(b); };
+      std::printf("Form gradients: u_m . (A_diff v_m) = %.15e\n", dot);
+      std::printf("Form gradients: sum_c kappa_c d_kappa[c] = %.15e\n", s_kappa);
+      std::printf("Form gradients: sum_n kq_n d_field[n] = %.15e\n", s_field);
+      std::printf("Form gradients: sum_c T_c . d_tensor[c] = %.15e\n", s_tensor);
+      std::printf("Form gradients: relative difference (kappa) = %.3e\n", rel(s_kappa, dot));
+      std::printf("Form gradients: relative difference (field) = %.3e\n", rel(s_field, dot));
+      std::printf("Form gradients: relative difference (tensor) = %.3e\n", rel(s_tensor, dot));
+      if (reaction > 0.0)
+      {
+        std::printf("Form gradients: u_m . ((A - A_diff) v_m) = %.15e\n", dot_r);
+        std::printf("Form gradients: sum_c sigma_c d_sigma[c] = %.15e\n", s_sigma);
+        std::printf("Form gradients: relative difference (sigma) = %.3e\n", rel(s_sigma, dot_r));
+      }
     }
 
     if (mat_comp)

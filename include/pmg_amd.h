@@ -605,6 +605,48 @@ int pmg_laplacian_has_robin(pmg_laplacian op);
 #define PMG_CELL_FORM_CONSTRAINED  2  /* marked dofs of u and v read as zero: v^T (dA/dkappa_c) u of the BC-treated A */
 int pmg_laplacian_cell_form(pmg_laplacian op, const double* u, const double* v, double* out_cells,
                             int flags, pmg_stream stream);
+/* ---- coefficient gradients of the form: kappa, nodal field, tensor, reaction (not in the reference) ----
+ * The derivatives of v_m^T A u_m with respect to each coefficient that enters A linearly, from ONE kernel that forms
+ * the point geometry once.  At the point q of cell c, with K = adj(J), detJ = |det J|, du / dv the reference gradients
+ * of u / v, pu_d = sum_r K[r][d] du_r (pv likewise), T_c the cell's coefficient tensor (the identity when none is set),
+ * kq_q = kq[dof(c, q)] (1 when no field is set), kappa_c read at call time and t_q = pv . T_c pu, each output is the
+ * derivative with respect to its own coefficient, which is divided out; all the others stay in, as currently set:
+ *     d_kappa[c]     = sum_q (w_q / detJ) kq_q t_q                   (pmg_laplacian_cell_form without PMG_CELL_FORM_KAPPA)
+ *     d_field[n]     = sum over the points (c, q) with dof(c, q) = n, c in the operator's two cell lists, of
+ *                      kappa_c (w_q / detJ) t_q
+ *     d_tensor[c][k] = kappa_c sum_q (w_q / detJ) kq_q m_k,  k over (xx, xy, xz, yy, yz, zz), m_xx = pv_x pu_x,
+ *                      m_xy = pv_x pu_y + pv_y pu_x: a packed off-diagonal value fills two entries of the matrix
+ *     d_sigma[c]     = sum_q w_q detJ u_q v_q                        (the lumped cell mass form: the derivative of the
+ *                      d .* x term of pmg_laplacian_set_reaction)
+ * A gradient is defined whether or not its coefficient is currently set: it is then taken at kq = 1 or T = I.  For a
+ * functional J(x) of the solution of A x = b the adjoint gradients are minus these outputs with u = x,
+ * v = lambda = A^-1 dJ/dx and PMG_CELL_FORM_CONSTRAINED.  The Robin coefficient's sensitivity is not provided.
+ *
+ * `u`, `v`: device arrays of size_local + num_ghosts doubles, as for pmg_laplacian_cell_form; they may be the same
+ * array.  Each output is a device array or NULL: d_kappa [ncells], d_field [size_local + num_ghosts], d_tensor
+ * [ncells][6], d_sigma [ncells].  A NULL output is not computed and costs nothing.  The per-cell outputs get a value
+ * for EVERY cell of the dofmap, ghost cells and cells in neither cell list included; d_field sums over the cells of the
+ * two cell lists only, the cells the apply visits: entries that no listed cell touches are exactly 0.  d_field is NOT
+ * zero on marked dofs: the point on a marked node still sees the unmarked dofs of its lines.  On a ghost-layer
+ * partition the owned entries of d_field are complete; ghost entries hold this rank's cells only, as those of the
+ * computed diagonal do.
+ * `flags`: 0 or PMG_CELL_FORM_CONSTRAINED (marked dofs of u and v read as zero, by a select: a NaN in a marked entry
+ * stays out).  PMG_CELL_FORM_KAPPA and every other bit are refused.
+ * NO EXCHANGE, not collective: the ghost entries of u and v are read as they are.
+ * The geometry is formed in place from the mesh, so the call works in every state the cell form works in (curved
+ * cells, batched geometry, the affine mode, the chain form, either recompute switch).  With d_field given, one fill of
+ * d_field with zeros on `stream` comes first; then ONE kernel launch.  No host synchronisation and no allocation: the
+ * call can be captured.  The per-cell sums are taken in a fixed order without atomics: two calls on the same data give
+ * the same bytes, and an output has the same bytes whichever other outputs are requested beside it.  d_field is summed
+ * with FP64 atomics: it agrees to rounding from call to call.
+ * Refused with PMG_ERR_INVALID and nothing written: a NULL op, u or v; all four outputs NULL; an illegal flag bit; an
+ * output overlapping u, v or another output. */
+int pmg_laplacian_form_gradients(pmg_laplacian op, const double* u, const double* v,
+                                 double* d_kappa,  /* [ncells]                  or NULL */
+                                 double* d_field,  /* [size_local + num_ghosts] or NULL */
+                                 double* d_tensor, /* [ncells][6]               or NULL */
+                                 double* d_sigma,  /* [ncells]                  or NULL */
+                                 int flags, pmg_stream stream);
 int pmg_laplacian_degree(pmg_laplacian op);
 /* Geometry mode of the apply.  0 (default): the reference's data structure, the
  * stored tensor G[cell][q][6] is streamed (48 bytes per quadrature point).

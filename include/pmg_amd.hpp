@@ -821,6 +821,25 @@ public:
     check(pmg_laplacian_cell_form(handle(u.map()), u.array().data(), v.array().data(), out_device.data(), flags,
                                   nullptr));
   }
+  /// The derivatives of v_m^T A u_m with respect to kappa [ncells], the nodal field [size_local + num_ghosts], the
+  /// per-cell tensor [ncells][6] and the reaction coefficient [ncells] (pmg_laplacian_form_gradients; not in the
+  /// reference), each into its span of device memory; an empty span is an output that is not wanted and costs
+  /// nothing.  With `constrained` the marked dofs of u and v read as zero.  No exchange, as cell_form.  One fill (with
+  /// d_field) and one launch.
+  template <typename Vector>
+  void form_gradients(const Vector& u, const Vector& v, std::span<T> d_kappa, std::span<T> d_field,
+                      std::span<T> d_tensor, std::span<T> d_sigma, bool constrained = true)
+  {
+    require_same_map(u, v);
+    const std::size_t nc = _kappa.size();
+    if ((!d_kappa.empty() && d_kappa.size() != nc) || (!d_field.empty() && d_field.size() != u.array().size())
+        || (!d_tensor.empty() && d_tensor.size() != 6 * nc) || (!d_sigma.empty() && d_sigma.size() != nc))
+      throw std::runtime_error("MatFreeLaplacian::form_gradients: an output has the wrong size");
+    auto p = [](std::span<T> s) { return s.empty() ? nullptr : s.data(); };
+    check(pmg_laplacian_form_gradients(handle(u.map()), u.array().data(), v.array().data(), p(d_kappa), p(d_field),
+                                       p(d_tensor), p(d_sigma), constrained ? PMG_CELL_FORM_CONSTRAINED : 0,
+                                       nullptr));
+  }
   /// Recomputed tensor (pmg_laplacian_set_tensor_recompute): -1 automatic, 0 always stream, 1 recompute (an error on
   /// an operator that cannot).  The handle must exist.
   void set_tensor_recompute(int mode)

@@ -123,6 +123,7 @@ _SIGS = {
     "pmg_laplacian_set_robin": (C.c_int, [vp, C.c_int32, c_ip, c_bp, vp, vp]),
     "pmg_laplacian_has_robin": (C.c_int, [vp]),
     "pmg_laplacian_cell_form": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
+    "pmg_laplacian_form_gradients": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "pmg_laplacian_degree": (C.c_int, [vp]),
     "pmg_laplacian_is_affine": (C.c_int, [vp]),
     "pmg_laplacian_set_geometry_mode": (C.c_int, [vp, C.c_int]),

@@ -185,13 +185,6 @@ __global__ void robin_kernel(long long npoints, int nd, const int32_t* __restric
 int check_facets(pmg_laplacian op, const char* who, int32_t nfacets, const int32_t* facet_cells,
                  const int8_t* facet_local)
 {
-  if (op->listed.empty() && op->ncells > 0)
-  {
-    op->listed.assign(op->ncells, 0);
-    for (int32_t c : op->pcell_h)
-      if (c >= 0)
-        op->listed[c] = 1;
-  }
   for (int32_t i = 0; i < nfacets; ++i)
   {
     const int32_t c = facet_cells[i];

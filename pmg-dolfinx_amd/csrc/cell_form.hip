@@ -16,15 +16,6 @@ using namespace pmg;
 
 namespace
 {
-// the sum over the 64 lanes of a wavefront, in lane 0: a fixed tree
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    x += __shfl_down(x, off, 64);
-  return x;
-}
-
 // One thread per node, LiftShape's workgroups.  u and v of the cell are gathered into LDS through the ascending dofmap
 // (bc != nullptr: a marked dof reads as 0 in both); every thread contracts both with D along the three axes at its own
 // point, forms G_q and the point's term dv^T G_q du; the workgroup sums the terms of each of its cells.

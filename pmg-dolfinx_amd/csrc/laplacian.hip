@@ -753,6 +753,11 @@ extern "C" int pmg_laplacian_create_curved(
   }
   PMG_TRY(upload(&op->pcell, plan.pcell.data(), plan.pcell.size(), s));
   PMG_TRY(upload(&op->pncell, plan.pncell.data(), plan.pncell.size(), s));
+  op->listed.assign(ncells, 0);
+  for (int32_t c : op->pcell_h)
+    if (c >= 0)
+      op->listed[c] = 1;
+  PMG_TRY(upload(reinterpret_cast<char**>(&op->cell_listed), op->listed.data(), op->listed.size(), s));
   op->n_bzero = (int32_t)plan.bzero.size();
   PMG_TRY(upload(&op->bzero, plan.bzero.data(), plan.bzero.size(), s));
   PMG_TRY(upload(&op->poff, plan.poff.data(), plan.poff.size(), s));
@@ -881,6 +886,7 @@ extern "C" int pmg_laplacian_destroy(pmg_laplacian op)
   (void)hipFree(op->D32);
   (void)hipFree(op->diag32);
   (void)hipFree(op->lift_cells);
+  (void)hipFree(op->cell_listed);
   for (hipEvent_t e : op->prof_events)
     (void)hipEventDestroy(e);
   for (hipEvent_t e : {op->ev_fork, op->ev_order, op->ev_join})

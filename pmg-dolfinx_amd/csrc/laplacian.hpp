@@ -130,10 +130,13 @@ struct pmg_laplacian_s
   long long diag32_version = -1;
   // boundary data (boundary.hip): the listed cells that hold a marked dof, built on the first
   // pmg_laplacian_apply_lifting (n_lift < 0: not yet) and freed with the handle; which cells are listed at all
-  // (host, built on the first pmg_laplacian_assemble_neumann)
+  // (host, built at creation)
   int32_t* lift_cells = nullptr;
   int32_t n_lift = -1;
   std::vector<char> listed;
+  // the same on the device, one byte per cell of the dofmap, uploaded with the cell lists at creation: which cells the
+  // apply visits (pmg_laplacian_form_gradients sums d_field over them alone)
+  int8_t* cell_listed = nullptr;
 };
 
 namespace pmg
@@ -382,6 +385,15 @@ struct LiftShape
   static constexpr int CPW = N >= 64 ? 1 : (64 + N - 1) / N; // 8 cells at degree 1, 3 at degree 2
   static constexpr int THREADS = ((CPW * N + 63) / 64) * 64;
 };
+
+// the sum over the 64 lanes of a wavefront, in lane 0: a fixed tree (the cell-local kernels' per-cell sums)
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    x += __shfl_down(x, off, 64);
+  return x;
+}
 
 // do p[0, np) and q[0, nq) share memory?
 inline bool overlaps(const double* p, size_t np, const double* q, size_t nq)

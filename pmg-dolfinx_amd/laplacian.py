@@ -129,6 +129,10 @@ class MatFreeLaplacian:
              lc.ctypes.data_as(_lib.c_ip), lc.size, bc_.ctypes.data_as(_lib.c_ip), bc_.size, ptr(self.bc_marker),
              self.node_order, perm.ctypes.data_as(_lib.c_ip) if perm is not None else None, current_stream())
         self._handle = h
+        # bumped by every method that changes a coefficient other than kappa (set_coefficient_field,
+        # set_coefficient_tensor, set_reaction, set_robin), before the library is called: a refused call leaves the
+        # count ahead, the safe side for adjoint.solve's staleness guard
+        self.coefficient_epoch = 0
 
     @property
     def handle(self):
@@ -170,6 +174,7 @@ class MatFreeLaplacian:
         the values at the dofs (all finite and > 0; its ghost entries are not read, the library scatters its own
         copy), or ``None`` to remove the field.  The tensor, its float form and a computed inverse diagonal are
         rebuilt; not inside a stream capture."""
+        self.coefficient_epoch += 1
         if v is None:
             call("pmg_laplacian_set_coefficient_field", self._handle, None, current_stream())
             return
@@ -190,6 +195,7 @@ class MatFreeLaplacian:
         (xx, xy, xz, yy, yz, zz) in physical coordinates; or ``None`` to remove the tensor.  The library copies it.
         The stored tensor, its float and affine forms and a computed inverse diagonal are rebuilt; not inside a
         stream capture."""
+        self.coefficient_epoch += 1
         import torch
 
         if t is None:
@@ -216,6 +222,7 @@ class MatFreeLaplacian:
         ``sigma`` is a float64 numpy array (uploaded here) or torch tensor of shape ``(ncells,)``, one finite value
         >= 0 per local cell, ghost cells included; or ``None`` to remove the term.  The library keeps d, not sigma.  A
         computed inverse diagonal is rebuilt; not inside a stream capture."""
+        self.coefficient_epoch += 1
         import torch
 
         if sigma is None:
@@ -303,6 +310,7 @@ class MatFreeLaplacian:
         uploaded here, or a float64 device tensor).  ``cells`` of length 0 or ``alpha=None`` removes the term.  The
         data g enters the right-hand side through ``assemble_neumann`` with ``h = g``.  A computed inverse diagonal is
         rebuilt; collective on several ranks; not inside a stream capture."""
+        self.coefficient_epoch += 1
         import torch
 
         cells = np.ascontiguousarray(cells if cells is not None else [], dtype=np.int32)
@@ -361,6 +369,55 @@ class MatFreeLaplacian:
         call("pmg_laplacian_cell_form", self._handle, vp(args[0].data_ptr()), vp(args[1].data_ptr()),
              vp(out.data_ptr()), flags, current_stream())
         return out
+
+    GRADIENTS = ("kappa", "field", "tensor", "sigma")  # the outputs of pmg_laplacian_form_gradients, in its order
+
+    def form_gradients(self, u, v, kappa: bool = False, field: bool = False, tensor: bool = False,
+                       sigma: bool = False, constrained: bool = True, out=None):
+        """The derivatives of ``v_m^T A u_m`` with respect to the coefficients (``pmg_laplacian_form_gradients``), for
+        the names requested: ``kappa`` [ncells], ``field`` [size_local + num_ghosts] (the nodal coefficient),
+        ``tensor`` [ncells, 6] and ``sigma`` [ncells] (the reaction coefficient).  Each coefficient's own value is
+        divided out, the others stay in as currently set; a gradient exists whether or not its coefficient is set.
+        With ``constrained=True`` the marked dofs of ``u`` and ``v`` read as zero.  ``u`` and ``v`` are as in
+        ``cell_form``: no exchange.  ``out`` may hold contiguous float64 device tensors for some of the requested
+        names; the others are made here.  Returns a dict name -> tensor.  One fill (with ``field``) and one launch;
+        capturable."""
+        import torch
+
+        n = self.layout.size_local + self.layout.num_ghosts
+        args = []
+        for name, t in (("u", u), ("v", v)):
+            if isinstance(t, Vector):
+                t = t.data
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous():
+                raise TypeError(f"{name} must be a Vector or a contiguous float64 torch tensor")
+            if t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} entries, the layout {n}")
+            args.append(t)
+        shapes = {"kappa": (self.ncells,), "field": (n,), "tensor": (self.ncells, 6), "sigma": (self.ncells,)}
+        wanted = dict(zip(self.GRADIENTS, (kappa, field, tensor, sigma)))
+        if not any(wanted.values()):
+            raise ValueError("form_gradients: no gradient requested")
+        out = dict(out) if out is not None else {}
+        if set(out) - {k for k in self.GRADIENTS if wanted[k]}:
+            raise ValueError(f"out names {sorted(set(out) - {k for k in self.GRADIENTS if wanted[k]})}, which "
+                             "are not requested")
+        res = {}
+        for name in self.GRADIENTS:
+            if not wanted[name]:
+                continue
+            t = out.get(name)
+            if t is None:
+                t = torch.empty(shapes[name], dtype=torch.float64, device=self.layout.device)
+            elif not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous():
+                raise TypeError(f"out[{name!r}] must be a contiguous float64 torch tensor")
+            elif t.numel() != int(np.prod(shapes[name])):
+                raise ValueError(f"out[{name!r}] has {t.numel()} entries, the gradient {int(np.prod(shapes[name]))}")
+            res[name] = t
+        ptrs = [vp(res[k].data_ptr()) if k in res else None for k in self.GRADIENTS]
+        call("pmg_laplacian_form_gradients", self._handle, vp(args[0].data_ptr()), vp(args[1].data_ptr()), *ptrs,
+             self.CELL_FORM_CONSTRAINED if constrained else 0, current_stream())
+        return res
 
     def lift_cell_count(self) -> int:
         """Cells that hold a marked dof (the lifting's work list); -1 before the first ``apply_lifting``."""
